@@ -158,10 +158,15 @@ def main():
     ap.add_argument("--no-time-to-cov", action="store_true", help="skip the nsqMain runs (profiling: only identical launches)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="scenarios of the CPU baseline sample (0 = auto)")
     ap.add_argument("--dump-acc", default="", help="testing: rank 0 writes the merged accumulators of the timed steps to this file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step returned (its all-reduced relmc_acc; the seq workload adds the annual indices) "
+                         "to DIR/<name>.npy, float64")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and "RANK" not in os.environ:
         if args.gpus > 1:
@@ -314,7 +319,7 @@ def main():
                 lo, cnt = (k * world + rank) * B, B        # global scenario index space: step k, rank r owns [(k*world + r)*B, +B)
             acc = eng.nsq_accumulate(args.seed, lo, cnt, opts)
             ms = eng.last_kernel_ms()
-            return allreduce(acc), ms, cnt                 # the convergence check's single all-reduce
+            return allreduce(acc), ms, cnt, {}             # the convergence check's single all-reduce
         unit = "scenarios/s"
         if args.workload == "nsq24":
             metric = "Monte Carlo DC-OPF scenarios/sec (RTS-24 HL2 non-sequential)"
@@ -335,11 +340,12 @@ def main():
             ms = eng.last_kernel_ms()
             trip = np.column_stack([e, d, n_])
             if comm is not None:
-                comm.allgather_rows(trip, [Y] * world)          # relmc_comm_allreduce_f64: every rank fills its own rows of a zeroed matrix
+                trip = comm.allgather_rows(trip, [Y] * world)   # relmc_comm_allreduce_f64: every rank fills its own rows of a zeroed matrix
             elif world > 1:
                 with guard("torch.distributed.all_gather of the annual indices"):
-                    rdist.allgather_years(trip, [Y] * world, device)
-            return allreduce(acc), ms, int(acc.n)
+                    trip = rdist.allgather_years(trip, [Y] * world, device)
+            n_rank = int(acc.n)
+            return allreduce(acc), ms, n_rank, {"year_ens": trip[:, 0], "year_dlc": trip[:, 1], "year_nlc": trip[:, 2]}
         unit, metric = "hourly DC-OPFs/s", "Monte Carlo hourly DC-OPF evaluations/sec (RTS-24 HL2 sequential)"
         workload = f"HL2 sequential MCS, RTS-24, {Y} simulated years x 8736 h per GPU per step, contingency hours only (BASELINE configs[3] shape)"
 
@@ -349,11 +355,13 @@ def main():
     t0 = time.perf_counter()
     total, kernel_ms, units_rank = None, [], 0
     for k in range(args.steps):
-        acc, ms, u = step(args.warmup + k)
+        acc, ms, u, arrays = step(args.warmup + k)
         kernel_ms.append(ms); units_rank += u
         total = acc if total is None else rdist.merge(total, acc)
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, acc, arrays, case)
     kernel_ms_per_rank = [sum(kernel_ms) / len(kernel_ms)]
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if pg_backend == "nccl" else "cpu")
@@ -540,6 +548,22 @@ def main():
     if rdist.abandoned_threads() or rdist.kept_forever():
         sys.stdout.flush(); sys.stderr.flush()
         os._exit(0)              # a helper thread is still inside a stalled RCCL call: do not wait for it at interpreter exit
+
+
+def dump_outputs(out_dir, acc, arrays, case):
+    """The last timed step's result as DIR/<name>.npy (float64): the relmc_acc fields, trimmed to the case's components and buses, plus the
+    workload's own arrays.  The scenario indices of a step depend on (--seed, --warmup, --steps, --batch / --total / --years, --gpus) only,
+    so two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    counts = [acc.n, acc.n_fail, acc.n_singular, acc.n_infeasible, acc.n_nonconverged, acc.sum_iters, acc.n_screened]
+    out = {"acc_counts": np.array(counts, dtype=np.float64),                # n, n_fail, n_singular, n_infeasible, n_nonconverged, sum_iters, n_screened
+           "acc_comp_fail": np.array(acc.comp_fail[:case.ncomp], dtype=np.float64),
+           "acc_sum_dns": np.array([acc.sum_dns, acc.sum_dns2], dtype=np.float64),
+           "acc_sum_nodal": np.array(acc.sum_nodal[:case.nb], dtype=np.float64)}
+    out.update({k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()})
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def sustained_rate(eng, opts, seed, n):

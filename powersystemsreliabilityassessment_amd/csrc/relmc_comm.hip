@@ -144,8 +144,6 @@ void comm_free(relmc_ctx* ctx)
     }
     if (ctx->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(ctx->comm);
     ctx->comm = nullptr;
-    if (ctx->dgather) (void)hipFree(ctx->dgather);
-    ctx->dgather = nullptr; ctx->gather_doubles = 0;
 }
 
 int comm_allreduce_f64(relmc_ctx* ctx, double* buf, int64_t count)
@@ -178,17 +176,12 @@ int comm_allreduce_f64(relmc_ctx* ctx, double* buf, int64_t count)
         return RELMC_OK;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((size_t)count > ctx->gather_doubles) {
-        if (ctx->dgather) (void)hipFree(ctx->dgather);
-        ctx->dgather = nullptr; ctx->gather_doubles = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->dgather, sizeof(double) * (size_t)count));
-        ctx->gather_doubles = (size_t)count;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->dgather, buf, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, ctx->dgather.grow((size_t)count));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dgather.get(), buf, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
     Guard g(ctx, "ncclAllReduce (annual indices)", ctx->comm_nranks, ctx->comm_rank);
-    const int rc = g_rccl.AllReduce(ctx->dgather, ctx->dgather, (size_t)count, /*ncclFloat64*/ 8, /*ncclSum*/ 0, ctx->comm, ctx->stream);
+    const int rc = g_rccl.AllReduce(ctx->dgather.get(), ctx->dgather.get(), (size_t)count, /*ncclFloat64*/ 8, /*ncclSum*/ 0, ctx->comm, ctx->stream);
     if (rc != 0) return rccl_fail(ctx, "ncclAllReduce", rc);
-    HIP_TRY(ctx, hipMemcpyAsync(buf, ctx->dgather, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(buf, ctx->dgather.get(), sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RELMC_OK;
 }
@@ -287,10 +280,10 @@ int32_t relmc_comm_allreduce_acc(relmc_ctx* ctx, relmc_acc* acc)
     }
     if (!ctx->comm) return fail(ctx, RELMC_ERR_INVALID, "relmc_comm_allreduce_acc: relmc_comm_init has not been called");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->dacc, acc, sizeof(*acc), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dacc.get(), acc, sizeof(*acc), hipMemcpyHostToDevice, ctx->stream));
     constexpr size_t NI = 6 + RELMC_MAX_COMP + 1, ND = 2 + RELMC_MAX_BUS;
     static_assert(sizeof(relmc_acc) == 8 * (NI + ND), "relmc_acc = NI int64 then ND doubles");
-    long long* di = reinterpret_cast<long long*>(ctx->dacc);
+    long long* di = reinterpret_cast<long long*>(ctx->dacc.get());
     double* dd = reinterpret_cast<double*>(di + NI);
     Guard g(ctx, "ncclAllReduce (relmc_acc)", ctx->comm_nranks, ctx->comm_rank);
     int rc = g_rccl.GroupStart();
@@ -298,7 +291,7 @@ int32_t relmc_comm_allreduce_acc(relmc_ctx* ctx, relmc_acc* acc)
     if (rc == 0) rc = g_rccl.AllReduce(dd, dd, ND, /*ncclFloat64*/ 8, /*ncclSum*/ 0, ctx->comm, ctx->stream);
     const int rc2 = g_rccl.GroupEnd();
     if (rc != 0 || rc2 != 0) return rccl_fail(ctx, "ncclAllReduce", rc ? rc : rc2);
-    HIP_TRY(ctx, hipMemcpyAsync(acc, ctx->dacc, sizeof(*acc), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(acc, ctx->dacc.get(), sizeof(*acc), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RELMC_OK;
 }

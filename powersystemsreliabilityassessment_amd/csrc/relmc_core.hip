@@ -50,16 +50,6 @@ int grid_for(relmc_ctx* ctx, int64_t n)
     return (int)g;
 }
 
-int ensure_partial(relmc_ctx* ctx, size_t bytes)
-{
-    if (bytes <= ctx->partial_bytes) return RELMC_OK;
-    if (ctx->dpartial) (void)hipFree(ctx->dpartial);
-    ctx->dpartial = nullptr; ctx->partial_bytes = 0;
-    HIP_TRY(ctx, hipMalloc(&ctx->dpartial, bytes));
-    ctx->partial_bytes = bytes;
-    return RELMC_OK;
-}
-
 // launches the evaluation kernel of one tile; *rows_out = scenario rows holding partial accumulators
 template <int MODE, class TL>
 int launch_eval_t(relmc_ctx* ctx, EvalArgs& a, int* rows_out, hipEvent_t ev_start, hipEvent_t ev_stop, int alt)
@@ -68,32 +58,26 @@ int launch_eval_t(relmc_ctx* ctx, EvalArgs& a, int* rows_out, hipEvent_t ev_star
     if (MODE == 6) {
         // dense last resort: [scenario rows of the grid][2 nb (2 nb + 1)] doubles of scratch; a small grid keeps it small (the units are few)
         if (blocks > 64) blocks = 64;
-        const size_t n = 2 * (size_t)ctx->nb, stride = n * (n + 1), need = sizeof(double) * stride * (size_t)blocks * TL::WPB * TL::SPW;
-        if (need > ctx->dense_bytes) {
-            if (ctx->ddense) (void)hipFree(ctx->ddense);
-            ctx->ddense = nullptr; ctx->dense_bytes = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->ddense, need));
-            ctx->dense_bytes = need;
-        }
-        a.dense = ctx->ddense; a.dense_stride = stride;
+        const size_t n = 2 * (size_t)ctx->nb, stride = n * (n + 1), need = stride * (size_t)blocks * TL::WPB * TL::SPW;
+        HIP_TRY(ctx, ctx->retry.dense.grow(need));
+        a.dense = ctx->retry.dense.get(); a.dense_stride = stride;
     }
-    int rc = ensure_partial(ctx, sizeof(PartialT<TL>) * 64 * TL::WPB * (size_t)blocks);
-    if (rc) return rc;
-    a.partial = ctx->dpartial;
+    HIP_TRY(ctx, ctx->dpartial.grow(sizeof(PartialT<TL>) * 64 * TL::WPB * (size_t)blocks));
+    a.partial = ctx->dpartial.get();
     a.scen_doubles = alt ? ctx->alt_scen_doubles[alt - 1] : ctx->scen_doubles;
     // the grid fills the device: first-dispatched and later wavefronts share every SIMD (see the kernel's priority balancing)
     a.prio_mode = blocks != ctx->num_cu * ctx->blocks_per_cu ? 0u : (ctx->blocks_per_cu == 2 ? 1u : (ctx->blocks_per_cu == 1 && TL::WPB >= 8 ? 2u : 0u));
     a.stash_off = alt ? ctx->alt_stash_off[alt - 1] : ctx->stash_off;
     a.case_bytes = (uint32_t)offsetof(DevCaseT<TL>, task);
 #if defined(RELMC_PHASE_TIMING) || defined(RELMC_TRACE)
-    if (!ctx->dtiming) HIP_TRY(ctx, hipMalloc(&ctx->dtiming, sizeof(unsigned long long) * 8 * 65536));
-    a.timing = ctx->dtiming; ctx->timing_waves = blocks * TL::WPB;
+    HIP_TRY(ctx, ctx->dtiming.grow(8 * 65536));
+    a.timing = ctx->dtiming.get(); ctx->timing_waves = blocks * TL::WPB;
 #else
     a.timing = nullptr;
 #endif
     HIP_TRY(ctx, hipEventRecord(ev_start ? ev_start : ctx->ev0, ctx->stream));
     hipLaunchKernelGGL((relmc_eval_kernel<MODE, TL>), dim3(blocks), dim3(64 * TL::WPB), alt ? ctx->alt_lds_bytes[alt - 1] : ctx->lds_bytes, ctx->stream,
-                       reinterpret_cast<const DevCaseT<TL>*>(alt ? ctx->dcase_alt[alt - 1] : ctx->dcase), a);
+                       reinterpret_cast<const DevCaseT<TL>*>(alt ? ctx->dcase_alt[alt - 1].get() : ctx->dcase.get()), a);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ev_stop ? ev_stop : ctx->ev1, ctx->stream));
     *rows_out = blocks * TL::WPB * TL::SPW;
@@ -139,11 +123,11 @@ int launch_eval(relmc_ctx* ctx, int mode, EvalArgs& a, int* rows_out, hipEvent_t
 int launch_finalize(relmc_ctx* ctx, int rows)
 {
     if (ctx->tile == 0)
-        hipLaunchKernelGGL(relmc_finalize_kernel<Tile24>, dim3(FIN_ITEMS), dim3(FIN_THREADS), 0, ctx->stream, reinterpret_cast<const DevCaseT<Tile24>*>(ctx->dcase),
-                           reinterpret_cast<const PartialT<Tile24>*>(ctx->dpartial), rows, ctx->dacc);
+        hipLaunchKernelGGL(relmc_finalize_kernel<Tile24>, dim3(FIN_ITEMS), dim3(FIN_THREADS), 0, ctx->stream, reinterpret_cast<const DevCaseT<Tile24>*>(ctx->dcase.get()),
+                           reinterpret_cast<const PartialT<Tile24>*>(ctx->dpartial.get()), rows, ctx->dacc.get());
     else
-        hipLaunchKernelGGL(relmc_finalize_kernel<Tile96>, dim3(FIN_ITEMS), dim3(FIN_THREADS), 0, ctx->stream, reinterpret_cast<const DevCaseT<Tile96>*>(ctx->dcase),
-                           reinterpret_cast<const PartialT<Tile96>*>(ctx->dpartial), rows, ctx->dacc);
+        hipLaunchKernelGGL(relmc_finalize_kernel<Tile96>, dim3(FIN_ITEMS), dim3(FIN_THREADS), 0, ctx->stream, reinterpret_cast<const DevCaseT<Tile96>*>(ctx->dcase.get()),
+                           reinterpret_cast<const PartialT<Tile96>*>(ctx->dpartial.get()), rows, ctx->dacc.get());
     HIP_TRY(ctx, hipGetLastError());
     return RELMC_OK;
 }
@@ -178,12 +162,12 @@ int case_load_impl(relmc_ctx* ctx, const relmc_case_desc* d, DevCaseT<TL>& C, in
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (alt) {
         const int v = order_variant - 1;
-        if (!ctx->dcase_alt[v]) HIP_TRY(ctx, hipMalloc(&ctx->dcase_alt[v], sizeof(DevCaseT<Tile96>) > sizeof(DevCaseT<Tile24>) ? sizeof(DevCaseT<Tile96>) : sizeof(DevCaseT<Tile24>)));
+        HIP_TRY(ctx, ctx->dcase_alt[v].grow(relmc_ctx::kCaseBytes));
         ctx->alt_stash_off[v] = stash_off; ctx->alt_scen_doubles[v] = scen; ctx->alt_lds_bytes[v] = lds_bytes;
         uint32_t most = ctx->lds_bytes;
         for (int q = 0; q < relmc_ctx::kAlt; ++q) if (ctx->alt_lds_bytes[q] > most) most = ctx->alt_lds_bytes[q];
         { const int rc = eval_set_lds<TL>(ctx, (int)most); if (rc) return rc; }
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->dcase_alt[v], &C, sizeof(C), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->dcase_alt[v].get(), &C, sizeof(C), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         return RELMC_OK;
     }
@@ -192,7 +176,7 @@ int case_load_impl(relmc_ctx* ctx, const relmc_case_desc* d, DevCaseT<TL>& C, in
     int bpc = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, relmc_eval_kernel<0, TL>, 64 * WPB, ctx->lds_bytes) != hipSuccess || bpc < 1) bpc = 1;
     ctx->blocks_per_cu = bpc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->dcase, &C, sizeof(C), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dcase.get(), &C, sizeof(C), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->nb = nb; ctx->ng = ng; ctx->nl = nl; ctx->ncomp = ncomp;
     ctx->has_seq = false;
@@ -220,19 +204,20 @@ int order_probe(relmc_ctx* ctx, int alt, int32_t* failures)
     EvalArgs a = make_args(o);
     a.seed = 0x5eedca5eull; a.first_index = 0; a.n = kProbeSamples;
     {
-        const int rc0 = fail_list_ensure(ctx, fail_cap_for(kProbeSamples) > ctx->fail_cap ? fail_cap_for(kProbeSamples) : ctx->fail_cap);
+        const int rc0 = fail_list_ensure(ctx, fail_cap_for(kProbeSamples));
         if (rc0) return rc0;
     }
-    HIP_TRY(ctx, hipMemsetAsync(ctx->dfail_count, 0, sizeof(uint32_t), ctx->stream));
-    a.fail_list = ctx->dfail; a.fail_count = ctx->dfail_count; a.fail_cap = ctx->fail_cap; a.unit_base = 0;
+    auto& R = ctx->retry;
+    HIP_TRY(ctx, hipMemsetAsync(R.fail_count.get(), 0, sizeof(uint32_t), ctx->stream));
+    a.fail_list = R.fail.get(); a.fail_count = R.fail_count.get(); a.fail_cap = (uint32_t)R.fail.size(); a.unit_base = 0;
     int rows = 0;
     int rc = launch_eval(ctx, 5, a, &rows, nullptr, nullptr, alt);      // MODE 5 = MODE 0 under its own kernel name
     if (rc) return rc;
     uint32_t cnt = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&cnt, ctx->dfail_count, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&cnt, R.fail_count.get(), sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemset(ctx->dfail_count, 0, sizeof(uint32_t)));
-    ctx->fail_dirty = false;
+    HIP_TRY(ctx, hipMemset(R.fail_count.get(), 0, sizeof(uint32_t)));
+    R.fail_dirty = false;
     *failures = (int32_t)cnt;
     return RELMC_OK;
 }
@@ -257,8 +242,8 @@ int order_calibrate(relmc_ctx* ctx)
         std::swap(ctx->scen_doubles, ctx->alt_scen_doubles[v]); std::swap(ctx->lds_bytes, ctx->alt_lds_bytes[v]); std::swap(ctx->stash_off, ctx->alt_stash_off[v]);
         std::swap(ctx->conflict_before, ctx->alt_conflict_before[v]); std::swap(ctx->conflict_after, ctx->alt_conflict_after[v]);
         // the host copy follows the image that runs: relmc_debug_schedule (and with it bench.py's operation count) describes the active schedule
-        if (ctx->tile == 0) HIP_TRY(ctx, hipMemcpy(&ctx->hcase24, ctx->dcase, sizeof(ctx->hcase24), hipMemcpyDeviceToHost));
-        else HIP_TRY(ctx, hipMemcpy(&ctx->hcase96, ctx->dcase, sizeof(ctx->hcase96), hipMemcpyDeviceToHost));
+        if (ctx->tile == 0) HIP_TRY(ctx, hipMemcpy(&ctx->hcase24, ctx->dcase.get(), sizeof(ctx->hcase24), hipMemcpyDeviceToHost));
+        else HIP_TRY(ctx, hipMemcpy(&ctx->hcase96, ctx->dcase.get(), sizeof(ctx->hcase96), hipMemcpyDeviceToHost));
         ctx->order_primary = best;
         int bpc = 0; hipError_t e = hipSuccess;
         const int lds = (int)ctx->lds_bytes;
@@ -300,8 +285,7 @@ int32_t relmc_ctx_create(int32_t device_id, relmc_ctx** out)
     if (hipSetDevice(device_id) != hipSuccess || hipGetDeviceProperties(&prop, device_id) != hipSuccess ||
         hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
-        hipMalloc(&ctx->dcase, sizeof(DevCaseT<Tile96>) > sizeof(DevCaseT<Tile24>) ? sizeof(DevCaseT<Tile96>) : sizeof(DevCaseT<Tile24>)) != hipSuccess || hipMalloc(&ctx->dacc, sizeof(DevAcc)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&ctx->hstage), sizeof(relmc_ctx::HostStage), hipHostMallocDefault) != hipSuccess) {
+        ctx->dcase.grow(relmc_ctx::kCaseBytes) != hipSuccess || ctx->dacc.grow(1) != hipSuccess || ctx->hstage.grow(1) != hipSuccess) {
         relmc_ctx_destroy(ctx);          // releases whatever was created before the failure
         return RELMC_ERR_NO_DEVICE;
     }
@@ -318,25 +302,12 @@ void relmc_ctx_destroy(relmc_ctx* ctx)
 {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    if (ctx->dpartial) (void)hipFree(ctx->dpartial);
-    if (ctx->dcase) (void)hipFree(ctx->dcase);
-    if (ctx->dacc) (void)hipFree(ctx->dacc);
-    if (ctx->hstage) (void)hipHostFree(ctx->hstage);
-    if (ctx->dtiming) (void)hipFree(ctx->dtiming);
-    if (ctx->dhist) (void)hipFree(ctx->dhist);
-    if (ctx->hhist) (void)hipHostFree(ctx->hhist);
-    for (void* p : {ctx->dcase_alt[0], ctx->dcase_alt[1]}) if (p) (void)hipFree(p);
-    retry_free(ctx);
-    seq_free(ctx);
-    screen_free(ctx);
     comm_free(ctx);
-    pipe_free(ctx);
-    memo_free(ctx);
-    db_free(ctx);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    const auto& P = ctx->pipe;
+    for (hipEvent_t e : {ctx->ev0, ctx->ev1, ctx->screen_ev0, ctx->screen_ev1, P.e_up[0], P.e_up[1], P.e_ks[0], P.e_ks[1], P.e_ke[0], P.e_ke[1], P.e_down[0], P.e_down[1]})
+        if (e) (void)hipEventDestroy(e);
+    for (hipStream_t s : {ctx->stream, P.up, P.down}) if (s) (void)hipStreamDestroy(s);
+    delete ctx;                    // the buffers release their memory
 }
 
 void relmc_solver_opts_default(relmc_solver_opts* o)
@@ -375,7 +346,7 @@ int32_t relmc_case_load(relmc_ctx* ctx, const relmc_case_desc* d)
     if (nb < 1 || ng < 0 || nl < 0 || nd < 0 || d->ref_bus < 0 || d->ref_bus >= nb || !(d->base_mva > 0))
         return fail(ctx, RELMC_ERR_INVALID, "relmc_case_load: inconsistent sizes");
     ctx->has_case = false;
-    db_free(ctx);                  // the state database belongs to the case it was filled for
+    ctx->db = {};                  // the state database belongs to the case it was filled for
     {   // the description is kept: the second elimination order (retry of non-converged units) is built from it when first needed
         auto& cc = ctx->case_copy;
         const int ninj = ng + nd, ncomp = ng + nl;
@@ -388,7 +359,7 @@ int32_t relmc_case_load(relmc_ctx* ctx, const relmc_case_desc* d)
         cc.d.br_from = cc.br_from.data(); cc.d.br_to = cc.br_to.data(); cc.d.br_b = cc.br_b.data(); cc.d.br_rate = cc.br_rate.data();
         cc.d.unavail = cc.unavail.data(); cc.d.always_up = cc.always_up.data();
         cc.valid = true;
-        retry_free(ctx);           // the scratch rows of the re-evaluation are sized for the case that was loaded (its bus count)
+        ctx->retry = {};           // the scratch rows of the re-evaluation are sized for the case that was loaded (its bus count)
         ctx->alt_state[0] = ctx->alt_state[1] = 0; ctx->retry_units = 0; ctx->retry_converged = 0; ctx->retry_overflow = 0;
         ctx->retry_dense_units = 0; ctx->retry_dense_converged = 0;
     }
@@ -442,9 +413,9 @@ int32_t relmc_mc_sampling_dev(relmc_ctx* ctx, uint64_t seed, uint64_t first_inde
     int64_t blocks = (total + 255) / 256;
     if (blocks > (int64_t)ctx->num_cu * 16) blocks = (int64_t)ctx->num_cu * 16;
     if (ctx->tile == 0)
-        hipLaunchKernelGGL(relmc_sampling_kernel<Tile24>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, reinterpret_cast<const DevCaseT<Tile24>*>(ctx->dcase), seed, first_index, n, eqstatus_dev);
+        hipLaunchKernelGGL(relmc_sampling_kernel<Tile24>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, reinterpret_cast<const DevCaseT<Tile24>*>(ctx->dcase.get()), seed, first_index, n, eqstatus_dev);
     else
-        hipLaunchKernelGGL(relmc_sampling_kernel<Tile96>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, reinterpret_cast<const DevCaseT<Tile96>*>(ctx->dcase), seed, first_index, n, eqstatus_dev);
+        hipLaunchKernelGGL(relmc_sampling_kernel<Tile96>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, reinterpret_cast<const DevCaseT<Tile96>*>(ctx->dcase.get()), seed, first_index, n, eqstatus_dev);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RELMC_OK;
@@ -457,13 +428,12 @@ int32_t relmc_mc_sampling(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, i
     if (n < 0 || (n > 0 && !eqstatus_host)) return fail(ctx, RELMC_ERR_INVALID, "relmc_mc_sampling: bad arguments");
     if (n == 0) return RELMC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint8_t* dbuf = nullptr;
+    DevBuf<uint8_t> dbuf;
     const size_t bytes = (size_t)n * ctx->ncomp;
-    HIP_TRY(ctx, hipMalloc(&dbuf, bytes));
-    int rc = relmc_mc_sampling_dev(ctx, seed, first_index, n, dbuf);
-    if (rc == RELMC_OK && hipMemcpy(eqstatus_host, dbuf, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    HIP_TRY(ctx, dbuf.grow(bytes));
+    int rc = relmc_mc_sampling_dev(ctx, seed, first_index, n, dbuf.get());
+    if (rc == RELMC_OK && hipMemcpy(eqstatus_host, dbuf.get(), bytes, hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(ctx, RELMC_ERR_HIP, "relmc_mc_sampling: device-to-host copy failed");
-    (void)hipFree(dbuf);
     return rc;
 }
 
@@ -515,14 +485,13 @@ int32_t relmc_dpp_probe(relmc_ctx* ctx, const double* in_host, double* out_host)
 {
     if (!ctx || !in_host || !out_host) return RELMC_ERR_INVALID;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    double* din = nullptr; double* dout = nullptr;
-    HIP_TRY(ctx, hipMalloc(&din, sizeof(double) * 64));
-    HIP_TRY(ctx, hipMalloc(&dout, sizeof(double) * 512));
-    HIP_TRY(ctx, hipMemcpy(din, in_host, sizeof(double) * 64, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(relmc_dpp_probe_kernel, dim3(1), dim3(64), 0, ctx->stream, din, dout);
+    DevBuf<double> din, dout;
+    HIP_TRY(ctx, din.grow(64));
+    HIP_TRY(ctx, dout.grow(512));
+    HIP_TRY(ctx, hipMemcpy(din.get(), in_host, sizeof(double) * 64, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(relmc_dpp_probe_kernel, dim3(1), dim3(64), 0, ctx->stream, din.get(), dout.get());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(out_host, dout, sizeof(double) * 512, hipMemcpyDeviceToHost));
-    (void)hipFree(din); (void)hipFree(dout);
+    HIP_TRY(ctx, hipMemcpy(out_host, dout.get(), sizeof(double) * 512, hipMemcpyDeviceToHost));
     return RELMC_OK;
 }
 }  // extern "C"

@@ -32,13 +32,57 @@ struct relmc_switches {
     bool db_no_probe = false;        // state database: every batch through the dedupe, no per-sample probe
 };
 
+namespace relmc_host {
+// Owner of n elements of T in device memory (hipMalloc) or pinned host memory (hipHostMalloc); move-only, released by the destructor.
+// grow(n) discards: a buffer smaller than n is released and n elements are allocated, contents not kept; on failure it is left empty.
+// The release is a plain hipFree / hipHostFree, which waits for the device: a buffer may be dropped while a queued kernel still reads it.
+template <class T, bool Pinned = false>
+class Buffer {
+public:
+    Buffer() = default;
+    Buffer(Buffer&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+    Buffer& operator=(Buffer&& o) noexcept
+    {
+        if (this != &o) { reset(); p_ = o.p_; n_ = o.n_; o.p_ = nullptr; o.n_ = 0; }
+        return *this;
+    }
+    ~Buffer() { reset(); }
+    T* get() const { return p_; }
+    size_t size() const { return n_; }
+    void reset()
+    {
+        if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr; n_ = 0;
+    }
+    hipError_t grow(size_t n)
+    {
+        if (n <= n_) return hipSuccess;
+        reset();
+        void* p = nullptr;
+        const hipError_t e = Pinned ? hipHostMalloc(&p, sizeof(T) * n, hipHostMallocDefault) : hipMalloc(&p, sizeof(T) * n);
+        if (e == hipSuccess) { p_ = static_cast<T*>(p); n_ = n; }
+        return e;
+    }
+private:
+    T* p_ = nullptr;
+    size_t n_ = 0;
+};
+template <class T> using DevBuf = Buffer<T, false>;
+template <class T> using PinBuf = Buffer<T, true>;
+}  // namespace relmc_host
+
 struct relmc_ctx {
+    template <class T> using DevBuf = relmc_host::DevBuf<T>;
+    template <class T> using PinBuf = relmc_host::PinBuf<T>;
+    static constexpr size_t kCaseBytes = sizeof(relmc::DevCaseT<relmc::Tile96>) > sizeof(relmc::DevCaseT<relmc::Tile24>) ? sizeof(relmc::DevCaseT<relmc::Tile96>)
+                                                                                                                      : sizeof(relmc::DevCaseT<relmc::Tile24>);
     int device = -1;
     relmc_switches sw;
     // relmc_seq_years' device buffers, kept between calls (six hipMalloc / hipFree pairs per call were 1 ms of a 17 ms step): grow-only
-    uint32_t* sq_dm = nullptr; size_t sq_dm_words = 0;
-    uint16_t* sq_hours = nullptr; double* sq_curt = nullptr; size_t sq_nh = 0;
-    uint32_t* sq_counts = nullptr; uint32_t* sq_off = nullptr; double* sq_year = nullptr; int sq_years = 0;
+    struct SeqStep {
+        DevBuf<uint32_t> dm, counts, off;    // counts: [0, n) listed hours per year, [n, 2 n) contingency hours per year (pre-screen)
+        DevBuf<uint16_t> hours; DevBuf<double> curt, year;
+    } sq;
     std::vector<int32_t> order_hint;     // relmc_case_order_hint: primary elimination order of the next relmc_case_load (external bus numbers), empty = the rule
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -46,28 +90,32 @@ struct relmc_ctx {
     int tile = 0;                        // 0: Tile24 (16-lane rows), 1: Tile96 (one scenario per wavefront)
     relmc::DevCaseT<relmc::Tile24> hcase24;
     relmc::DevCaseT<relmc::Tile96> hcase96;
-    void* dcase = nullptr;               // device image of the active tile's case
+    DevBuf<uint8_t> dcase;               // device image of the active tile's case (kCaseBytes)
     int nb = 0, ng = 0, nl = 0, ncomp = 0;
-    void* dpartial = nullptr;
-    size_t partial_bytes = 0;
-    relmc::DevAcc* dacc = nullptr;
-    struct HostStage { relmc_acc acc; uint32_t fail_cnt, pad; }* hstage = nullptr;      // pinned: accumulators + listed-unit count of a fused launch come back in one synchronisation
+    DevBuf<uint8_t> dpartial;
+    DevBuf<relmc::DevAcc> dacc;
+    struct HostStage { relmc_acc acc; uint32_t fail_cnt, pad; };
+    PinBuf<HostStage> hstage;            // accumulators + listed-unit count of a fused launch come back in one synchronisation
     int num_cu = 0;
     int blocks_per_cu = 0;
     uint32_t scen_doubles = 0, lds_bytes = 0, stash_off = 0;
-    unsigned long long* dtiming = nullptr; int timing_waves = 0;
-    double* dhist = nullptr; double* hhist = nullptr /* pinned */; int64_t hist_cap = 0;   // per-sample dns of one launch (checkpoint histories of small batches, relmc_nsq_run)
-    // distinct-state path: device buffers sized for memo_cap samples
-    int64_t memo_cap = 0; size_t memo_tmp_bytes = 0;
-    uint32_t *mk = nullptr, *mperm0 = nullptr, *mperm1 = nullptr, *mhead = nullptr, *muid = nullptr, *mstart = nullptr, *mnu = nullptr;
-    unsigned long long *mch0 = nullptr, *mch1 = nullptr; void* mtmp = nullptr;
-    uint32_t *mmiss = nullptr, *mk2 = nullptr;   // probe-first database path: miss list (sample indices) and the masks of the misses
+    DevBuf<unsigned long long> dtiming; int timing_waves = 0;
+    struct History { DevBuf<double> d; PinBuf<double> h; } hist;      // per-sample dns of one launch (checkpoint histories of small batches, relmc_nsq_run)
+    // distinct-state path: device buffers sized for the samples of a dedupe
+    struct Memo {
+        DevBuf<uint32_t> k, perm0, perm1, head, uid, start, nu;
+        DevBuf<unsigned long long> ch0, ch1; DevBuf<uint8_t> tmp;
+        DevBuf<uint32_t> miss, k2;           // probe-first database path: miss list (sample indices) and the masks of the misses
+    } memo;
     // persistent state database (nsqMain.m:91-99): rows in HBM, open-addressing table of row ids
-    int64_t db_cap = 0, db_n = 0, db_samples = 0; uint64_t db_tcap = 0;
-    uint32_t* db_keys = nullptr; unsigned long long* db_count = nullptr; double* db_dns = nullptr; int32_t* db_meta = nullptr;
-    double* db_nodal = nullptr; uint32_t* db_table = nullptr; relmc::DevAcc* db_partial = nullptr; int db_partial_cap = 0;
-    bool db_has_opts = false; relmc_solver_opts db_opts;
-    bool db_invalid = false;                 // an entry point failed between the count bumps of a batch and its bookkeeping: relmc_db_reset / relmc_case_load only
+    struct Database {
+        int64_t cap = 0, n = 0, samples = 0;     // cap: rows the five row arrays hold (the table has at least twice as many slots)
+        DevBuf<uint32_t> keys; DevBuf<unsigned long long> count; DevBuf<double> dns; DevBuf<int32_t> meta; DevBuf<double> nodal; DevBuf<uint32_t> table;
+        DevBuf<relmc::DevAcc> partial;
+        DevBuf<unsigned long long> snap;         // row counts before a stretch of small batches (relmc_nsq_run)
+        bool has_opts = false; relmc_solver_opts opts = {};
+        bool invalid = false;                    // an entry point failed between the count bumps of a batch and its bookkeeping: relmc_db_reset / relmc_case_load only
+    } db;
     // retry of the units the primary elimination order does not converge on: a second device image of the case built with
     // another static order (lazily, from a copy of the description), the kernel's list of such units, scratch rows for their re-evaluation
     struct CaseCopy {
@@ -76,28 +124,28 @@ struct relmc_ctx {
     } case_copy;
     static constexpr int kAlt = 2;           // further static orders: [0] the primary rule with the ties broken the other way, [1] fill first
     int alt_state[kAlt] = {0, 0};            // 0 not built yet, 1 ready, -1 unavailable (that order does not fit the tile)
-    void* dcase_alt[kAlt] = {nullptr, nullptr}; uint32_t alt_scen_doubles[kAlt] = {0, 0}, alt_lds_bytes[kAlt] = {0, 0}, alt_stash_off[kAlt] = {0, 0};
-    relmc::FailRec* dfail = nullptr; uint32_t* dfail_count = nullptr; bool fail_dirty = false;
-    uint32_t fail_cap = 0;                   // entries of dfail (grows with the size of the call, fail_arm)
-    double* ddense = nullptr; size_t dense_bytes = 0;      // global scratch of the dense pivoted last resort (MODE 6)
+    DevBuf<uint8_t> dcase_alt[kAlt]; uint32_t alt_scen_doubles[kAlt] = {0, 0}, alt_lds_bytes[kAlt] = {0, 0}, alt_stash_off[kAlt] = {0, 0};
+    struct Retry {
+        DevBuf<relmc::FailRec> fail; DevBuf<uint32_t> fail_count; bool fail_dirty = false;   // the kernel's list (grows with the size of the call, fail_arm)
+        DevBuf<double> dense;                // global scratch of the dense pivoted last resort (MODE 6)
+        // scratch rows of the re-evaluation: twice `rows` listed units (the third order's compact rows start at `rows`)
+        DevBuf<uint32_t> keys; DevBuf<double> dns; DevBuf<int32_t> meta; DevBuf<double> nodal, scale; int64_t rows = 0;
+    } retry;
     int64_t retry_dense_units = 0, retry_dense_converged = 0;    // units that went to it since the case was loaded
     int64_t retry_overflow = 0;              // units that did not fit the list and kept their first-attempt results (relmc_retry_overflow)
     std::vector<double> hlf;                 // host copy of the hourly load factors (load scale of a re-evaluated hour)
-    // scratch rows of the re-evaluation, sized for rcap listed units of a case with rnb buses (twice: the third order's compact rows)
-    uint32_t* rkeys = nullptr; double* rdns = nullptr; int32_t* rmeta = nullptr; double* rnodal = nullptr; double* rscale = nullptr; int64_t rcap = 0; int rnb = 0;
     int64_t retry_units = 0, retry_converged = 0;        // since the case was loaded
     int order_primary = 0; int32_t order_probe[3] = {-1, -1, -1};   // which static order runs first, and the calibration's failure counts (-1 = not probed)
-    unsigned long long* db_snap = nullptr; int64_t db_snap_cap = 0;      // row counts before a stretch of small batches (relmc_nsq_run)
     // host-buffer entry points (relmc_mc_simulation, relmc_seq_mcsimulation): double-buffered chunk pipeline, device buffers
     // and pinned staging kept across calls
     struct HostPipe {
         bool ready = false; int ncomp = 0, nb = 0;
         hipStream_t up = nullptr, down = nullptr;
         hipEvent_t e_up[2] = {nullptr, nullptr}, e_ks[2] = {nullptr, nullptr}, e_ke[2] = {nullptr, nullptr}, e_down[2] = {nullptr, nullptr};
-        uint8_t* d_st[2] = {nullptr, nullptr}; double* d_sc[2] = {nullptr, nullptr}; double* d_dns[2] = {nullptr, nullptr}; double* d_nod[2] = {nullptr, nullptr};
-        int32_t* d_stat[2] = {nullptr, nullptr}; int32_t* d_it[2] = {nullptr, nullptr};
-        uint8_t* h_st[2] = {nullptr, nullptr}; double* h_sc[2] = {nullptr, nullptr}; double* h_dns[2] = {nullptr, nullptr}; double* h_nod[2] = {nullptr, nullptr};
-        int32_t* h_stat[2] = {nullptr, nullptr}; int32_t* h_it[2] = {nullptr, nullptr};
+        struct Bufs {
+            DevBuf<uint8_t> d_st; DevBuf<double> d_sc, d_dns, d_nod; DevBuf<int32_t> d_stat, d_it;
+            PinBuf<uint8_t> h_st; PinBuf<double> h_sc, h_dns, h_nod; PinBuf<int32_t> h_stat, h_it;
+        } buf[2];
     } pipe;
     // communicator over the ranks of a multi-GPU run (optional; relmc_comm_*): RCCL, or the host's own collective
     void* comm = nullptr; int comm_nranks = 0, comm_rank = -1;
@@ -106,20 +154,19 @@ struct relmc_ctx {
     int64_t comm_calls = 0; double comm_seconds = 0.0;                                     // all-reduces of relmc_acc through this context, wall time in them
     double comm_timeout_s = 120.0;                                                         // wall-clock guard of communicator init and of every collective
     void* watchdog = nullptr;                                                              // the guard's thread (relmc_comm.hip), started at the first guarded call
-    double* dgather = nullptr; size_t gather_doubles = 0;                                  // device staging of comm_allreduce_f64 (RCCL)
+    DevBuf<double> dgather;                                                                // device staging of comm_allreduce_f64 (RCCL)
     // sequential track
-    bool has_seq = false; relmc::SeqCase hseq; relmc::SeqCase* dseq = nullptr; double* dlf = nullptr;
-    // HL1 copper-sheet model
-    bool has_hl1 = false; relmc::Hl1Case* dhl1 = nullptr; double* dsorted = nullptr; double* dsuffix = nullptr; int hl1_hours = 0;
-    double* h1_lole = nullptr; double* h1_eue = nullptr; int64_t h1_cap = 0; double* h1_part = nullptr; int64_t h1_part_cap = 0;   // relmc_hl1_nsq's device buffers, grow-only
+    bool has_seq = false; relmc::SeqCase hseq; DevBuf<relmc::SeqCase> dseq; DevBuf<double> dlf;
+    // HL1 copper-sheet model; lole / eue / part: relmc_hl1_nsq's device buffers, grow-only
+    bool has_hl1 = false; int hl1_hours = 0;
+    struct Hl1 { DevBuf<relmc::Hl1Case> dcase; DevBuf<double> sorted, suffix, lole, eue, part; } hl1;
     // zero-curtailment pre-screen (relmc_screen.hip): certificate tables of the case (device pointers inside tab), grow-only work buffers of a pre-pass
     struct Screen {
         relmc::ScreenTab tab = {};
-        void* dtab = nullptr;
-        uint32_t* keys = nullptr; uint8_t* flags = nullptr; uint32_t* idx = nullptr; uint32_t* dcount = nullptr; void* tmp = nullptr;
-        size_t tmp_bytes = 0; int64_t cap = 0;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        DevBuf<uint8_t> dtab;
+        DevBuf<uint32_t> keys; DevBuf<uint8_t> flags; DevBuf<uint32_t> idx, dcount; DevBuf<uint8_t> tmp;
     } screen;
+    hipEvent_t screen_ev0 = nullptr, screen_ev1 = nullptr;      // timing of the pre-pass
     double last_kernel_ms = 0.0;
     long conflict_before = 0, conflict_after = 0;   // modelled extra LDS cycles per Newton step before / after the placement search
     long alt_conflict_before[kAlt] = {0, 0}, alt_conflict_after[kAlt] = {0, 0};      // the same of the further orders' images
@@ -183,34 +230,26 @@ using ScaleFn = std::function<double(unsigned long long)>;          // unit -> l
 // known_count (optional): the number of listed units if the caller has already copied it back with its results
 int fail_retry(relmc_ctx* ctx, const relmc_solver_opts& o, double fail_threshold, const ScaleFn* scale, RetryOut& out, double* ms, const uint32_t* known_count = nullptr);
 void acc_add_unit(relmc_acc* acc, const FailRec& rec, double dns, int32_t meta, const double* nodal, int nb, int ncomp, double fail_threshold);
-void retry_free(relmc_ctx* ctx);
 
 // ---- relmc_simulate.hip -------------------------------------------------------------------------------------------------------
-void pipe_free(relmc_ctx* ctx);
 int pipe_run(relmc_ctx* ctx, const uint8_t* states, const double* load_scale, int64_t n, const relmc_solver_opts& o, double fail_threshold,
              double* dns, double* nodal, int32_t* status, int32_t* iters);
 int nsq_accumulate_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t n, const relmc_solver_opts* opts, relmc_acc* acc_out, double* dns_dev);
 
 // ---- relmc_database.hip -------------------------------------------------------------------------------------------------------
-void db_free(relmc_ctx* ctx);
-void memo_free(relmc_ctx* ctx);
 int db_accumulate(relmc_ctx* ctx, relmc_acc* acc_out);
-int db_rewind(relmc_ctx* ctx, int64_t rows0, int64_t samples0);      // back to the first rows0 rows with the counts saved in ctx->db_snap
-int db_snapshot(relmc_ctx* ctx);                                    // saves the counts of the present rows into ctx->db_snap
+int db_rewind(relmc_ctx* ctx, int64_t rows0, int64_t samples0);      // back to the first rows0 rows with the counts saved in ctx->db.snap
+int db_snapshot(relmc_ctx* ctx);                                    // saves the counts of the present rows into ctx->db.snap
 int db_sample_dns(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t m, double* dns_dev);   // dns of every sample of a range from its row
 
 // ---- relmc_comm.hip -----------------------------------------------------------------------------------------------------------
-void comm_free(relmc_ctx* ctx);
+void comm_free(relmc_ctx* ctx);                   // stops the watchdog, destroys the RCCL communicator
 inline int comm_ranks(const relmc_ctx* ctx) { return (ctx->comm || ctx->host_allreduce) ? ctx->comm_nranks : 1; }
 // sum over the ranks of a vector of doubles, in place (the all-gather of the sequential loop: every rank fills its own slots, zeros elsewhere --
 // x + 0 + ... + 0 is exact).  RCCL: one ncclAllReduce; host collective: through the registered relmc_acc all-reduce, 130 doubles per call
 int comm_allreduce_f64(relmc_ctx* ctx, double* buf, int64_t count);
 
-// ---- relmc_seq.hip ------------------------------------------------------------------------------------------------------------
-void seq_free(relmc_ctx* ctx);
-
 // ---- relmc_screen.hip ---------------------------------------------------------------------------------------------------------
-void screen_free(relmc_ctx* ctx);
 int screen_build(relmc_ctx* ctx, const relmc_case_desc* d);          // relmc_case_load: PTDF / LODF tables of the certificate
 // samples [first_index, first_index + m): masks of the uncovered ones in ctx->screen.keys (own position), their ascending positions in ctx->screen.idx
 int screen_prepass_nsq(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t m, uint32_t* n_surv, double* ms);

@@ -40,23 +40,21 @@ int32_t relmc_debug_mc_simulation_dense(relmc_ctx* ctx, const uint8_t* states_ho
     const int ow = mask_words(ctx), ncomp = ctx->ncomp, nb = ctx->nb;
     std::vector<uint32_t> keys((size_t)n * ow, 0u);
     for (int64_t r = 0; r < n; ++r) for (int k = 0; k < ncomp; ++k) if (states_host[(size_t)r * ncomp + k]) keys[(size_t)r * ow + (k >> 5)] |= 1u << (k & 31);
-    uint32_t* dk = nullptr; double* dd = nullptr; int32_t* dm = nullptr; double* dn = nullptr;
-    auto cleanup = [&]() { (void)hipFree(dk); (void)hipFree(dd); (void)hipFree(dm); (void)hipFree(dn); };
-    if (hipMalloc(&dk, sizeof(uint32_t) * keys.size()) != hipSuccess || hipMalloc(&dd, sizeof(double) * (size_t)n) != hipSuccess ||
-        hipMalloc(&dm, sizeof(int32_t) * (size_t)n) != hipSuccess || hipMalloc(&dn, sizeof(double) * (size_t)n * nb) != hipSuccess) { cleanup(); return fail(ctx, RELMC_ERR_HIP, "dense simulation: device allocation failed"); }
+    DevBuf<uint32_t> dk; DevBuf<double> dd, dn; DevBuf<int32_t> dm;
+    if (dk.grow(keys.size()) != hipSuccess || dd.grow((size_t)n) != hipSuccess || dm.grow((size_t)n) != hipSuccess || dn.grow((size_t)n * nb) != hipSuccess)
+        return fail(ctx, RELMC_ERR_HIP, "dense simulation: device allocation failed");
     int rc = RELMC_OK;
-    if (hipMemcpy(dk, keys.data(), sizeof(uint32_t) * keys.size(), hipMemcpyHostToDevice) != hipSuccess) rc = fail(ctx, RELMC_ERR_HIP, "dense simulation: H2D failed");
+    if (hipMemcpy(dk.get(), keys.data(), sizeof(uint32_t) * keys.size(), hipMemcpyHostToDevice) != hipSuccess) rc = fail(ctx, RELMC_ERR_HIP, "dense simulation: H2D failed");
     EvalArgs a = make_args(o);
-    a.n = n; a.memo_keys = dk; a.db_first = 0; a.dns = dd; a.status = dm; a.nodal = dn;
+    a.n = n; a.memo_keys = dk.get(); a.db_first = 0; a.dns = dd.get(); a.status = dm.get(); a.nodal = dn.get();
     int rows = 0;
     if (rc == RELMC_OK) rc = launch_eval(ctx, 6, a, &rows);
     if (rc == RELMC_OK) rc = finish_timing(ctx);
     std::vector<int32_t> meta((size_t)n);
-    if (rc == RELMC_OK && (hipMemcpy(dns_host, dd, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
-                           hipMemcpy(meta.data(), dm, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
-                           (nodal_host && hipMemcpy(nodal_host, dn, sizeof(double) * (size_t)n * nb, hipMemcpyDeviceToHost) != hipSuccess)))
+    if (rc == RELMC_OK && (hipMemcpy(dns_host, dd.get(), sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+                           hipMemcpy(meta.data(), dm.get(), sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+                           (nodal_host && hipMemcpy(nodal_host, dn.get(), sizeof(double) * (size_t)n * nb, hipMemcpyDeviceToHost) != hipSuccess)))
         rc = fail(ctx, RELMC_ERR_HIP, "dense simulation: D2H failed");
-    cleanup();
     if (rc) return rc;
     for (int64_t r = 0; r < n; ++r) { if (status_host) status_host[r] = meta[(size_t)r] & 3; if (iters_host) iters_host[r] = (int32_t)((uint32_t)meta[(size_t)r] >> 8); }
     return RELMC_OK;
@@ -67,9 +65,9 @@ int32_t relmc_debug_phase_cycles(relmc_ctx* ctx, unsigned long long* out8)
 {
     if (!ctx || !out8) return RELMC_ERR_INVALID;
     for (int k = 0; k < 8; ++k) out8[k] = 0;
-    if (!ctx->dtiming || ctx->timing_waves <= 0) return RELMC_OK;
+    if (!ctx->dtiming.get() || ctx->timing_waves <= 0) return RELMC_OK;
     std::vector<unsigned long long> h((size_t)ctx->timing_waves * 8);
-    HIP_TRY(ctx, hipMemcpy(h.data(), ctx->dtiming, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(h.data(), ctx->dtiming.get(), h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (int w = 0; w < ctx->timing_waves; ++w) for (int k = 0; k < 8; ++k) out8[k] += h[(size_t)w * 8 + k];
     return RELMC_OK;
 }
@@ -80,8 +78,8 @@ int32_t relmc_debug_trace(relmc_ctx* ctx, double* out, int32_t n_doubles)
 {
     if (!ctx || !out || n_doubles < 0) return RELMC_ERR_INVALID;
     for (int k = 0; k < n_doubles; ++k) out[k] = 0.0;
-    if (!ctx->dtiming || n_doubles > 8 * 65536) return RELMC_OK;
-    HIP_TRY(ctx, hipMemcpy(out, ctx->dtiming, sizeof(double) * n_doubles, hipMemcpyDeviceToHost));
+    if (!ctx->dtiming.get() || n_doubles > 8 * 65536) return RELMC_OK;
+    HIP_TRY(ctx, hipMemcpy(out, ctx->dtiming.get(), sizeof(double) * n_doubles, hipMemcpyDeviceToHost));
     return RELMC_OK;
 }
 

@@ -8,15 +8,6 @@
 
 namespace relmc_host {
 
-void retry_free(relmc_ctx* ctx)
-{
-    for (void* p : {(void*)ctx->rkeys, (void*)ctx->rdns, (void*)ctx->rmeta, (void*)ctx->rnodal, (void*)ctx->rscale, (void*)ctx->dfail, (void*)ctx->dfail_count,
-                    (void*)ctx->ddense}) if (p) (void)hipFree(p);
-    ctx->rkeys = nullptr; ctx->rdns = nullptr; ctx->rmeta = nullptr; ctx->rnodal = nullptr; ctx->rscale = nullptr; ctx->rcap = 0; ctx->rnb = 0;
-    ctx->dfail = nullptr; ctx->dfail_count = nullptr; ctx->fail_cap = 0; ctx->fail_dirty = false;
-    ctx->ddense = nullptr; ctx->dense_bytes = 0;
-}
-
 // ---- second chance for the units the primary elimination order does not converge on ---------------------------------------------
 // The block elimination runs in an order fixed per case; on a few states (6.7e-7 of the RTS-96 scenarios, 4e-10 on RTS-24) that order
 // meets a stiff line next to a bus with an interior injection and the Newton steps of the last iterations lose their digits (DESIGN.md
@@ -36,19 +27,16 @@ uint32_t fail_cap_for(int64_t call_units)
 }
 int fail_list_ensure(relmc_ctx* ctx, uint32_t cap)
 {
-    if (!ctx->dfail_count) {
-        HIP_TRY(ctx, hipMalloc(&ctx->dfail_count, sizeof(uint32_t)));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dfail_count, 0, sizeof(uint32_t), ctx->stream));
+    auto& R = ctx->retry;
+    if (!R.fail_count.get()) {
+        HIP_TRY(ctx, R.fail_count.grow(1));
+        HIP_TRY(ctx, hipMemsetAsync(R.fail_count.get(), 0, sizeof(uint32_t), ctx->stream));
     }
-    if (cap <= ctx->fail_cap) return RELMC_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->dfail) (void)hipFree(ctx->dfail);
-    ctx->dfail = nullptr; ctx->fail_cap = 0;
-    HIP_TRY(ctx, hipMalloc(&ctx->dfail, sizeof(FailRec) * (size_t)cap));
-    ctx->fail_cap = cap;
+    if (cap <= R.fail.size()) return RELMC_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // the list is dropped below: no launch may still write to it
+    HIP_TRY(ctx, R.fail.grow(cap));
     return RELMC_OK;
 }
-
 
 int alt_ensure(relmc_ctx* ctx, int v)          // v = 0, 1: which further order
 {
@@ -69,16 +57,15 @@ int fail_arm(relmc_ctx* ctx, EvalArgs& a, int64_t unit_base, bool reset, int64_t
     a.fail_list = nullptr; a.fail_count = nullptr; a.fail_cap = 0; a.unit_base = unit_base;
     if (ctx->sw.no_retry) return RELMC_OK;      // diagnosis switch: the first attempt's results as they are
     // (a case whose further static orders do not fit the tile is armed all the same: the dense pivoted level needs no second image)
-    if (reset || !ctx->dfail) {
-        const uint32_t want = fail_cap_for(call_units);
-        const int rc = fail_list_ensure(ctx, want > ctx->fail_cap ? want : ctx->fail_cap);
+    if (reset || !ctx->retry.fail.get()) {
+        const int rc = fail_list_ensure(ctx, fail_cap_for(call_units));
         if (rc) return rc;
     }
     // the count is zero whenever a call has collected its list (fail_retry zeroes it after a non-empty one), so the common case costs no
     // memset launch; only a call that was abandoned between arming and collecting leaves it to be cleared here
-    if (reset && ctx->fail_dirty) { HIP_TRY(ctx, hipMemsetAsync(ctx->dfail_count, 0, sizeof(uint32_t), ctx->stream)); }
-    if (reset) ctx->fail_dirty = true;
-    a.fail_list = ctx->dfail; a.fail_count = ctx->dfail_count; a.fail_cap = ctx->fail_cap;
+    if (reset && ctx->retry.fail_dirty) { HIP_TRY(ctx, hipMemsetAsync(ctx->retry.fail_count.get(), 0, sizeof(uint32_t), ctx->stream)); }
+    if (reset) ctx->retry.fail_dirty = true;
+    a.fail_list = ctx->retry.fail.get(); a.fail_count = ctx->retry.fail_count.get(); a.fail_cap = (uint32_t)ctx->retry.fail.size();
     return RELMC_OK;
 }
 
@@ -86,8 +73,8 @@ int fail_arm(relmc_ctx* ctx, EvalArgs& a, int64_t unit_base, bool reset, int64_t
 int fail_listed(relmc_ctx* ctx, uint32_t* cnt)
 {
     *cnt = 0;
-    if (!ctx->dfail_count) return RELMC_OK;
-    HIP_TRY(ctx, hipMemcpy(cnt, ctx->dfail_count, sizeof(*cnt), hipMemcpyDeviceToHost));
+    if (!ctx->retry.fail_count.get()) return RELMC_OK;
+    HIP_TRY(ctx, hipMemcpy(cnt, ctx->retry.fail_count.get(), sizeof(*cnt), hipMemcpyDeviceToHost));
     return RELMC_OK;
 }
 
@@ -98,40 +85,39 @@ int fail_retry(relmc_ctx* ctx, const relmc_solver_opts& o, double fail_threshold
     const bool have_scale = scale_fn != nullptr;
     auto scale = [&](unsigned long long u) { return (*scale_fn)(u); };
     out.rec.clear();
-    if (!ctx->dfail_count) return RELMC_OK;
+    if (!ctx->retry.fail_count.get()) return RELMC_OK;
     uint32_t cnt = 0;
     if (known_count) cnt = *known_count;            // the caller read the count with its results (one synchronisation)
-    else HIP_TRY(ctx, hipMemcpy(&cnt, ctx->dfail_count, sizeof(cnt), hipMemcpyDeviceToHost));
-    ctx->fail_dirty = false;
+    else HIP_TRY(ctx, hipMemcpy(&cnt, ctx->retry.fail_count.get(), sizeof(cnt), hipMemcpyDeviceToHost));
+    ctx->retry.fail_dirty = false;
     if (cnt == 0) return RELMC_OK;
-    HIP_TRY(ctx, hipMemset(ctx->dfail_count, 0, sizeof(uint32_t)));
-    if (cnt > ctx->fail_cap) {                               // the units beyond the list were accumulated by the kernel as they were
-        ctx->retry_overflow += (int64_t)(cnt - ctx->fail_cap);
-        cnt = ctx->fail_cap;
+    HIP_TRY(ctx, hipMemset(ctx->retry.fail_count.get(), 0, sizeof(uint32_t)));
+    const uint32_t cap = (uint32_t)ctx->retry.fail.size();
+    if (cnt > cap) {                                         // the units beyond the list were accumulated by the kernel as they were
+        ctx->retry_overflow += (int64_t)(cnt - cap);
+        cnt = cap;
     }
     out.rec.resize(cnt);
-    HIP_TRY(ctx, hipMemcpy(out.rec.data(), ctx->dfail, sizeof(FailRec) * cnt, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out.rec.data(), ctx->retry.fail.get(), sizeof(FailRec) * cnt, hipMemcpyDeviceToHost));
     std::sort(out.rec.begin(), out.rec.end(), [](const FailRec& x, const FailRec& y) { return x.unit < y.unit; });
     const int ow = ctx->tile == 0 ? Tile24::OW : Tile96::OW;
     const size_t nb = (size_t)ctx->nb;
-    if ((int64_t)cnt > ctx->rcap || ctx->nb > ctx->rnb) {    // scratch rows of the re-evaluation, sized by what was listed (twice: the third order's compact rows)
-        for (void* p : {(void*)ctx->rkeys, (void*)ctx->rdns, (void*)ctx->rmeta, (void*)ctx->rnodal, (void*)ctx->rscale}) if (p) (void)hipFree(p);
-        ctx->rkeys = nullptr; ctx->rdns = nullptr; ctx->rmeta = nullptr; ctx->rnodal = nullptr; ctx->rscale = nullptr; ctx->rcap = 0; ctx->rnb = 0;
-        size_t rc2 = kFailCapMin; while (rc2 < cnt) rc2 *= 2;
-        HIP_TRY(ctx, hipMalloc(&ctx->rkeys, sizeof(uint32_t) * rc2 * 2 * 8));
-        HIP_TRY(ctx, hipMalloc(&ctx->rdns, sizeof(double) * rc2 * 2));
-        HIP_TRY(ctx, hipMalloc(&ctx->rmeta, sizeof(int32_t) * rc2 * 2));
-        HIP_TRY(ctx, hipMalloc(&ctx->rnodal, sizeof(double) * rc2 * 2 * nb));
-        HIP_TRY(ctx, hipMalloc(&ctx->rscale, sizeof(double) * rc2 * 2));
-        ctx->rcap = (int64_t)rc2; ctx->rnb = ctx->nb;
-    }
+    auto& R = ctx->retry;
+    // scratch rows of the re-evaluation, sized by what was listed (twice: the third order's compact rows); the bus count is the case's (reset by relmc_case_load)
+    if ((int64_t)cnt > R.rows) { R.rows = kFailCapMin; while (R.rows < (int64_t)cnt) R.rows *= 2; }
+    const size_t rc2 = (size_t)R.rows;
+    HIP_TRY(ctx, R.keys.grow(rc2 * 2 * 8));
+    HIP_TRY(ctx, R.dns.grow(rc2 * 2));
+    HIP_TRY(ctx, R.meta.grow(rc2 * 2));
+    HIP_TRY(ctx, R.nodal.grow(rc2 * 2 * nb));
+    HIP_TRY(ctx, R.scale.grow(rc2 * 2));
     std::vector<uint32_t> keys((size_t)cnt * ow);
     for (uint32_t r = 0; r < cnt; ++r) for (int q = 0; q < ow; ++q) keys[(size_t)r * ow + q] = out.rec[r].mask[q];
-    HIP_TRY(ctx, hipMemcpy(ctx->rkeys, keys.data(), sizeof(uint32_t) * keys.size(), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->retry.keys.get(), keys.data(), sizeof(uint32_t) * keys.size(), hipMemcpyHostToDevice));
     if (have_scale) {
         std::vector<double> sc(cnt);
         for (uint32_t r = 0; r < cnt; ++r) sc[r] = scale(out.rec[r].unit);
-        HIP_TRY(ctx, hipMemcpy(ctx->rscale, sc.data(), sizeof(double) * cnt, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(ctx->retry.scale.get(), sc.data(), sizeof(double) * cnt, hipMemcpyHostToDevice));
     }
     out.dns.resize(cnt); out.meta.resize(cnt); out.nodal.resize((size_t)cnt * nb);
     // first the whole list under the second order, then whatever is still non-converged under the third (the sets of states the three
@@ -146,10 +132,10 @@ int fail_retry(relmc_ctx* ctx, const relmc_solver_opts& o, double fail_threshold
         if (level > 0 && !have) continue;
         EvalArgs a = make_args(o);
         a.fail_threshold = fail_threshold;
-        a.load_scale = have_scale ? ctx->rscale : nullptr;
+        a.load_scale = have_scale ? ctx->retry.scale.get() : nullptr;
         int rows = 0, rc;
         if (level == 0 || (dense && dense_first)) {
-            a.n = (int64_t)cnt; a.memo_keys = ctx->rkeys; a.db_first = 0; a.dns = ctx->rdns; a.status = ctx->rmeta; a.nodal = ctx->rnodal;
+            a.n = (int64_t)cnt; a.memo_keys = ctx->retry.keys.get(); a.db_first = 0; a.dns = ctx->retry.dns.get(); a.status = ctx->retry.meta.get(); a.nodal = ctx->retry.nodal.get();
             rc = dense ? launch_eval(ctx, 6, a, &rows) : launch_eval(ctx, 4, a, &rows, nullptr, nullptr, have ? 1 : 0);
             if (rc) return rc;
             if (dense) ctx->retry_dense_units += cnt;
@@ -158,7 +144,7 @@ int fail_retry(relmc_ctx* ctx, const relmc_solver_opts& o, double fail_threshold
             if (rc) return rc;
             if (ms) *ms += ctx->last_kernel_ms;
             ctx->last_kernel_ms = before;
-            HIP_TRY(ctx, hipMemcpy(out.meta.data(), ctx->rmeta, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(out.meta.data(), ctx->retry.meta.get(), sizeof(int32_t) * cnt, hipMemcpyDeviceToHost));
             if (dense) for (uint32_t r = 0; r < cnt; ++r) if ((out.meta[r] & 3) == 0 || (out.meta[r] & 3) == 3) ctx->retry_dense_converged += 1;
         } else {
             // what the second order left non-converged, compacted behind the list's rows and evaluated under the third order in ONE launch
@@ -167,13 +153,13 @@ int fail_retry(relmc_ctx* ctx, const relmc_solver_opts& o, double fail_threshold
             for (uint32_t r = 0; r < cnt; ++r) if ((out.meta[r] & 3) == 1 || (out.meta[r] & 3) == 2) idx.push_back(r);
             if (idx.empty()) break;
             if (dense) ctx->retry_dense_units += (int64_t)idx.size();
-            const size_t m = idx.size(), base = (size_t)ctx->rcap;
+            const size_t m = idx.size(), base = (size_t)ctx->retry.rows;
             std::vector<uint32_t> k2(m * ow); std::vector<double> s2(m);
             for (size_t q = 0; q < m; ++q) { for (int w = 0; w < ow; ++w) k2[q * ow + w] = out.rec[idx[q]].mask[w]; if (have_scale) s2[q] = scale(out.rec[idx[q]].unit); }
-            HIP_TRY(ctx, hipMemcpy(ctx->rkeys + base * ow, k2.data(), sizeof(uint32_t) * k2.size(), hipMemcpyHostToDevice));
-            if (have_scale) HIP_TRY(ctx, hipMemcpy(ctx->rscale + base, s2.data(), sizeof(double) * m, hipMemcpyHostToDevice));
-            a.n = (int64_t)m; a.memo_keys = ctx->rkeys; a.db_first = (int64_t)base; a.dns = ctx->rdns; a.status = ctx->rmeta; a.nodal = ctx->rnodal;
-            a.load_scale = have_scale ? ctx->rscale + base : nullptr;
+            HIP_TRY(ctx, hipMemcpy(ctx->retry.keys.get() + base * ow, k2.data(), sizeof(uint32_t) * k2.size(), hipMemcpyHostToDevice));
+            if (have_scale) HIP_TRY(ctx, hipMemcpy(ctx->retry.scale.get() + base, s2.data(), sizeof(double) * m, hipMemcpyHostToDevice));
+            a.n = (int64_t)m; a.memo_keys = ctx->retry.keys.get(); a.db_first = (int64_t)base; a.dns = ctx->retry.dns.get(); a.status = ctx->retry.meta.get(); a.nodal = ctx->retry.nodal.get();
+            a.load_scale = have_scale ? ctx->retry.scale.get() + base : nullptr;
             rc = dense ? launch_eval(ctx, 6, a, &rows) : launch_eval(ctx, 4, a, &rows, nullptr, nullptr, level + 1);
             if (rc) return rc;
             const double before = ctx->last_kernel_ms;
@@ -182,23 +168,23 @@ int fail_retry(relmc_ctx* ctx, const relmc_solver_opts& o, double fail_threshold
             if (ms) *ms += ctx->last_kernel_ms;
             ctx->last_kernel_ms = before;
             for (size_t q = 0; q < m; ++q) {
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->rdns + idx[q], ctx->rdns + base + q, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->rmeta + idx[q], ctx->rmeta + base + q, sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->rnodal + (size_t)idx[q] * nb, ctx->rnodal + (base + q) * nb, sizeof(double) * nb, hipMemcpyDeviceToDevice, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->retry.dns.get() + idx[q], ctx->retry.dns.get() + base + q, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->retry.meta.get() + idx[q], ctx->retry.meta.get() + base + q, sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->retry.nodal.get() + (size_t)idx[q] * nb, ctx->retry.nodal.get() + (base + q) * nb, sizeof(double) * nb, hipMemcpyDeviceToDevice, ctx->stream));
             }
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             if (dense) {
                 std::vector<int32_t> m2(m);
-                HIP_TRY(ctx, hipMemcpy(m2.data(), ctx->rmeta + base, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
+                HIP_TRY(ctx, hipMemcpy(m2.data(), ctx->retry.meta.get() + base, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
                 for (size_t q = 0; q < m; ++q) if ((m2[q] & 3) == 0 || (m2[q] & 3) == 3) ctx->retry_dense_converged += 1;
             } else {
-                HIP_TRY(ctx, hipMemcpy(out.meta.data(), ctx->rmeta, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost));      // what is still left, for the next level
+                HIP_TRY(ctx, hipMemcpy(out.meta.data(), ctx->retry.meta.get(), sizeof(int32_t) * cnt, hipMemcpyDeviceToHost));      // what is still left, for the next level
             }
         }
     }
-    HIP_TRY(ctx, hipMemcpy(out.dns.data(), ctx->rdns, sizeof(double) * cnt, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out.meta.data(), ctx->rmeta, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out.nodal.data(), ctx->rnodal, sizeof(double) * cnt * nb, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out.dns.data(), ctx->retry.dns.get(), sizeof(double) * cnt, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out.meta.data(), ctx->retry.meta.get(), sizeof(int32_t) * cnt, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out.nodal.data(), ctx->retry.nodal.get(), sizeof(double) * cnt * nb, hipMemcpyDeviceToHost));
     ctx->retry_units += cnt;
     for (uint32_t r = 0; r < cnt; ++r) if ((out.meta[r] & 3) == 0 || (out.meta[r] & 3) == 3) ctx->retry_converged += 1;
     return RELMC_OK;

@@ -247,15 +247,6 @@ struct ScreenFlagSet { __device__ bool operator()(uint8_t f) const { return f !=
 
 namespace relmc_host {
 
-void screen_free(relmc_ctx* ctx)
-{
-    auto& S = ctx->screen;
-    for (void* p : {(void*)S.dtab, (void*)S.keys, (void*)S.flags, (void*)S.idx, (void*)S.dcount, S.tmp}) if (p) (void)hipFree(p);
-    if (S.ev0) (void)hipEventDestroy(S.ev0);
-    if (S.ev1) (void)hipEventDestroy(S.ev1);
-    S = relmc_ctx::Screen();
-}
-
 namespace {
 // dense inverse of the reduced susceptance matrix by Gauss-Jordan with partial pivoting; false = singular (the base topology is not one island)
 bool invert(std::vector<double>& A, int n)
@@ -346,7 +337,7 @@ bool screen_tables(const relmc_case_desc* d, std::vector<double>& h, std::vector
 // screen = 1 then certifies nothing.
 int screen_build(relmc_ctx* ctx, const relmc_case_desc* d)
 {
-    screen_free(ctx);                                        // the work buffers are sized for the tile of the case that was loaded
+    ctx->screen = {};                                        // the work buffers are sized for the tile of the case that was loaded
     auto& S = ctx->screen;
     const int ng = d->ng, nl = d->nl;
     S.tab.nl = nl; S.tab.ng = ng; S.tab.valid = 0; S.tab.total_load = d->total_load;
@@ -356,10 +347,10 @@ int screen_build(relmc_ctx* ctx, const relmc_case_desc* d)
     const size_t n_d = h.size();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t bytes = n_d * sizeof(double) + (size_t)nl;
-    HIP_TRY(ctx, hipMalloc(&S.dtab, bytes));
-    HIP_TRY(ctx, hipMemcpy(S.dtab, h.data(), n_d * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(reinterpret_cast<unsigned char*>(S.dtab) + n_d * sizeof(double), bridge.data(), (size_t)nl, hipMemcpyHostToDevice));
-    const double* dd = reinterpret_cast<const double*>(S.dtab);
+    HIP_TRY(ctx, S.dtab.grow(bytes));
+    HIP_TRY(ctx, hipMemcpy(S.dtab.get(), h.data(), n_d * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(reinterpret_cast<unsigned char*>(S.dtab.get()) + n_d * sizeof(double), bridge.data(), (size_t)nl, hipMemcpyHostToDevice));
+    const double* dd = reinterpret_cast<const double*>(S.dtab.get());
     S.tab.sum_pmin = sum_pmin; S.tab.sum_rng = sum_rng;
     S.tab.pmin = dd; S.tab.rng = dd + ng; S.tab.f_min = dd + 2 * ng; S.tab.f_rng = S.tab.f_min + nl; S.tab.f_load = S.tab.f_rng + nl; S.tab.lim = S.tab.f_load + nl;
     S.tab.gpair = S.tab.lim + nl; S.tab.hmat = S.tab.gpair + (size_t)2 * nl * ng;
@@ -372,19 +363,17 @@ namespace {
 int screen_buffers(relmc_ctx* ctx, int64_t m)
 {
     auto& S = ctx->screen;
-    if (!S.ev0) { HIP_TRY(ctx, hipEventCreate(&S.ev0)); HIP_TRY(ctx, hipEventCreate(&S.ev1)); }
-    if (!S.dcount) HIP_TRY(ctx, hipMalloc(&S.dcount, sizeof(uint32_t) * 2));
-    if (m <= S.cap) return RELMC_OK;
-    for (void* p : {(void*)S.keys, (void*)S.flags, (void*)S.idx, S.tmp}) if (p) (void)hipFree(p);
-    S.keys = nullptr; S.flags = nullptr; S.idx = nullptr; S.tmp = nullptr; S.cap = 0; S.tmp_bytes = 0;
-    const int ow = mask_words(ctx);
+    if (!ctx->screen_ev0) HIP_TRY(ctx, hipEventCreate(&ctx->screen_ev0));
+    if (!ctx->screen_ev1) HIP_TRY(ctx, hipEventCreate(&ctx->screen_ev1));
+    HIP_TRY(ctx, S.dcount.grow(2));
+    const size_t n = (size_t)m, ow = (size_t)mask_words(ctx);
+    if (n <= S.flags.size() && n <= S.idx.size() && n * ow <= S.keys.size() && S.tmp.get()) return RELMC_OK;
     size_t tb = 0;
-    (void)rocprim::select(nullptr, tb, rocprim::counting_iterator<uint32_t>(0u), (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)m, ScreenFlagSet(), ctx->stream);
-    HIP_TRY(ctx, hipMalloc(&S.keys, sizeof(uint32_t) * (size_t)ow * (size_t)m));
-    HIP_TRY(ctx, hipMalloc(&S.flags, (size_t)m));
-    HIP_TRY(ctx, hipMalloc(&S.idx, sizeof(uint32_t) * (size_t)m));
-    HIP_TRY(ctx, hipMalloc(&S.tmp, tb ? tb : 16));
-    S.cap = m; S.tmp_bytes = tb;
+    (void)rocprim::select(nullptr, tb, rocprim::counting_iterator<uint32_t>(0u), (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, ScreenFlagSet(), ctx->stream);
+    HIP_TRY(ctx, S.keys.grow(n * ow));
+    HIP_TRY(ctx, S.flags.grow(n));
+    HIP_TRY(ctx, S.idx.grow(n));
+    HIP_TRY(ctx, S.tmp.grow(tb ? tb : 16));
     return RELMC_OK;
 }
 
@@ -392,11 +381,11 @@ int screen_buffers(relmc_ctx* ctx, int64_t m)
 int screen_select(relmc_ctx* ctx, int64_t m, uint32_t* n_out)
 {
     auto& S = ctx->screen;
-    size_t tb = S.tmp_bytes;
-    HIP_TRY(ctx, rocprim::select(S.tmp, tb, rocprim::counting_iterator<uint32_t>(0u), S.flags, S.idx, S.dcount, (size_t)m, ScreenFlagSet(), ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&ctx->hstage->fail_cnt, S.dcount, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    size_t tb = S.tmp.size();
+    HIP_TRY(ctx, rocprim::select(S.tmp.get(), tb, rocprim::counting_iterator<uint32_t>(0u), S.flags.get(), S.idx.get(), S.dcount.get(), (size_t)m, ScreenFlagSet(), ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&ctx->hstage.get()->fail_cnt, S.dcount.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *n_out = ctx->hstage->fail_cnt;
+    *n_out = ctx->hstage.get()->fail_cnt;
     return RELMC_OK;
 }
 
@@ -415,19 +404,19 @@ int screen_prepass_nsq(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int6
     int rc = screen_buffers(ctx, m);
     if (rc) return rc;
     auto& S = ctx->screen;
-    HIP_TRY(ctx, hipEventRecord(S.ev0, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->screen_ev0, ctx->stream));
     const int64_t g = grid256(ctx, m);
-    if (ctx->tile == 0) hipLaunchKernelGGL(relmc_screen_sample_kernel<Tile24>, dim3((unsigned)g), dim3(256), 0, ctx->stream, reinterpret_cast<const DevCaseT<Tile24>*>(ctx->dcase), S.tab, seed, first_index, m, S.keys, S.flags);
-    else hipLaunchKernelGGL(relmc_screen_sample_kernel<Tile96>, dim3((unsigned)g), dim3(256), 0, ctx->stream, reinterpret_cast<const DevCaseT<Tile96>*>(ctx->dcase), S.tab, seed, first_index, m, S.keys, S.flags);
+    if (ctx->tile == 0) hipLaunchKernelGGL(relmc_screen_sample_kernel<Tile24>, dim3((unsigned)g), dim3(256), 0, ctx->stream, reinterpret_cast<const DevCaseT<Tile24>*>(ctx->dcase.get()), S.tab, seed, first_index, m, S.keys.get(), S.flags.get());
+    else hipLaunchKernelGGL(relmc_screen_sample_kernel<Tile96>, dim3((unsigned)g), dim3(256), 0, ctx->stream, reinterpret_cast<const DevCaseT<Tile96>*>(ctx->dcase.get()), S.tab, seed, first_index, m, S.keys.get(), S.flags.get());
     HIP_TRY(ctx, hipGetLastError());
-    size_t tb = S.tmp_bytes;
-    HIP_TRY(ctx, rocprim::select(S.tmp, tb, rocprim::counting_iterator<uint32_t>(0u), S.flags, S.idx, S.dcount, (size_t)m, ScreenFlagSet(), ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(S.ev1, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&ctx->hstage->fail_cnt, S.dcount, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    size_t tb = S.tmp.size();
+    HIP_TRY(ctx, rocprim::select(S.tmp.get(), tb, rocprim::counting_iterator<uint32_t>(0u), S.flags.get(), S.idx.get(), S.dcount.get(), (size_t)m, ScreenFlagSet(), ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->screen_ev1, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&ctx->hstage.get()->fail_cnt, S.dcount.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *n_surv = ctx->hstage->fail_cnt;
+    *n_surv = ctx->hstage.get()->fail_cnt;
     float t = 0.f;
-    if (ms && hipEventElapsedTime(&t, S.ev0, S.ev1) == hipSuccess) *ms += t;
+    if (ms && hipEventElapsedTime(&t, ctx->screen_ev0, ctx->screen_ev1) == hipSuccess) *ms += t;
     return RELMC_OK;
 }
 
@@ -436,7 +425,7 @@ int screen_gather_keys(relmc_ctx* ctx, uint32_t n_surv, uint32_t* keys_out)
     if (n_surv == 0) return RELMC_OK;
     auto& S = ctx->screen;
     const int ow = mask_words(ctx);
-    hipLaunchKernelGGL(relmc_screen_gather_keys_kernel, dim3((unsigned)grid256(ctx, (int64_t)n_surv * ow)), dim3(256), 0, ctx->stream, S.keys, S.idx, (int64_t)n_surv, ow, keys_out);
+    hipLaunchKernelGGL(relmc_screen_gather_keys_kernel, dim3((unsigned)grid256(ctx, (int64_t)n_surv * ow)), dim3(256), 0, ctx->stream, S.keys.get(), S.idx.get(), (int64_t)n_surv, ow, keys_out);
     HIP_TRY(ctx, hipGetLastError());
     return RELMC_OK;
 }
@@ -449,8 +438,8 @@ int screen_prepass_rows(relmc_ctx* ctx, int64_t first, int64_t n, uint32_t* n_su
     if (rc) return rc;
     auto& S = ctx->screen;
     const int64_t g = grid256(ctx, n);
-    if (ctx->tile == 0) hipLaunchKernelGGL(relmc_screen_rows_kernel<Tile24::OW>, dim3((unsigned)g), dim3(256), 0, ctx->stream, S.tab, ctx->db_keys, first, n, ctx->nb, ctx->db_dns, ctx->db_meta, ctx->db_nodal, S.flags);
-    else hipLaunchKernelGGL(relmc_screen_rows_kernel<Tile96::OW>, dim3((unsigned)g), dim3(256), 0, ctx->stream, S.tab, ctx->db_keys, first, n, ctx->nb, ctx->db_dns, ctx->db_meta, ctx->db_nodal, S.flags);
+    if (ctx->tile == 0) hipLaunchKernelGGL(relmc_screen_rows_kernel<Tile24::OW>, dim3((unsigned)g), dim3(256), 0, ctx->stream, S.tab, ctx->db.keys.get(), first, n, ctx->nb, ctx->db.dns.get(), ctx->db.meta.get(), ctx->db.nodal.get(), S.flags.get());
+    else hipLaunchKernelGGL(relmc_screen_rows_kernel<Tile96::OW>, dim3((unsigned)g), dim3(256), 0, ctx->stream, S.tab, ctx->db.keys.get(), first, n, ctx->nb, ctx->db.dns.get(), ctx->db.meta.get(), ctx->db.nodal.get(), S.flags.get());
     HIP_TRY(ctx, hipGetLastError());
     return screen_select(ctx, n, n_surv);
 }
@@ -465,13 +454,13 @@ int screen_seq_compact(relmc_ctx* ctx, const uint32_t* masks, int n_years, uint1
     if (rc) return rc;
     auto& S = ctx->screen;
     const int64_t g = grid256(ctx, total);
-    HIP_TRY(ctx, hipEventRecord(S.ev0, ctx->stream));
-    if (ctx->tile == 0) hipLaunchKernelGGL(relmc_seq_flag_kernel<Tile24::OW>, dim3((unsigned)g), dim3(256), 0, ctx->stream, S.tab, masks, ctx->dlf, hpy, total, S.flags);
-    else hipLaunchKernelGGL(relmc_seq_flag_kernel<Tile96::OW>, dim3((unsigned)g), dim3(256), 0, ctx->stream, S.tab, masks, ctx->dlf, hpy, total, S.flags);
+    HIP_TRY(ctx, hipEventRecord(ctx->screen_ev0, ctx->stream));
+    if (ctx->tile == 0) hipLaunchKernelGGL(relmc_seq_flag_kernel<Tile24::OW>, dim3((unsigned)g), dim3(256), 0, ctx->stream, S.tab, masks, ctx->dlf.get(), hpy, total, S.flags.get());
+    else hipLaunchKernelGGL(relmc_seq_flag_kernel<Tile96::OW>, dim3((unsigned)g), dim3(256), 0, ctx->stream, S.tab, masks, ctx->dlf.get(), hpy, total, S.flags.get());
     HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(relmc_seq_compact_flags_kernel, dim3(n_years), dim3(256), 0, ctx->stream, S.flags, hpy, hours, counts, ncont);
+    hipLaunchKernelGGL(relmc_seq_compact_flags_kernel, dim3(n_years), dim3(256), 0, ctx->stream, S.flags.get(), hpy, hours, counts, ncont);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(S.ev1, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->screen_ev1, ctx->stream));
     return RELMC_OK;
 }
 
@@ -506,19 +495,18 @@ int32_t relmc_debug_screen_states(relmc_ctx* ctx, const uint8_t* states_host, co
     if (rc) return rc;
     auto& S = ctx->screen;
     const int ow = mask_words(ctx), ncomp = ctx->ncomp;
-    uint8_t* dst = nullptr; double* dsc = nullptr;
-    HIP_TRY(ctx, hipMalloc(&dst, (size_t)n * ncomp));
-    if (load_scale_host && hipMalloc(&dsc, sizeof(double) * (size_t)n) != hipSuccess) { (void)hipFree(dst); return fail(ctx, RELMC_ERR_HIP, "relmc_debug_screen_states: allocation failed"); }
-    bool ok = hipMemcpyAsync(dst, states_host, (size_t)n * ncomp, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
-              (!dsc || hipMemcpyAsync(dsc, load_scale_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    DevBuf<uint8_t> dst; DevBuf<double> dsc;
+    HIP_TRY(ctx, dst.grow((size_t)n * ncomp));
+    if (load_scale_host) HIP_TRY(ctx, dsc.grow((size_t)n));
+    bool ok = hipMemcpyAsync(dst.get(), states_host, (size_t)n * ncomp, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+              (!dsc.get() || hipMemcpyAsync(dsc.get(), load_scale_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     if (ok) {
-        hipLaunchKernelGGL(relmc_screen_pack_kernel, dim3((unsigned)grid256(ctx, n * ow)), dim3(256), 0, ctx->stream, dst, n, ncomp, ow, S.keys);
-        if (ctx->tile == 0) hipLaunchKernelGGL(relmc_screen_keys_kernel<Tile24::OW>, dim3((unsigned)grid256(ctx, n)), dim3(256), 0, ctx->stream, S.tab, S.keys, dsc, n, S.flags);
-        else hipLaunchKernelGGL(relmc_screen_keys_kernel<Tile96::OW>, dim3((unsigned)grid256(ctx, n)), dim3(256), 0, ctx->stream, S.tab, S.keys, dsc, n, S.flags);
-        ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(certified_host, S.flags, (size_t)n, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+        hipLaunchKernelGGL(relmc_screen_pack_kernel, dim3((unsigned)grid256(ctx, n * ow)), dim3(256), 0, ctx->stream, dst.get(), n, ncomp, ow, S.keys.get());
+        if (ctx->tile == 0) hipLaunchKernelGGL(relmc_screen_keys_kernel<Tile24::OW>, dim3((unsigned)grid256(ctx, n)), dim3(256), 0, ctx->stream, S.tab, S.keys.get(), dsc.get(), n, S.flags.get());
+        else hipLaunchKernelGGL(relmc_screen_keys_kernel<Tile96::OW>, dim3((unsigned)grid256(ctx, n)), dim3(256), 0, ctx->stream, S.tab, S.keys.get(), dsc.get(), n, S.flags.get());
+        ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(certified_host, S.flags.get(), (size_t)n, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
              hipStreamSynchronize(ctx->stream) == hipSuccess;
     }
-    (void)hipFree(dst); if (dsc) (void)hipFree(dsc);
     if (!ok) return fail(ctx, RELMC_ERR_HIP, "relmc_debug_screen_states: kernel / copy failed");
     for (int64_t i = 0; i < n; ++i) certified_host[i] = certified_host[i] ? 0 : 1;
     return RELMC_OK;

@@ -10,25 +10,10 @@
 
 namespace relmc_host {
 
-void seq_free(relmc_ctx* ctx)
-{
-    for (void* q : {(void*)ctx->sq_dm, (void*)ctx->sq_hours, (void*)ctx->sq_curt, (void*)ctx->sq_counts, (void*)ctx->sq_off, (void*)ctx->sq_year, (void*)ctx->dseq,
-                    (void*)ctx->dlf, (void*)ctx->dhl1, (void*)ctx->dsorted, (void*)ctx->dsuffix, (void*)ctx->h1_lole, (void*)ctx->h1_eue, (void*)ctx->h1_part}) if (q) (void)hipFree(q);
-    ctx->h1_lole = ctx->h1_eue = ctx->h1_part = nullptr; ctx->h1_cap = 0; ctx->h1_part_cap = 0;
-    ctx->sq_dm = nullptr; ctx->sq_hours = nullptr; ctx->sq_curt = nullptr; ctx->sq_counts = ctx->sq_off = nullptr; ctx->sq_year = nullptr;
-    ctx->sq_dm_words = 0; ctx->sq_nh = 0; ctx->sq_years = 0;
-    ctx->dseq = nullptr; ctx->dlf = nullptr; ctx->dhl1 = nullptr; ctx->dsorted = ctx->dsuffix = nullptr; ctx->has_seq = false; ctx->has_hl1 = false;
-}
-
 namespace {
-// chronology of years [first_year, first_year + n_years) into device masks (every word written)
-// *dmasks_out == nullptr on entry: a buffer is allocated for the caller (who frees it); otherwise the masks go into the caller's buffer
-int seq_sample(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int n_years, uint32_t** dmasks_out)
+// chronology of years [first_year, first_year + n_years) into the caller's device masks dm (n_years * hpy * mw words, every word written)
+int seq_sample(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int n_years, uint32_t* dm)
 {
-    const size_t words = (size_t)n_years * ctx->hseq.hpy * ctx->hseq.mw;
-    const bool own = *dmasks_out == nullptr;
-    uint32_t* dm = *dmasks_out;
-    if (own) HIP_TRY(ctx, hipMalloc(&dm, words * sizeof(uint32_t)));
     // segments of at most ~48 KB of masks in LDS, and at least ~2 workgroups per CU over the launch (a segment's chains are walked from hour 0: cheap)
     const int hpy = ctx->hseq.hpy, mw = ctx->hseq.mw, cap = (48 * 1024) / (4 * mw) - 64;
     int nseg = (hpy + cap - 1) / cap;
@@ -38,9 +23,8 @@ int seq_sample(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int n_years, 
     int sl = seg_len;                                            // LDS row stride = 64 / mw (mod 64): conflict-free word-major rows
     while (sl % 64 != (64 / mw) % 64) ++sl;
     hipLaunchKernelGGL(relmc_seq_sampling_kernel, dim3((unsigned)((int64_t)n_years * nseg)), dim3(256), (size_t)sl * mw * sizeof(uint32_t), ctx->stream,
-                       ctx->dseq, seed, first_year, nseg, seg_len, sl, dm);
-    if (hipGetLastError() != hipSuccess) { if (own) (void)hipFree(dm); return fail(ctx, RELMC_ERR_HIP, "seq: sampling launch failed"); }
-    *dmasks_out = dm;
+                       ctx->dseq.get(), seed, first_year, nseg, seg_len, sl, dm);
+    if (hipGetLastError() != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "seq: sampling launch failed");
     return RELMC_OK;
 }
 }  // namespace
@@ -66,13 +50,12 @@ int32_t relmc_seq_load(relmc_ctx* ctx, const double* mttf, const double* mttr, i
         if (!(mttf[k] > 0) || !(mttr[k] > 0)) return fail(ctx, RELMC_ERR_INVALID, "relmc_seq_load: MTTF / MTTR must be positive");
         q.mttf[k] = mttf[k]; q.mttr[k] = mttr[k];
     }
-    if (!ctx->dseq) HIP_TRY(ctx, hipMalloc(&ctx->dseq, sizeof(SeqCase)));
-    if (ctx->dlf) (void)hipFree(ctx->dlf);
-    ctx->dlf = nullptr;
-    HIP_TRY(ctx, hipMalloc(&ctx->dlf, sizeof(double) * hpy));
+    HIP_TRY(ctx, ctx->dseq.grow(1));
+    ctx->dlf.reset();
+    HIP_TRY(ctx, ctx->dlf.grow((size_t)hpy));
     ctx->hlf.assign(load_factors, load_factors + hpy);
-    HIP_TRY(ctx, hipMemcpy(ctx->dseq, &q, sizeof(q), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->dlf, load_factors, sizeof(double) * hpy, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->dseq.get(), &q, sizeof(q), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->dlf.get(), load_factors, sizeof(double) * hpy, hipMemcpyHostToDevice));
     ctx->has_seq = true;
     return RELMC_OK;
 }
@@ -84,17 +67,15 @@ int32_t relmc_seq_mcsampling(relmc_ctx* ctx, uint64_t seed, uint64_t first_year,
     if (num_years < 0 || (num_years > 0 && !state_host)) return fail(ctx, RELMC_ERR_INVALID, "relmc_seq_mcsampling: bad arguments");
     if (num_years == 0) return RELMC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint32_t* dm = nullptr;
-    int rc = seq_sample(ctx, seed, first_year, num_years, &dm);
-    if (rc) return rc;
     const int64_t nh = (int64_t)num_years * ctx->hseq.hpy;
     const size_t bytes = (size_t)nh * ctx->hseq.ncomp;
-    uint8_t* dst = nullptr;
-    if (hipMalloc(&dst, bytes) != hipSuccess) { (void)hipFree(dm); return fail(ctx, RELMC_ERR_HIP, "relmc_seq_mcsampling: allocation failed"); }
-    hipLaunchKernelGGL(relmc_seq_expand_kernel, dim3(ctx->num_cu * 8), dim3(256), 0, ctx->stream, dm, nh, ctx->hseq.ncomp, ctx->hseq.mw, dst);
+    DevBuf<uint32_t> dm; DevBuf<uint8_t> dst;
+    if (dm.grow((size_t)nh * ctx->hseq.mw) != hipSuccess || dst.grow(bytes) != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "relmc_seq_mcsampling: allocation failed");
+    int rc = seq_sample(ctx, seed, first_year, num_years, dm.get());
+    if (rc) return rc;
+    hipLaunchKernelGGL(relmc_seq_expand_kernel, dim3(ctx->num_cu * 8), dim3(256), 0, ctx->stream, dm.get(), nh, ctx->hseq.ncomp, ctx->hseq.mw, dst.get());
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
-        hipMemcpy(state_host, dst, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(ctx, RELMC_ERR_HIP, "relmc_seq_mcsampling: kernel / copy failed");
-    (void)hipFree(dm); (void)hipFree(dst);
+        hipMemcpy(state_host, dst.get(), bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(ctx, RELMC_ERR_HIP, "relmc_seq_mcsampling: kernel / copy failed");
     return rc;
 }
 
@@ -125,37 +106,27 @@ int32_t relmc_seq_years(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int3
     const int hpy = ctx->hseq.hpy;
     // the device buffers of a step live in the context and only ever grow
     const size_t nh = (size_t)n_years * hpy, words = nh * (size_t)ctx->hseq.mw;
-    bool alloc_ok = true;
-    if (ctx->sq_dm_words < words) { if (ctx->sq_dm) (void)hipFree(ctx->sq_dm); ctx->sq_dm = nullptr; ctx->sq_dm_words = 0;
-                                    alloc_ok = hipMalloc(&ctx->sq_dm, words * sizeof(uint32_t)) == hipSuccess; if (alloc_ok) ctx->sq_dm_words = words; }
-    if (alloc_ok && ctx->sq_nh < nh) { if (ctx->sq_hours) (void)hipFree(ctx->sq_hours); if (ctx->sq_curt) (void)hipFree(ctx->sq_curt); ctx->sq_hours = nullptr; ctx->sq_curt = nullptr; ctx->sq_nh = 0;
-                                       alloc_ok = hipMalloc(&ctx->sq_hours, nh * sizeof(uint16_t)) == hipSuccess && hipMalloc(&ctx->sq_curt, nh * sizeof(double)) == hipSuccess; if (alloc_ok) ctx->sq_nh = nh; }
-    if (alloc_ok && ctx->sq_years < n_years) {
-        for (void* q : {(void*)ctx->sq_counts, (void*)ctx->sq_off, (void*)ctx->sq_year}) if (q) (void)hipFree(q);
-        ctx->sq_counts = ctx->sq_off = nullptr; ctx->sq_year = nullptr; ctx->sq_years = 0;
-        // sq_counts: [0, n) listed hours per year, [cap, cap + n) contingency hours per year (pre-screen)
-        alloc_ok = hipMalloc(&ctx->sq_counts, sizeof(uint32_t) * 2 * n_years) == hipSuccess && hipMalloc(&ctx->sq_off, sizeof(uint32_t) * (n_years + 1)) == hipSuccess &&
-                   hipMalloc(&ctx->sq_year, sizeof(double) * 3 * n_years) == hipSuccess;
-        if (alloc_ok) ctx->sq_years = n_years;
-    }
-    if (!alloc_ok) return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: device allocation failed");
-    uint32_t* dm = ctx->sq_dm; uint16_t* const dhours = ctx->sq_hours; uint32_t* const dcounts = ctx->sq_counts; uint32_t* const doff = ctx->sq_off;
-    double* const dcurt = ctx->sq_curt; double* const dyear = ctx->sq_year;
-    auto cleanup = [&]() {};
-    int rc = seq_sample(ctx, seed, first_year, n_years, &dm);
+    auto& Q = ctx->sq;
+    // counts: [0, n) listed hours per year, [n, 2 n) contingency hours per year (pre-screen), n = the years the buffer was made for
+    if (Q.dm.grow(words) != hipSuccess || Q.hours.grow(nh) != hipSuccess || Q.curt.grow(nh) != hipSuccess || Q.counts.grow(2 * (size_t)n_years) != hipSuccess ||
+        Q.off.grow((size_t)n_years + 1) != hipSuccess || Q.year.grow(3 * (size_t)n_years) != hipSuccess)
+        return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: device allocation failed");
+    uint32_t* const dm = Q.dm.get(); uint16_t* const dhours = Q.hours.get(); uint32_t* const dcounts = Q.counts.get(); uint32_t* const doff = Q.off.get();
+    double* const dcurt = Q.curt.get(); double* const dyear = Q.year.get();
+    int rc = seq_sample(ctx, seed, first_year, n_years, dm);
     if (rc) return rc;
     std::vector<uint32_t> counts(n_years), ncont(n_years), off(n_years + 1, 0);
     bool ok = hipMemsetAsync(dcurt, 0, nh * sizeof(double), ctx->stream) == hipSuccess;
     // screen = 1 (relmc_screen.hip): the contingency hours are counted as before, but only the ones the zero-curtailment certificate does not cover
     // -- at the hour's own load factor -- are listed for the interior point; a covered hour's curtailment stays the 0 it was set to above
     const bool screen = o.screen != 0 && ctx->screen.tab.valid != 0;
-    uint32_t* const dncont = dcounts + ctx->sq_years;
+    uint32_t* const dncont = dcounts + Q.counts.size() / 2;
     if (screen) ok = ok && screen_seq_compact(ctx, dm, n_years, dhours, dcounts, dncont) == RELMC_OK;
     else hipLaunchKernelGGL(relmc_seq_compact_kernel, dim3(n_years), dim3(256), 0, ctx->stream, dm, hpy, ctx->hseq.mw, dhours, dcounts);
     ok = ok && hipGetLastError() == hipSuccess && hipMemcpyAsync(counts.data(), dcounts, sizeof(uint32_t) * n_years, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
          (!screen || hipMemcpyAsync(ncont.data(), dncont, sizeof(uint32_t) * n_years, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess) &&
          hipStreamSynchronize(ctx->stream) == hipSuccess;
-    if (!ok) { cleanup(); return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: compaction failed"); }
+    if (!ok) return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: compaction failed");
     int64_t certified = 0;
     for (int y = 0; y < n_years; ++y) {
         off[y + 1] = off[y] + counts[y];
@@ -164,43 +135,42 @@ int32_t relmc_seq_years(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int3
     }
     const int64_t nlp = off[n_years];
     double ms = 0.0;
-    if (screen) { float t = 0.f; if (hipEventElapsedTime(&t, ctx->screen.ev0, ctx->screen.ev1) == hipSuccess) ms += t; }      // the certificate's pre-pass (the stream was synchronised above)
+    if (screen) { float t = 0.f; if (hipEventElapsedTime(&t, ctx->screen_ev0, ctx->screen_ev1) == hipSuccess) ms += t; }      // the certificate's pre-pass (the stream was synchronised above)
     if (nlp > 0) {
-        if (hipMemcpyAsync(doff, off.data(), sizeof(uint32_t) * (n_years + 1), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { cleanup(); return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: H2D failed"); }
+        if (hipMemcpyAsync(doff, off.data(), sizeof(uint32_t) * (n_years + 1), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: H2D failed");
         EvalArgs a = make_args(o);
         a.fail_threshold = curtail_threshold;
-        a.n = nlp; a.seq_masks = dm; a.seq_offsets = doff; a.seq_hours = dhours; a.load_factors = ctx->dlf; a.curt = dcurt;
+        a.n = nlp; a.seq_masks = dm; a.seq_offsets = doff; a.seq_hours = dhours; a.load_factors = ctx->dlf.get(); a.curt = dcurt;
         a.seq_nyears = n_years; a.seq_hpy = hpy;
         int blocks = 0;
         rc = fail_arm(ctx, a, 0, true, a.n);
-        if (rc) { cleanup(); return rc; }
+        if (rc) return rc;
         rc = launch_eval(ctx, 2, a, &blocks);
-        if (rc) { cleanup(); return rc; }
+        if (rc) return rc;
         // accumulators and the count of listed hours in one synchronisation (pinned staging), as in the fused non-sequential pass
-        if (launch_finalize(ctx, blocks) != RELMC_OK || hipMemcpyAsync(&ctx->hstage->acc, ctx->dacc, sizeof(relmc_acc), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            (a.fail_count && hipMemcpyAsync(&ctx->hstage->fail_cnt, ctx->dfail_count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) { cleanup(); return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: finalize failed"); }
+        if (launch_finalize(ctx, blocks) != RELMC_OK || hipMemcpyAsync(&ctx->hstage.get()->acc, ctx->dacc.get(), sizeof(relmc_acc), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            (a.fail_count && hipMemcpyAsync(&ctx->hstage.get()->fail_cnt, ctx->retry.fail_count.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: finalize failed");
         rc = finish_timing(ctx);
-        if (rc) { cleanup(); return rc; }
-        *acc_out = ctx->hstage->acc;
-        const uint32_t listed = a.fail_count ? ctx->hstage->fail_cnt : 0u;
+        if (rc) return rc;
+        *acc_out = ctx->hstage.get()->acc;
+        const uint32_t listed = a.fail_count ? ctx->hstage.get()->fail_cnt : 0u;
         ms += ctx->last_kernel_ms;
         RetryOut ro;                                                   // hours the primary elimination order did not converge on
         const ScaleFn scale = [&](unsigned long long u) { return ctx->hlf[(size_t)(u % (unsigned long long)hpy)]; };
         rc = fail_retry(ctx, o, curtail_threshold, &scale, ro, &ms, a.fail_count ? &listed : nullptr);
-        if (rc) { cleanup(); return rc; }
+        if (rc) return rc;
         for (size_t r = 0; r < ro.rec.size(); ++r) {
             acc_add_unit(acc_out, ro.rec[r], ro.dns[r], ro.meta[r], &ro.nodal[r * (size_t)ctx->nb], ctx->nb, ctx->ncomp, curtail_threshold);
-            if (hipMemcpy(dcurt + ro.rec[r].unit, &ro.dns[r], sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { cleanup(); return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: H2D failed"); }
+            if (hipMemcpy(dcurt + ro.rec[r].unit, &ro.dns[r], sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: H2D failed");
         }
     }
     acc_out->n += certified; acc_out->n_screened += certified;
     hipLaunchKernelGGL(relmc_seq_annual_kernel, dim3(n_years), dim3(256), 0, ctx->stream, dcurt, hpy, curtail_threshold, dyear);
     std::vector<double> yr((size_t)3 * n_years);
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(yr.data(), dyear, sizeof(double) * 3 * n_years, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess) { cleanup(); return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: annual indices failed"); }
+        hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: annual indices failed");
     for (int y = 0; y < n_years; ++y) { years_out[y].ens = yr[3 * y]; years_out[y].dlc = yr[3 * y + 1]; years_out[y].nlc = yr[3 * y + 2]; }
     ctx->last_kernel_ms = ms;
-    cleanup();
     return RELMC_OK;
 }
 
@@ -341,15 +311,14 @@ int32_t relmc_hl1_load(relmc_ctx* ctx, int32_t ngen, const double* capacity_mw, 
     std::vector<double> sorted(hourly_load_mw, hourly_load_mw + nhours), suffix(nhours + 1, 0.0);
     std::sort(sorted.begin(), sorted.end());
     for (int k = nhours - 1; k >= 0; --k) suffix[k] = suffix[k + 1] + sorted[k];
-    if (ctx->dsorted) (void)hipFree(ctx->dsorted);
-    if (ctx->dsuffix) (void)hipFree(ctx->dsuffix);
-    ctx->dsorted = ctx->dsuffix = nullptr;
-    if (!ctx->dhl1) HIP_TRY(ctx, hipMalloc(&ctx->dhl1, sizeof(Hl1Case)));
-    HIP_TRY(ctx, hipMalloc(&ctx->dsorted, sizeof(double) * nhours));
-    HIP_TRY(ctx, hipMalloc(&ctx->dsuffix, sizeof(double) * (nhours + 1)));
-    HIP_TRY(ctx, hipMemcpy(ctx->dhl1, &h, sizeof(h), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->dsorted, sorted.data(), sizeof(double) * nhours, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->dsuffix, suffix.data(), sizeof(double) * (nhours + 1), hipMemcpyHostToDevice));
+    auto& H = ctx->hl1;
+    H.sorted.reset(); H.suffix.reset();
+    HIP_TRY(ctx, H.dcase.grow(1));
+    HIP_TRY(ctx, H.sorted.grow((size_t)nhours));
+    HIP_TRY(ctx, H.suffix.grow((size_t)nhours + 1));
+    HIP_TRY(ctx, hipMemcpy(ctx->hl1.dcase.get(), &h, sizeof(h), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->hl1.sorted.get(), sorted.data(), sizeof(double) * nhours, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->hl1.suffix.get(), suffix.data(), sizeof(double) * (nhours + 1), hipMemcpyHostToDevice));
     ctx->hl1_hours = nhours; ctx->has_hl1 = true;
     return RELMC_OK;
 }
@@ -366,24 +335,13 @@ int32_t relmc_hl1_nsq(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64
     int64_t blocks = (n + 255) / 256;
     if (blocks > (int64_t)ctx->num_cu * 8) blocks = (int64_t)ctx->num_cu * 8;
     // per-iteration outputs and block partials live in the context between calls (three hipMalloc / hipFree pairs were 0.5 ms of a 0.8 ms call)
-    if ((iter_lole_host || iter_eue_host) && n > ctx->h1_cap) {
-        if (ctx->h1_lole) (void)hipFree(ctx->h1_lole);
-        if (ctx->h1_eue) (void)hipFree(ctx->h1_eue);
-        ctx->h1_lole = ctx->h1_eue = nullptr; ctx->h1_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->h1_lole, sizeof(double) * (size_t)n));
-        HIP_TRY(ctx, hipMalloc(&ctx->h1_eue, sizeof(double) * (size_t)n));
-        ctx->h1_cap = n;
-    }
-    if (blocks > ctx->h1_part_cap) {
-        if (ctx->h1_part) (void)hipFree(ctx->h1_part);
-        ctx->h1_part = nullptr; ctx->h1_part_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->h1_part, sizeof(double) * 4 * (size_t)blocks));
-        ctx->h1_part_cap = blocks;
-    }
-    double* const dl = iter_lole_host ? ctx->h1_lole : nullptr; double* const de = iter_eue_host ? ctx->h1_eue : nullptr; double* const dpart = ctx->h1_part;
+    auto& H = ctx->hl1;
+    if (iter_lole_host || iter_eue_host) { HIP_TRY(ctx, H.lole.grow((size_t)n)); HIP_TRY(ctx, H.eue.grow((size_t)n)); }
+    HIP_TRY(ctx, H.part.grow(4 * (size_t)blocks));
+    double* const dl = iter_lole_host ? ctx->hl1.lole.get() : nullptr; double* const de = iter_eue_host ? ctx->hl1.eue.get() : nullptr; double* const dpart = ctx->hl1.part.get();
     int rc = RELMC_OK;
     (void)hipEventRecord(ctx->ev0, ctx->stream);
-    hipLaunchKernelGGL(relmc_hl1_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ctx->dhl1, ctx->dsorted, ctx->dsuffix, seed,
+    hipLaunchKernelGGL(relmc_hl1_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ctx->hl1.dcase.get(), ctx->hl1.sorted.get(), ctx->hl1.suffix.get(), seed,
                        first_index, n, dl, de, dpart);
     (void)hipEventRecord(ctx->ev1, ctx->stream);
     std::vector<double> part((size_t)4 * blocks);

@@ -15,36 +15,24 @@ namespace relmc_host {
 // chunk k in and chunk k-2 out while the GPU works on chunk k-1.  Device and staging buffers are allocated once per context.
 constexpr int64_t kPipeChunk = 131072;
 
-void pipe_free(relmc_ctx* ctx)
-{
-    auto& P = ctx->pipe;
-    for (int b = 0; b < 2; ++b) {
-        for (void* p : {(void*)P.d_st[b], (void*)P.d_sc[b], (void*)P.d_dns[b], (void*)P.d_nod[b], (void*)P.d_stat[b], (void*)P.d_it[b]}) if (p) (void)hipFree(p);
-        for (void* p : {(void*)P.h_st[b], (void*)P.h_sc[b], (void*)P.h_dns[b], (void*)P.h_nod[b], (void*)P.h_stat[b], (void*)P.h_it[b]}) if (p) (void)hipHostFree(p);
-        for (hipEvent_t e : {P.e_up[b], P.e_ks[b], P.e_ke[b], P.e_down[b]}) if (e) (void)hipEventDestroy(e);
-    }
-    if (P.up) (void)hipStreamDestroy(P.up);
-    if (P.down) (void)hipStreamDestroy(P.down);
-    P = relmc_ctx::HostPipe();
-}
-
 int pipe_ensure(relmc_ctx* ctx)
 {
     auto& P = ctx->pipe;
     if (P.ready && P.ncomp == ctx->ncomp && P.nb == ctx->nb) return RELMC_OK;
-    pipe_free(ctx);
+    P.ready = false;
+    if (!P.up) HIP_TRY(ctx, hipStreamCreateWithFlags(&P.up, hipStreamNonBlocking));
+    if (!P.down) HIP_TRY(ctx, hipStreamCreateWithFlags(&P.down, hipStreamNonBlocking));
+    for (int b = 0; b < 2; ++b)
+        for (hipEvent_t* e : {&P.e_up[b], &P.e_ks[b], &P.e_ke[b], &P.e_down[b]}) if (!*e) HIP_TRY(ctx, hipEventCreate(e));
     const size_t c = (size_t)kPipeChunk, nc = (size_t)ctx->ncomp, nb = (size_t)ctx->nb;
-    bool ok = hipStreamCreateWithFlags(&P.up, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&P.down, hipStreamNonBlocking) == hipSuccess;
-    for (int b = 0; b < 2 && ok; ++b) {
-        ok = hipEventCreate(&P.e_up[b]) == hipSuccess && hipEventCreate(&P.e_ks[b]) == hipSuccess && hipEventCreate(&P.e_ke[b]) == hipSuccess &&
-             hipEventCreate(&P.e_down[b]) == hipSuccess &&
-             hipMalloc(&P.d_st[b], c * nc) == hipSuccess && hipMalloc(&P.d_sc[b], c * 8) == hipSuccess && hipMalloc(&P.d_dns[b], c * 8) == hipSuccess &&
-             hipMalloc(&P.d_nod[b], c * nb * 8) == hipSuccess && hipMalloc(&P.d_stat[b], c * 4) == hipSuccess && hipMalloc(&P.d_it[b], c * 4) == hipSuccess &&
-             hipHostMalloc(&P.h_st[b], c * nc, hipHostMallocDefault) == hipSuccess && hipHostMalloc(&P.h_sc[b], c * 8, hipHostMallocDefault) == hipSuccess &&
-             hipHostMalloc(&P.h_dns[b], c * 8, hipHostMallocDefault) == hipSuccess && hipHostMalloc(&P.h_nod[b], c * nb * 8, hipHostMallocDefault) == hipSuccess &&
-             hipHostMalloc(&P.h_stat[b], c * 4, hipHostMallocDefault) == hipSuccess && hipHostMalloc(&P.h_it[b], c * 4, hipHostMallocDefault) == hipSuccess;
+    bool ok = true;
+    for (auto& B : P.buf) {
+        B = {};                  // sized for the case's component and bus counts: rebuilt when they change
+        ok = ok && B.d_st.grow(c * nc) == hipSuccess && B.d_sc.grow(c) == hipSuccess && B.d_dns.grow(c) == hipSuccess && B.d_nod.grow(c * nb) == hipSuccess &&
+             B.d_stat.grow(c) == hipSuccess && B.d_it.grow(c) == hipSuccess && B.h_st.grow(c * nc) == hipSuccess && B.h_sc.grow(c) == hipSuccess &&
+             B.h_dns.grow(c) == hipSuccess && B.h_nod.grow(c * nb) == hipSuccess && B.h_stat.grow(c) == hipSuccess && B.h_it.grow(c) == hipSuccess;
     }
-    if (!ok) { pipe_free(ctx); return fail(ctx, RELMC_ERR_HIP, "host-buffer pipeline: allocation failed"); }
+    if (!ok) { for (auto& B : P.buf) B = {}; return fail(ctx, RELMC_ERR_HIP, "host-buffer pipeline: allocation failed"); }
     P.ready = true; P.ncomp = ctx->ncomp; P.nb = ctx->nb;
     return RELMC_OK;
 }
@@ -80,36 +68,36 @@ int pipe_run(relmc_ctx* ctx, const uint8_t* states, const double* load_scale, in
         HIP_TRY(ctx, hipEventSynchronize(P.e_down[b]));
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, P.e_ks[b], P.e_ke[b]) == hipSuccess) kernel_ms += ms;
-        std::memcpy(dns + lo, P.h_dns[b], sizeof(double) * (size_t)m);
-        if (nodal) par_memcpy(nodal + (size_t)lo * nb, P.h_nod[b], sizeof(double) * (size_t)m * nb);
-        if (status) std::memcpy(status + lo, P.h_stat[b], sizeof(int32_t) * (size_t)m);
-        if (iters) std::memcpy(iters + lo, P.h_it[b], sizeof(int32_t) * (size_t)m);
+        std::memcpy(dns + lo, P.buf[b].h_dns.get(), sizeof(double) * (size_t)m);
+        if (nodal) par_memcpy(nodal + (size_t)lo * nb, P.buf[b].h_nod.get(), sizeof(double) * (size_t)m * nb);
+        if (status) std::memcpy(status + lo, P.buf[b].h_stat.get(), sizeof(int32_t) * (size_t)m);
+        if (iters) std::memcpy(iters + lo, P.buf[b].h_it.get(), sizeof(int32_t) * (size_t)m);
         return RELMC_OK;
     };
     for (int64_t k = 0; k < nchunk; ++k) {
         const int b = (int)(k & 1);
         const int64_t lo = k * kPipeChunk, m = (n - lo) < kPipeChunk ? (n - lo) : kPipeChunk;
         if (k >= 2) { rc = drain(k - 2); if (rc) return rc; }     // frees slot b (device buffers and staging)
-        par_memcpy(P.h_st[b], states + (size_t)lo * nc, (size_t)m * nc);
-        if (load_scale) std::memcpy(P.h_sc[b], load_scale + lo, sizeof(double) * (size_t)m);
-        HIP_TRY(ctx, hipMemcpyAsync(P.d_st[b], P.h_st[b], (size_t)m * nc, hipMemcpyHostToDevice, P.up));
-        if (load_scale) HIP_TRY(ctx, hipMemcpyAsync(P.d_sc[b], P.h_sc[b], sizeof(double) * (size_t)m, hipMemcpyHostToDevice, P.up));
+        par_memcpy(P.buf[b].h_st.get(), states + (size_t)lo * nc, (size_t)m * nc);
+        if (load_scale) std::memcpy(P.buf[b].h_sc.get(), load_scale + lo, sizeof(double) * (size_t)m);
+        HIP_TRY(ctx, hipMemcpyAsync(P.buf[b].d_st.get(), P.buf[b].h_st.get(), (size_t)m * nc, hipMemcpyHostToDevice, P.up));
+        if (load_scale) HIP_TRY(ctx, hipMemcpyAsync(P.buf[b].d_sc.get(), P.buf[b].h_sc.get(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, P.up));
         HIP_TRY(ctx, hipEventRecord(P.e_up[b], P.up));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, P.e_up[b], 0));
         EvalArgs a = make_args(o);
         a.fail_threshold = fail_threshold;
-        a.n = m; a.states = P.d_st[b]; a.load_scale = load_scale ? P.d_sc[b] : nullptr;
-        a.dns = P.d_dns[b]; a.nodal = nodal ? P.d_nod[b] : nullptr; a.status = status ? P.d_stat[b] : nullptr; a.iters = iters ? P.d_it[b] : nullptr;
+        a.n = m; a.states = P.buf[b].d_st.get(); a.load_scale = load_scale ? P.buf[b].d_sc.get() : nullptr;
+        a.dns = P.buf[b].d_dns.get(); a.nodal = nodal ? P.buf[b].d_nod.get() : nullptr; a.status = status ? P.buf[b].d_stat.get() : nullptr; a.iters = iters ? P.buf[b].d_it.get() : nullptr;
         int rows = 0;
         rc = fail_arm(ctx, a, lo, k == 0, n);
         if (rc) return rc;
         rc = launch_eval(ctx, 1, a, &rows, P.e_ks[b], P.e_ke[b]);
         if (rc) return rc;
         HIP_TRY(ctx, hipStreamWaitEvent(P.down, P.e_ke[b], 0));
-        HIP_TRY(ctx, hipMemcpyAsync(P.h_dns[b], P.d_dns[b], sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, P.down));
-        if (nodal) HIP_TRY(ctx, hipMemcpyAsync(P.h_nod[b], P.d_nod[b], sizeof(double) * (size_t)m * nb, hipMemcpyDeviceToHost, P.down));
-        if (status) HIP_TRY(ctx, hipMemcpyAsync(P.h_stat[b], P.d_stat[b], sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, P.down));
-        if (iters) HIP_TRY(ctx, hipMemcpyAsync(P.h_it[b], P.d_it[b], sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, P.down));
+        HIP_TRY(ctx, hipMemcpyAsync(P.buf[b].h_dns.get(), P.buf[b].d_dns.get(), sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, P.down));
+        if (nodal) HIP_TRY(ctx, hipMemcpyAsync(P.buf[b].h_nod.get(), P.buf[b].d_nod.get(), sizeof(double) * (size_t)m * nb, hipMemcpyDeviceToHost, P.down));
+        if (status) HIP_TRY(ctx, hipMemcpyAsync(P.buf[b].h_stat.get(), P.buf[b].d_stat.get(), sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, P.down));
+        if (iters) HIP_TRY(ctx, hipMemcpyAsync(P.buf[b].h_it.get(), P.buf[b].d_it.get(), sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost, P.down));
         HIP_TRY(ctx, hipEventRecord(P.e_down[b], P.down));
     }
     for (int64_t k = nchunk >= 2 ? nchunk - 2 : 0; k < nchunk; ++k) { rc = drain(k); if (rc) return rc; }
@@ -158,7 +146,7 @@ int nsq_accumulate_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int
             const int rc0 = screen_prepass_nsq(ctx, seed, first_index + (uint64_t)done, m, &ns, &ms_total);
             if (rc0) return rc0;
             certified = m - (int64_t)ns;
-            a.n = (int64_t)ns; a.memo_keys = ctx->screen.keys; a.memo_perm = ctx->screen.idx;
+            a.n = (int64_t)ns; a.memo_keys = ctx->screen.keys.get(); a.memo_perm = ctx->screen.idx.get();
         }
         int blocks = 0;
         relmc_acc part;
@@ -173,17 +161,17 @@ int nsq_accumulate_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int
             if (rc) return rc;
             // accumulators and the count of listed units come back in ONE synchronisation, through the context's pinned staging words (two more
             // blocking 4-byte copies per launch used to follow the kernel)
-            HIP_TRY(ctx, hipMemcpyAsync(&ctx->hstage->acc, ctx->dacc, sizeof(relmc_acc), hipMemcpyDeviceToHost, ctx->stream));
-            if (a.fail_count) HIP_TRY(ctx, hipMemcpyAsync(&ctx->hstage->fail_cnt, ctx->dfail_count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(&ctx->hstage.get()->acc, ctx->dacc.get(), sizeof(relmc_acc), hipMemcpyDeviceToHost, ctx->stream));
+            if (a.fail_count) HIP_TRY(ctx, hipMemcpyAsync(&ctx->hstage.get()->fail_cnt, ctx->retry.fail_count.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
             rc = finish_timing(ctx);
             if (rc) return rc;
             ms_total += ctx->last_kernel_ms;
-            part = ctx->hstage->acc;
+            part = ctx->hstage.get()->acc;
             // more non-converged units than the list holds (a case the calibration did not foresee): a longer list and the same chunk again --
             // the launch is a function of (seed, range) alone, so the second one lists them all
-            listed = a.fail_count ? ctx->hstage->fail_cnt : 0u;
-            if (a.fail_list == nullptr || listed <= ctx->fail_cap || ctx->fail_cap >= kFailCapMax || attempt >= 2) break;
-            HIP_TRY(ctx, hipMemset(ctx->dfail_count, 0, sizeof(uint32_t)));
+            listed = a.fail_count ? ctx->hstage.get()->fail_cnt : 0u;
+            if (a.fail_list == nullptr || listed <= ctx->retry.fail.size() || ctx->retry.fail.size() >= kFailCapMax || attempt >= 2) break;
+            HIP_TRY(ctx, hipMemset(ctx->retry.fail_count.get(), 0, sizeof(uint32_t)));
             rc = fail_list_ensure(ctx, listed + listed / 8 > kFailCapMax ? kFailCapMax : listed + listed / 8);
             if (rc) return rc;
         }
@@ -302,14 +290,8 @@ int32_t relmc_nsq_run(relmc_ctx* ctx, const relmc_nsq_opts* o, relmc_nsq_result*
         const int64_t R = nranks, r = ctx->comm_rank;
         const int64_t per = kStretch / o->batch * o->batch;
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        if (ctx->hist_cap < per) {
-            if (ctx->dhist) (void)hipFree(ctx->dhist);
-            if (ctx->hhist) (void)hipHostFree(ctx->hhist);
-            ctx->dhist = ctx->hhist = nullptr; ctx->hist_cap = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dhist, sizeof(double) * (size_t)per));
-            HIP_TRY(ctx, hipHostMalloc(&ctx->hhist, sizeof(double) * (size_t)per, hipHostMallocDefault));
-            ctx->hist_cap = per;
-        }
+        HIP_TRY(ctx, ctx->hist.d.grow((size_t)per));
+        HIP_TRY(ctx, ctx->hist.h.grow((size_t)per));
         constexpr int64_t NI = (int64_t)(offsetof(relmc_acc, sum_dns) / sizeof(int64_t)), ND = (int64_t)((sizeof(relmc_acc) - offsetof(relmc_acc, sum_dns)) / sizeof(double));
         std::vector<double> box;
         auto pack = [&](const relmc_acc& a, double* q) {
@@ -329,10 +311,10 @@ int32_t relmc_nsq_run(relmc_ctx* ctx, const relmc_nsq_opts* o, relmc_nsq_result*
             relmc_acc_zero(&part);
             int rc = RELMC_OK;
             if (cnt > 0) {
-                rc = nsq_accumulate_impl(ctx, o->seed, (uint64_t)lo, cnt, &o->solver, &part, trip ? ctx->dhist : nullptr);
+                rc = nsq_accumulate_impl(ctx, o->seed, (uint64_t)lo, cnt, &o->solver, &part, trip ? ctx->hist.d.get() : nullptr);
                 if (rc == RELMC_OK) kernel_ms += ctx->last_kernel_ms;
                 if (rc == RELMC_OK && trip) {
-                    if (hipMemcpyAsync(ctx->hhist, ctx->dhist, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                    if (hipMemcpyAsync(ctx->hist.h.get(), ctx->hist.d.get(), sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
                         hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, RELMC_ERR_HIP, "relmc_nsq_run: copy of the per-sample dns failed");
                 }
             }
@@ -340,7 +322,7 @@ int32_t relmc_nsq_run(relmc_ctx* ctx, const relmc_nsq_opts* o, relmc_nsq_result*
             box.assign((size_t)(3 * ncp + NI + ND), 0.0);
             if (rc == RELMC_OK) {
                 if (trip) for (int64_t i = 0; i < cnt; ++i) {
-                    const double v = ctx->hhist[(size_t)i];
+                    const double v = ctx->hist.h.get()[(size_t)i];
                     double* t = &box[(size_t)(3 * ((lo - lo0 + i) / o->batch))];
                     t[0] += v; t[1] = std::fma(v, v, t[1]); t[2] += v > 1e-4 /* nsqMain.m:270 */ ? 1.0 : 0.0;
                 }
@@ -449,15 +431,9 @@ int32_t relmc_nsq_run(relmc_ctx* ctx, const relmc_nsq_opts* o, relmc_nsq_result*
         const bool use_db = o->distinct_states == 2;
         const int64_t per = kStretch / o->batch * o->batch;       // buffer size = longest stretch
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        if (ctx->hist_cap < per) {
-            if (ctx->dhist) (void)hipFree(ctx->dhist);
-            if (ctx->hhist) (void)hipHostFree(ctx->hhist);
-            ctx->dhist = ctx->hhist = nullptr; ctx->hist_cap = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->dhist, sizeof(double) * (size_t)per));
-            HIP_TRY(ctx, hipHostMalloc(&ctx->hhist, sizeof(double) * (size_t)per, hipHostMallocDefault));
-            ctx->hist_cap = per;
-        }
-        const double* const hd = ctx->hhist;
+        HIP_TRY(ctx, ctx->hist.d.grow((size_t)per));
+        HIP_TRY(ctx, ctx->hist.h.grow((size_t)per));
+        const double* const hd = ctx->hist.h.get();
         while (beta > o->beta_limit && done < o->max_samples) {
             // How long a stretch?  beta falls like 1 / sqrt(n), so the run will need about done * (beta / limit)^2 samples: go to 90 % of that in
             // one stretch, then to 103 % of the (then better) prediction -- a stretch that is cut is taken again over its used part, so the last one
@@ -486,7 +462,7 @@ int32_t relmc_nsq_run(relmc_ctx* ctx, const relmc_nsq_opts* o, relmc_nsq_result*
             const int64_t m = (o->max_samples - done) < len ? (o->max_samples - done) : len;
             relmc_acc part;
             int rc;
-            const int64_t rows0 = ctx->db_n, samples0 = ctx->db_samples;
+            const int64_t rows0 = ctx->db.n, samples0 = ctx->db.samples;
             // what a stretch that is cut and taken again must not count twice: its second attempts, its kernel time
             const int64_t ru0 = ctx->retry_units, rc0_ = ctx->retry_converged, rd0 = ctx->retry_dense_units, rdc0 = ctx->retry_dense_converged, ro0 = ctx->retry_overflow;
             const double kernel_ms0 = kernel_ms;
@@ -496,14 +472,14 @@ int32_t relmc_nsq_run(relmc_ctx* ctx, const relmc_nsq_opts* o, relmc_nsq_result*
                 rc = relmc_nsq_db_batch(ctx, o->seed, (uint64_t)done, m, &o->solver, nullptr, nullptr);
                 if (rc) return rc;
                 kernel_ms += ctx->last_kernel_ms;
-                rc = db_sample_dns(ctx, o->seed, (uint64_t)done, m, ctx->dhist);
+                rc = db_sample_dns(ctx, o->seed, (uint64_t)done, m, ctx->hist.d.get());
                 if (rc) return rc;
             } else {
-                rc = nsq_accumulate_impl(ctx, o->seed, (uint64_t)done, m, &o->solver, &part, ctx->dhist);
+                rc = nsq_accumulate_impl(ctx, o->seed, (uint64_t)done, m, &o->solver, &part, ctx->hist.d.get());
                 if (rc) return rc;
                 kernel_ms += ctx->last_kernel_ms;
             }
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->hhist, ctx->dhist, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->hist.h.get(), ctx->hist.d.get(), sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             relmc_acc run = res->acc;                       // only n, n_fail, sum_dns, sum_dns2 are advanced per checkpoint
             int64_t used = 0;

@@ -323,6 +323,34 @@ int32_t relmc_hl1_load(relmc_ctx* ctx, int32_t ngen, const double* capacity_mw, 
 int32_t relmc_hl1_nsq(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t n, relmc_hl1_acc* acc,
                       double* iter_lole_host, double* iter_eue_host);
 
+/* ---- HL1 copper-sheet sequential MC (PowerSystemAdequacy.jl:214-268 run_sequential_mc) ------------------- */
+/* Two-state exponential units sampled at integer steps.  A chain of Y years has steps n = 1 .. Y*H (step n is hour (n-1) mod H of
+ * chain year (n-1) div H); the fleet state carries over from year to year.  With T_1 < T_2 < ... a unit's cumulative transition
+ * times, its state at step n is its start state toggled once for every T_j <= n.
+ * Draw e of unit k in chain c: U = (philox4x32_10(ctr = (c_lo, c_hi, k | 0x40000000, e >> 2), key = (seed_lo, seed_hi))[e & 3] + 0.5) / 2^32.
+ * Durations -mttf*ln U (UP) / -mttr*ln U (DOWN) in fp64, T_{j+1} = T_j + duration, product and sum each rounded (no FMA).
+ *   RELMC_HL1_START_ALL_UP:     every unit UP at time 0, draw 0 is the first time to failure (the reference, :223-224)
+ *   RELMC_HL1_START_STATIONARY: draw 0 decides the start state (DOWN iff U < mttr / (mttf + mttr)), durations from draw 1 on
+ * Per step: cap_avail = sum of the UP units' capacities in ascending unit order; loss iff cap_avail < load (strict), deficit
+ * load - cap_avail (:249-256).  Per year: loss hours, EUE, and loss events = steps where the loss flag rises (step 1 of the chain
+ * counts if it is a loss hour; an event that runs across a year boundary counts once, in the year it started). */
+#define RELMC_HL1_START_ALL_UP     0
+#define RELMC_HL1_START_STATIONARY 1
+typedef struct { double lole, eue, lolf; } relmc_hl1_seq_year;            /* loss hours, MWh, loss events of one simulated year */
+typedef struct {
+    int64_t years;                                                          /* simulated years summed */
+    double sum_lole, sum_eue, sum_lolf, sum_lole2, sum_eue2, sum_lolf2;
+} relmc_hl1_seq_acc;
+/* Fleet (ngen <= 128 units, mttf / mttr in hours, finite and > 0) and the hourly load curve of one year (nhours >= 1).  Held apart
+ * from relmc_hl1_load's model: neither call disturbs the other. */
+int32_t relmc_hl1_seq_load(relmc_ctx* ctx, int32_t ngen, const double* capacity_mw, const double* mttf_h, const double* mttr_h,
+                           int32_t nhours, const double* hourly_load_mw);
+/* chains [first_chain, first_chain + n_chains), each years_per_chain consecutive years; years_host: optional [n_chains * years_per_chain],
+ * chain-major.  Results depend on (seed, chain, start, years_per_chain, data) only, not on how a chain range is split into calls; the
+ * sums of `acc` are taken in a fixed order, so a repeated call is bitwise identical. */
+int32_t relmc_hl1_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain,
+                      int32_t start, relmc_hl1_seq_acc* acc, relmc_hl1_seq_year* years_host);
+
 /* ---- sequential HL2 (/root/reference/Montecarlo_seq/) ----------------- */
 /* relmc_seq_load          <- seqmeantime() [MTTF MTTR] (seqmeantime.m:21-36) + the hourly load factors of
  *                            anloducurve (anloducurve.m:24-88, seqMain.m:67)

@@ -448,6 +448,42 @@ function run_non_sequential_mc(eng::Engine, capacity::Vector{Float64}, for_rate:
     return (lole_hours_yr=acc.sum_lole / acc.n, eue_mwh_yr=acc.sum_eue / acc.n)
 end
 
+"relmc_hl1_seq_year / relmc_hl1_seq_acc (include/relmc.h)"
+struct Hl1SeqYear
+    lole::Cdouble; eue::Cdouble; lolf::Cdouble
+end
+mutable struct Hl1SeqAcc
+    years::Int64; sum_lole::Cdouble; sum_eue::Cdouble; sum_lolf::Cdouble; sum_lole2::Cdouble; sum_eue2::Cdouble; sum_lolf2::Cdouble
+    Hl1SeqAcc() = new()
+end
+const HL1_START = Dict(:all_up => Int32(0), :stationary => Int32(1))      # RELMC_HL1_START_*
+
+"""
+run_sequential_mc (PowerSystemAdequacy.jl:214-268): `chains` chronological chains of years ÷ chains consecutive years each on the GPU.
+The defaults are the reference's shape (one chain, every unit UP at the start); start=:stationary makes short parallel chains unbiased.
+Returns LOLE, EUE, LOLF (events per year), LOLD (hours per event) and the per-year indices in chain-major order.
+"""
+function run_sequential_mc(eng::Engine, capacity::Vector{Float64}, mttf::Vector{Float64}, mttr::Vector{Float64},
+                           hourly_load::Vector{Float64}, years::Integer; seed::Integer=1, chains::Integer=1, start::Symbol=:all_up)
+    (years >= 1 && chains >= 1 && years % chains == 0) || throw(ArgumentError("years must be a positive multiple of chains"))
+    check(ccall((:relmc_hl1_seq_load, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}),
+                eng.h, length(capacity), capacity, mttf, mttr, length(hourly_load), hourly_load), eng.h, "relmc_hl1_seq_load")
+    acc = Hl1SeqAcc(); yrs = Vector{Hl1SeqYear}(undef, years)
+    check(ccall((:relmc_hl1_seq, LIB), Int32, (Ptr{Cvoid}, UInt64, UInt64, Int64, Int32, Int32, Ref{Hl1SeqAcc}, Ptr{Hl1SeqYear}),
+                eng.h, seed, 0, chains, years ÷ chains, HL1_START[start], acc, yrs), eng.h, "relmc_hl1_seq")
+    lole = acc.sum_lole / years; lolf = acc.sum_lolf / years
+    year_lole = [y.lole for y in yrs]; cum = cumsum(year_lole)
+    return (lole_hours_yr=lole, eue_mwh_yr=acc.sum_eue / years, lolf_occ_yr=lolf, lold_hours=lolf > 0 ? lole / lolf : NaN,
+            year_lole=year_lole, year_eue=[y.eue for y in yrs], year_lolf=[y.lolf for y in yrs],
+            convergence_history=[cum[k] / k for k in 10:10:years])                  # :263-265
+end
+
+# Layout of the HL1 sequential structs, kept apart from LAYOUT (tests/test_hl1_seq_host.py compares it with the C compiler's)
+const LAYOUT_HL1_SEQ = [
+    ("relmc_hl1_seq_year", 24, [("lole", 0), ("eue", 8), ("lolf", 16)]),
+    ("relmc_hl1_seq_acc", 56, [("years", 0), ("sum_lole", 8), ("sum_eue", 16), ("sum_lolf", 24), ("sum_lole2", 32), ("sum_eue2", 40), ("sum_lolf2", 48)]),
+]
+
 # Layout table of the plain-C structs this file mirrors: tests/test_c_abi.py compiles a C program printing sizeof / offsetof of
 # include/relmc.h's structs and compares with these numbers and with the ctypes mirror, so drift in either mirror is caught
 # without a Julia installation.  (name, sizeof, [(field, offset) ...])

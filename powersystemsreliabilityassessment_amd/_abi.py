@@ -119,6 +119,18 @@ class SeqYear(C.Structure):
     _fields_ = [("ens", C.c_double), ("dlc", C.c_double), ("nlc", C.c_double), ("n_contingency", C.c_int64)]
 
 
+class Hl1SeqYear(C.Structure):            # relmc_hl1_seq_year
+    _fields_ = [("lole", C.c_double), ("eue", C.c_double), ("lolf", C.c_double)]
+
+
+class Hl1SeqAcc(C.Structure):             # relmc_hl1_seq_acc
+    _fields_ = [("years", C.c_int64), ("sum_lole", C.c_double), ("sum_eue", C.c_double), ("sum_lolf", C.c_double),
+                ("sum_lole2", C.c_double), ("sum_eue2", C.c_double), ("sum_lolf2", C.c_double)]
+
+
+HL1_START_ALL_UP, HL1_START_STATIONARY = 0, 1     # RELMC_HL1_START_*
+
+
 class SeqOpts(C.Structure):
     _fields_ = [
         ("cov_threshold", C.c_double), ("max_years", C.c_int32), ("batch_years", C.c_int32), ("seed", C.c_uint64),

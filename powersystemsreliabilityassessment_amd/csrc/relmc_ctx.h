@@ -160,6 +160,9 @@ struct relmc_ctx {
     // HL1 copper-sheet model; lole / eue / part: relmc_hl1_nsq's device buffers, grow-only
     bool has_hl1 = false; int hl1_hours = 0;
     struct Hl1 { DevBuf<relmc::Hl1Case> dcase; DevBuf<double> sorted, suffix, lole, eue, part; } hl1;
+    // HL1 sequential chronology (relmc_hl1_seq): its own fleet / load curve, grow-only per-year records and reduction partials
+    bool has_hl1_seq = false;
+    struct Hl1Seq { int ngen = 0, nhours = 0; DevBuf<relmc::Hl1SeqCase> dcase; DevBuf<double> load, years, part; } hl1_seq;
     // zero-curtailment pre-screen (relmc_screen.hip): certificate tables of the case (device pointers inside tab), grow-only work buffers of a pre-pass
     struct Screen {
         relmc::ScreenTab tab = {};

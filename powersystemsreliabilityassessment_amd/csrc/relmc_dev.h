@@ -206,5 +206,13 @@ struct Hl1Case {
     double cap[NCOMPMAX];
 };
 
+// HL1 sequential chronology (relmc_hl1_seq): the fleet's rates and the stationary start thresholds, mirrored by include/relmc.h's contract
+struct Hl1SeqCase {
+    int32_t ngen, nhours;
+    double cap[NCOMPMAX], mttf[NCOMPMAX], mttr[NCOMPMAX];
+    double q[NCOMPMAX];              // mttr / (mttf + mttr): RELMC_HL1_START_STATIONARY starts unit k DOWN iff draw 0 < q[k]
+};
+constexpr int HL1_SEQ_WINDOW = 512;  // hours per LDS window of relmc_hl1_seq_kernel (a wavefront's masks: WINDOW x 4 x u32 = 8 KB)
+
 
 }  // namespace relmc

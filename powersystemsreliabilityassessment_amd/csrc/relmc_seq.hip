@@ -1,5 +1,5 @@
 // relmc_seq.hip — the sequential (chronological) HL2 track of /root/reference/Montecarlo_seq/ (seq_mcsampling.m, seq_mcsimulation.m, calnlc.m,
-// seqMain.m:85-249) and the HL1 copper-sheet model of GeneratingAdequacy/PowerSystemAdequacy.jl:169-208.
+// seqMain.m:85-249) and the HL1 copper-sheet models of GeneratingAdequacy/PowerSystemAdequacy.jl:169-208 (non-sequential) and :214-268 (sequential).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -353,6 +353,79 @@ int32_t relmc_hl1_nsq(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64
     if (rc) return rc;
     acc->n = n;
     for (int64_t b = 0; b < blocks; ++b) { acc->sum_lole += part[4 * b]; acc->sum_eue += part[4 * b + 1]; acc->sum_lole2 += part[4 * b + 2]; acc->sum_eue2 += part[4 * b + 3]; }
+    return RELMC_OK;
+}
+
+// ---- HL1 sequential chronology: PowerSystemAdequacy.jl:214-268 ----------------------------------------------------------------
+int32_t relmc_hl1_seq_load(relmc_ctx* ctx, int32_t ngen, const double* capacity_mw, const double* mttf_h, const double* mttr_h,
+                           int32_t nhours, const double* hourly_load_mw)
+{
+    if (!ctx) return RELMC_ERR_INVALID;
+    if (!capacity_mw || !mttf_h || !mttr_h || !hourly_load_mw || ngen < 1 || nhours < 1)
+        return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_load: bad arguments");
+    if (ngen > NCOMPMAX) return fail(ctx, RELMC_ERR_UNSUPPORTED, "relmc_hl1_seq_load: more than 128 units");
+    Hl1SeqCase h; std::memset(&h, 0, sizeof(h));
+    h.ngen = ngen; h.nhours = nhours;
+    for (int g = 0; g < ngen; ++g) {
+        if (!(std::isfinite(mttf_h[g]) && mttf_h[g] > 0.0 && std::isfinite(mttr_h[g]) && mttr_h[g] > 0.0))
+            return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_load: MTTF / MTTR of unit " + std::to_string(g) + " not finite and positive");
+        h.cap[g] = capacity_mw[g]; h.mttf[g] = mttf_h[g]; h.mttr[g] = mttr_h[g];
+        h.q[g] = mttr_h[g] / (mttf_h[g] + mttr_h[g]);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto& S = ctx->hl1_seq;
+    ctx->has_hl1_seq = false;
+    HIP_TRY(ctx, S.dcase.grow(1));
+    HIP_TRY(ctx, S.load.grow((size_t)nhours));
+    HIP_TRY(ctx, hipMemcpy(S.dcase.get(), &h, sizeof(h), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(S.load.get(), hourly_load_mw, sizeof(double) * nhours, hipMemcpyHostToDevice));
+    S.ngen = ngen; S.nhours = nhours; ctx->has_hl1_seq = true;
+    return RELMC_OK;
+}
+
+int32_t relmc_hl1_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain, int32_t start,
+                      relmc_hl1_seq_acc* acc, relmc_hl1_seq_year* years_host)
+{
+    if (!ctx) return RELMC_ERR_INVALID;
+    if (!ctx->has_hl1_seq) return fail(ctx, RELMC_ERR_NO_CASE, "relmc_hl1_seq: relmc_hl1_seq_load has not been called");
+    if (!acc || n_chains < 0 || years_per_chain < 1 || (start != RELMC_HL1_START_ALL_UP && start != RELMC_HL1_START_STATIONARY))
+        return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq: bad arguments");
+    std::memset(acc, 0, sizeof(*acc));
+    if (n_chains == 0) return RELMC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto& S = ctx->hl1_seq;
+    // chains go in launches of at most ~4M year records (96 MB); a chain's records never depend on the launch it is in
+    const int64_t max_rec = (int64_t)1 << 22;
+    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_chains, max_rec / years_per_chain));
+    const int64_t rec_max = per * years_per_chain;
+    const int64_t rblocks_max = std::min<int64_t>(1024, (rec_max + 255) / 256);
+    HIP_TRY(ctx, S.years.grow((size_t)rec_max * 3));
+    HIP_TRY(ctx, S.part.grow((size_t)rblocks_max * 6));
+    std::vector<double> part;
+    double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double kernel_ms = 0.0;
+    for (int64_t c0 = 0; c0 < n_chains; c0 += per) {
+        const int64_t nc = std::min(per, n_chains - c0), nrec = nc * years_per_chain;
+        const int64_t rblocks = std::min<int64_t>(1024, (nrec + 255) / 256);
+        (void)hipEventRecord(ctx->ev0, ctx->stream);
+        hipLaunchKernelGGL(relmc_hl1_seq_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
+                           first_chain + (uint64_t)c0, nc, years_per_chain, start, S.years.get());
+        hipLaunchKernelGGL(relmc_hl1_seq_reduce_kernel, dim3((unsigned)rblocks), dim3(256), 0, ctx->stream, S.years.get(), nrec, S.part.get());
+        (void)hipEventRecord(ctx->ev1, ctx->stream);
+        if (hipGetLastError() != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_seq: launch failed");
+        part.resize((size_t)rblocks * 6);
+        HIP_TRY(ctx, hipMemcpyAsync(part.data(), S.part.get(), sizeof(double) * 6 * rblocks, hipMemcpyDeviceToHost, ctx->stream));
+        if (years_host)
+            HIP_TRY(ctx, hipMemcpyAsync(years_host + c0 * years_per_chain, S.years.get(), sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
+        if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_seq: synchronisation failed");
+        kernel_ms += ctx->last_kernel_ms;
+        for (int64_t b = 0; b < rblocks; ++b)
+            for (int j = 0; j < 6; ++j) sum[j] += part[(size_t)b * 6 + j];
+    }
+    ctx->last_kernel_ms = kernel_ms;
+    acc->years = n_chains * years_per_chain;
+    acc->sum_lole = sum[0]; acc->sum_eue = sum[1]; acc->sum_lolf = sum[2];
+    acc->sum_lole2 = sum[3]; acc->sum_eue2 = sum[4]; acc->sum_lolf2 = sum[5];
     return RELMC_OK;
 }
 

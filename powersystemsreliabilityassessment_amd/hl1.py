@@ -5,6 +5,9 @@ Mirror of the reference's Julia module GeneratingAdequacy/PowerSystemAdequacy.jl
   run_analytical(gens, load; step_size)       (:113-163)  exact COPT convolution, host arithmetic (numpy)
   run_non_sequential_mc(gens, load, iterations)(:169-208)  Monte Carlo, evaluated by the HIP library
                                                             (relmc_hl1_load / relmc_hl1_nsq)
+  run_sequential_mc(gens, load, years)         (:214-268)  chronological Monte Carlo on the GPU, with loss-of-load
+                                                            frequency (relmc_hl1_seq_load / relmc_hl1_seq)
+  compare_results(results)                     (:275-290)  the comparison table (text; no plot)
 `rts24_generators()` / `rts24_load()` give the IEEE RTS-79 fleet and the 8736-hour reference load
 curve (Montecarlo_seq/anloducurve.m) whose exact answers are the published LOLE 9.3941 h/yr and
 EUE 1176.29 MWh/yr.
@@ -49,6 +52,17 @@ class ReliabilityResult:              # :47-53
     eue_mwh_yr: float
     computation_time: float
     convergence_history: np.ndarray = field(default_factory=lambda: np.zeros(0))
+
+
+@dataclass
+class SequentialReliabilityResult(ReliabilityResult):
+    """run_sequential_mc's result: the reference's fields plus frequency / duration and the per-year indices (global year order,
+    chain-major: the years of chain 0, then chain 1, ...)."""
+    lolf_occ_yr: float = 0.0          # loss-of-load events per year
+    lold_hours: float = float("nan")  # hours per event, LOLE / LOLF (NaN without an event)
+    year_lole: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    year_eue: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    year_lolf: np.ndarray = field(default_factory=lambda: np.zeros(0))
 
 
 def rts24_generators() -> list:
@@ -134,6 +148,56 @@ def run_non_sequential_mc(gens, load: LoadModel, iterations: int, *, seed: int =
     k = np.arange(100, iterations + 1, 100)
     history = np.cumsum(it_lole)[k - 1] / k if k.size else np.zeros(0)
     return ReliabilityResult("Non-Sequential MC", acc.sum_lole / iterations, acc.sum_eue / iterations, time.time() - t0, history)
+
+
+_SEQ_START = {"all_up": _abi.HL1_START_ALL_UP, "stationary": _abi.HL1_START_STATIONARY}
+
+
+def run_sequential_mc(gens, load: LoadModel, years: int, *, seed: int = 1, chains: int = 1, start: str = "all_up",
+                      engine=None) -> SequentialReliabilityResult:
+    """PowerSystemAdequacy.jl:214-268 on the GPU: `chains` independent chronological chains of years // chains consecutive years each
+    (the fleet state carries over from year to year inside a chain).  The defaults are the reference's shape: one chain, every unit UP
+    at the start.  start="stationary" draws each unit's start state from its stationary distribution, so that short chains run in
+    parallel are unbiased.  convergence_history = running LOLE every 10 years (:263-265)."""
+    from . import api
+    years, chains = int(years), int(chains)
+    if years < 1 or chains < 1 or years % chains:
+        raise ValueError(f"run_sequential_mc: years ({years}) must be a positive multiple of chains ({chains})")
+    if start not in _SEQ_START:
+        raise ValueError(f"run_sequential_mc: start must be one of {sorted(_SEQ_START)}, not {start!r}")
+    eng = engine or api.default_engine()
+    L = eng.L
+    t0 = time.time()
+    cap = np.ascontiguousarray([g.capacity for g in gens], dtype=np.float64)
+    mttf = np.ascontiguousarray([g.mttf for g in gens], dtype=np.float64)
+    mttr = np.ascontiguousarray([g.mttr for g in gens], dtype=np.float64)
+    hl = np.ascontiguousarray(load.hourly_load, dtype=np.float64)
+    key = (cap.tobytes(), mttf.tobytes(), mttr.tobytes(), hl.tobytes())
+    if getattr(eng, "_hl1_seq_loaded", None) != key:       # fleet and load curve stay on the device between calls on the same model
+        eng._check(L.relmc_hl1_seq_load(eng._h, cap.size, cap.ctypes.data_as(_abi.c_double_p), mttf.ctypes.data_as(_abi.c_double_p),
+                                        mttr.ctypes.data_as(_abi.c_double_p), hl.size, hl.ctypes.data_as(_abi.c_double_p)),
+                   "relmc_hl1_seq_load")
+        eng._hl1_seq_loaded = key
+    acc = _abi.Hl1SeqAcc()
+    yr = np.zeros((years, 3))
+    eng._check(L.relmc_hl1_seq(eng._h, int(seed), 0, chains, years // chains, _SEQ_START[start], C.byref(acc),
+                               yr.ctypes.data_as(C.POINTER(_abi.Hl1SeqYear))), "relmc_hl1_seq")
+    k = np.arange(10, years + 1, 10)
+    history = np.cumsum(yr[:, 0])[k - 1] / k if k.size else np.zeros(0)
+    lole, eue, lolf = acc.sum_lole / years, acc.sum_eue / years, acc.sum_lolf / years
+    return SequentialReliabilityResult("Sequential MC", lole, eue, time.time() - t0, history, lolf_occ_yr=lolf,
+                                       lold_hours=lole / lolf if lolf > 0 else float("nan"),
+                                       year_lole=yr[:, 0].copy(), year_eue=yr[:, 1].copy(), year_lolf=yr[:, 2].copy())
+
+
+def compare_results(results) -> str:
+    """The method comparison table of :275-290 (the reference prints it and plots the convergence histories; plots are out of scope)."""
+    rule = "=" * 42
+    lines = [rule, "       METHOD COMPARISON SUMMARY", rule,
+             "%-20s | %-10s | %-10s | %-10s" % ("Method", "LOLE(h/yr)", "EUE(MWh)", "Time(s)"), "-" * 60]
+    lines += ["%-20s | %-10.4f | %-10.2f | %-10.4f" % (r.method, r.lole_hours_yr, r.eue_mwh_yr, r.computation_time) for r in results]
+    lines.append("-" * 60)
+    return "\n".join(lines) + "\n"
 
 
 class Hl1Acc(C.Structure):

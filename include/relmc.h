@@ -351,6 +351,33 @@ int32_t relmc_hl1_seq_load(relmc_ctx* ctx, int32_t ngen, const double* capacity_
 int32_t relmc_hl1_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain,
                       int32_t start, relmc_hl1_seq_acc* acc, relmc_hl1_seq_year* years_host);
 
+/* ---- HL1 planning model: maintenance, energy-limited units, LFU (generating_adequancy_comparative.jl:15-120, tail_risk.jl:12-91) ---- */
+/* Year y is the global index first_year + i; hour h is 0-based; every year starts with every ELU's energy at 0; years are independent.
+ * Block b of hour h of year y: philox4x32_10(ctr = (y_lo, y_hi, 0x20000000 | h, b), key = (seed_lo, seed_hi)); word j = word j & 3 of
+ * block j >> 2 (the 0x20000000 tag keeps these draws apart from the 0x40000000 / 0x80000000 chronologies and the non-sequential draws).
+ *   LFU:   U_i = (word_i + 0.5) / 2^32 (i = 0, 1), z = sqrt(-2 ln U_1) * cos(2 pi U_2), load = load_h + z * sigma (product and sum each
+ *          rounded, no FMA)
+ *   units: unit k is in maintenance in week w = h / 168 + 1 iff start_k >= 1 and start_k <= w < start_k + weeks_k (start 0 = none);
+ *          unit k is down iff word 2 + k < thr_k, thr_k = floor(for_rate_k * 2^32) clamped to [0, 2^32 - 1] (as relmc_hl1_load)
+ *   hour:  in ascending unit order, skip units in maintenance or down; an ELU (finite limit) whose energy >= limit is exhausted and
+ *          skipped, any other ELU adds its capacity to cap_elu; a non-ELU unit adds to cap_unl.  unserved = max(0, load - cap_unl).
+ *          unserved > cap_elu: deficit = unserved - cap_elu, every available ELU's energy += its capacity;
+ *          else unserved > 0: every available ELU's energy += unserved * (cap_i / cap_elu).
+ *   year:  loss hours (deficit > 0), EUE (sum of deficits, hour order), loss events (rising edges of the loss flag, hour 0 counts).
+ * Results depend only on (seed, year index, data), never on how a year range is split into calls; a repeated call is bitwise identical. */
+#define RELMC_HL1_PLAN_MAX_ELU 8
+/* Fleet (ngen <= 128 units, at most 8 of them with a finite energy_limit_mwh; INFINITY = not energy-limited), maintenance windows in
+ * weeks (1-based start, 0 = none) and the hourly load curve of one year (1 <= nhours < 2^29), lfu_sigma_mw >= 0.  Held apart from the
+ * relmc_hl1_load and relmc_hl1_seq_load models: none of the three calls disturbs the others. */
+int32_t relmc_hl1_plan_load(relmc_ctx* ctx, int32_t ngen, const double* capacity_mw, const double* for_rate,
+                            const int32_t* outage_start_week, const int32_t* outage_weeks, const double* energy_limit_mwh,
+                            int32_t nhours, const double* hourly_load_mw, double lfu_sigma_mw);
+/* years [first_year, first_year + n_years).  acc: sums over the years (lolf = loss events).  years_host: optional [n_years] (loss hours,
+ * EUE, loss events).  hour_loss_count_host: optional [nhours], overwritten with this call's number of loss years per hour.
+ * elu_energy_host: optional [n_years][n_elu], MWh used per ELU per year (ELUs in unit order). */
+int32_t relmc_hl1_plan(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int64_t n_years, relmc_hl1_seq_acc* acc,
+                       relmc_hl1_seq_year* years_host, int64_t* hour_loss_count_host, double* elu_energy_host);
+
 /* ---- sequential HL2 (/root/reference/Montecarlo_seq/) ----------------- */
 /* relmc_seq_load          <- seqmeantime() [MTTF MTTR] (seqmeantime.m:21-36) + the hourly load factors of
  *                            anloducurve (anloducurve.m:24-88, seqMain.m:67)

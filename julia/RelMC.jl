@@ -484,6 +484,39 @@ const LAYOUT_HL1_SEQ = [
     ("relmc_hl1_seq_acc", 56, [("years", 0), ("sum_lole", 8), ("sum_eue", 16), ("sum_lolf", 24), ("sum_lole2", 32), ("sum_eue2", 40), ("sum_lolf2", 48)]),
 ]
 
+"""
+run_monte_carlo_simulation (generating_adequancy_comparative.jl:15-120, tail_risk.jl:12-91): the HL1 planning model's Monte Carlo on the
+GPU.  `outage_start` are 1-based maintenance start weeks (0 = none), `energy_limit` MWh per year (Inf = not energy-limited, at most 8
+ELUs), `lfu_sigma_mw` the LFU standard deviation.  Returns LOLE, EUE, LOLF, the per-year indices, the hourly loss probability and the
+MWh used per ELU per year (n_years x n_elu).
+"""
+function run_planning_mc(eng::Engine, capacity::Vector{Float64}, for_rate::Vector{Float64}, outage_start::Vector{Int32},
+                         outage_weeks::Vector{Int32}, energy_limit::Vector{Float64}, hourly_load::Vector{Float64}, lfu_sigma_mw::Float64,
+                         n_years::Integer; seed::Integer=1)
+    n_years >= 1 || throw(ArgumentError("n_years must be positive"))
+    check(ccall((:relmc_hl1_plan_load, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble},
+                                                     Int32, Ptr{Cdouble}, Cdouble),
+                eng.h, length(capacity), capacity, for_rate, outage_start, outage_weeks, energy_limit, length(hourly_load), hourly_load,
+                lfu_sigma_mw), eng.h, "relmc_hl1_plan_load")
+    n_elu = count(isfinite, energy_limit)
+    acc = Hl1SeqAcc(); yrs = Vector{Hl1SeqYear}(undef, n_years); hours = zeros(Int64, length(hourly_load))
+    elu = zeros(Float64, n_elu, n_years)                                   # column-major: column y = the C record [y][n_elu]
+    check(ccall((:relmc_hl1_plan, LIB), Int32, (Ptr{Cvoid}, UInt64, UInt64, Int64, Ref{Hl1SeqAcc}, Ptr{Hl1SeqYear}, Ptr{Int64}, Ptr{Cdouble}),
+                eng.h, seed, 0, n_years, acc, yrs, hours, n_elu > 0 ? elu : C_NULL), eng.h, "relmc_hl1_plan")
+    year_lole = [y.lole for y in yrs]; cum = cumsum(year_lole)
+    return (lole_hours_yr=acc.sum_lole / n_years, eue_mwh_yr=acc.sum_eue / n_years, lolf_occ_yr=acc.sum_lolf / n_years,
+            year_lole=year_lole, year_eue=[y.eue for y in yrs], year_lolf=[y.lolf for y in yrs],
+            hourly_loss_prob=hours ./ n_years, elu_energy=permutedims(elu),
+            lole_history=[cum[k] / k for k in 100:100:n_years])                 # comparative.jl:114-116
+end
+
+# Structs the HL1 planning wrappers pass (the planning calls reuse the sequential model's records; no struct of their own), checked
+# against the C compiler by tests/test_hl1_plan_host.py
+const LAYOUT_HL1_PLAN = [
+    ("relmc_hl1_seq_year", 24, [("lole", 0), ("eue", 8), ("lolf", 16)]),
+    ("relmc_hl1_seq_acc", 56, [("years", 0), ("sum_lole", 8), ("sum_eue", 16), ("sum_lolf", 24), ("sum_lole2", 32), ("sum_eue2", 40), ("sum_lolf2", 48)]),
+]
+
 # Layout table of the plain-C structs this file mirrors: tests/test_c_abi.py compiles a C program printing sizeof / offsetof of
 # include/relmc.h's structs and compares with these numbers and with the ctypes mirror, so drift in either mirror is caught
 # without a Julia installation.  (name, sizeof, [(field, offset) ...])

@@ -163,6 +163,10 @@ struct relmc_ctx {
     // HL1 sequential chronology (relmc_hl1_seq): its own fleet / load curve, grow-only per-year records and reduction partials
     bool has_hl1_seq = false;
     struct Hl1Seq { int ngen = 0, nhours = 0; DevBuf<relmc::Hl1SeqCase> dcase; DevBuf<double> load, years, part; } hl1_seq;
+    // HL1 planning model (relmc_hl1_plan): its own fleet / maintenance / ELUs / load curve, grow-only per-year records, ELU energies,
+    // hour loss counts and reduction partials
+    bool has_hl1_plan = false;
+    struct Hl1Plan { int nhours = 0, n_elu = 0; DevBuf<relmc::PlanCase> dcase; DevBuf<double> load, years, elu, part; DevBuf<unsigned long long> hours; } hl1_plan;
     // zero-curtailment pre-screen (relmc_screen.hip): certificate tables of the case (device pointers inside tab), grow-only work buffers of a pre-pass
     struct Screen {
         relmc::ScreenTab tab = {};

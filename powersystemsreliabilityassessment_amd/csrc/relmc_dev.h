@@ -214,5 +214,25 @@ struct Hl1SeqCase {
 };
 constexpr int HL1_SEQ_WINDOW = 512;  // hours per LDS window of relmc_hl1_seq_kernel (a wavefront's masks: WINDOW x 4 x u32 = 8 KB)
 
+// HL1 planning model (relmc_hl1_plan): maintenance windows, ELU slots and Bernoulli thresholds, mirrored by include/relmc.h's contract
+constexpr int PLAN_MAX_ELU = 8;
+constexpr uint32_t PLAN_TAG = 0x20000000u;
+
+// one unit, 32 bytes: a single scalar load per unit and hour
+struct __attribute__((aligned(32))) PlanUnit {
+    double cap;
+    uint32_t thr;                    // down iff its word < thr
+    int32_t slot;                    // ELU slot 0..7 (unit order), -1 = not energy-limited
+    int32_t mlo, mhi;                // in maintenance at hour h iff mlo <= h < mhi (0-based hours, clipped to the year; mlo = mhi = 0: none)
+    int32_t pad[2];
+};
+
+struct PlanCase {
+    int32_t ngen, nhours, n_elu, nblk;   // nblk = Philox blocks per hour = (ngen + 5) / 4 (words 0, 1: LFU normal; word 2 + k: unit k)
+    double sigma;                        // LFU standard deviation, MW
+    double elu_cap[PLAN_MAX_ELU], elu_lim[PLAN_MAX_ELU];   // unused slots: capacity 0, limit +inf
+    PlanUnit unit[NCOMPMAX];
+};
+
 
 }  // namespace relmc

@@ -79,7 +79,13 @@ def rts24_load(hours: int = 8736) -> LoadModel:
 def add_unit_convolution(probs: np.ndarray, unit: Generator, step_size: float) -> np.ndarray:
     """COPT recursion with capacity rounding split between neighbouring steps (:67-111).
     `probs[k]` = P(outage = k*step_size)."""
-    Cc, q = unit.capacity, unit.for_rate
+    return convolve_unit(probs, unit.capacity, unit.for_rate, step_size)
+
+
+def convolve_unit(probs: np.ndarray, capacity: float, q: float, step_size: float) -> np.ndarray:
+    """add_unit_convolution for a unit of `capacity` MW that is out with probability `q` (the planning model passes its effective q,
+    generating_adequacy_comprehensive.jl:34-70)."""
+    Cc = capacity
     p = 1.0 - q
     max_old = (probs.size - 1) * step_size if probs.size else 0.0
     n_new = int(np.ceil((max_old + Cc) / step_size)) + 1

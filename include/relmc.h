@@ -351,6 +351,43 @@ int32_t relmc_hl1_seq_load(relmc_ctx* ctx, int32_t ngen, const double* capacity_
 int32_t relmc_hl1_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain,
                       int32_t start, relmc_hl1_seq_acc* acc, relmc_hl1_seq_year* years_host);
 
+/* ---- HL1 multi-area chronology with tie-line transfers (AdequacyAssessmentII.jl:73-250 solve_curtailment_fast / run_fast_sequential_simulation) ---- */
+/* The chronology is relmc_hl1_seq's, word for word: draws (seed, chain, k | 0x40000000, event) with k the GLOBAL unit index (units stored
+ * area-major: area 0's units, then area 1's, ...), the same start rules, steps n = 1 .. Y*H with the state carried across years, no FMA.
+ * A one-area run without ties therefore has relmc_hl1_seq's chronology, and ISOLATED / INTERCONNECTED runs of one seed see the same fleet.
+ * Per step (every area shares nhours H, 0-based areas):
+ *   m_i = cap_i - load_i[h], cap_i = sum of area i's UP units' capacities in ascending unit order.
+ *   T[i][j] = T[j][i] = sum of the capacities of the ties between i and j (parallel ties summed; ties never fail).
+ *   every m_i >= 0: nothing is curtailed.  ISOLATED: no transfer.
+ *   INTERCONNECTED, RELMC_HL1_AREA_FLOW_REFERENCE (:105-167): R = T; loop { s = lowest i with m_i > 1e-4, t = lowest i with m_i < -1e-4,
+ *     stop if either is missing; BFS from s (FIFO queue [s], s marked; pop u, u == t: path found; else for v = 0..n-1 ascending, if
+ *     R[u][v] > 1e-4 and v unmarked: parent[v] = u, mark v, push v); no path: STOP the whole loop (the reference's break);
+ *     f = min(m_s, -m_t), then f = min(f, R[parent[v]][v]) along the path; m_s -= f; m_t += f; R[p][v] -= f, R[v][p] += f on the path }.
+ *   INTERCONNECTED, RELMC_HL1_AREA_FLOW_MAX_FLOW: the same BFS from each source s (m_s > 1e-4) in ascending order, ending at the first
+ *     popped area u with m_u < -1e-4 (the sink); augment as above and restart from the lowest source; stop when no source reaches a
+ *     deficit: a maximum flow of the super-source / super-sink graph, so the total curtailment is the least possible.
+ *   Both rules stop after at most 4096 augmentations per step (a guard; not reached on 8 areas).
+ *   c_i = -m_i if m_i < 0 else 0; area i has a loss hour iff c_i > 0; the system has one iff any c_i > 0, its deficit sum c_i in area order.
+ * Per year, for each area and for the system: loss hours, EUE and loss events (rising edges of the flag along the chain, step 1 counts,
+ * an event counts in the year it starts), as relmc_hl1_seq. */
+#define RELMC_AREA_MAX 8
+#define RELMC_HL1_AREA_ISOLATED        0
+#define RELMC_HL1_AREA_INTERCONNECTED  1
+#define RELMC_HL1_AREA_FLOW_REFERENCE  0
+#define RELMC_HL1_AREA_FLOW_MAX_FLOW   1
+/* n_areas <= RELMC_AREA_MAX areas of units_per_area[i] >= 1 units each (<= 128 units in total; capacity_mw / mttf_h / mttr_h area-major,
+ * mttf / mttr finite and > 0), hourly_load_mw [n_areas][nhours], n_ties >= 0 ties (0-based endpoints in range, from != to, capacity
+ * finite and >= 0).  Held apart from the relmc_hl1_load / relmc_hl1_seq_load / relmc_hl1_plan_load models: no call disturbs another. */
+int32_t relmc_hl1_area_load(relmc_ctx* ctx, int32_t n_areas, const int32_t* units_per_area, const double* capacity_mw,
+                            const double* mttf_h, const double* mttr_h, int32_t nhours, const double* hourly_load_mw,
+                            int32_t n_ties, const int32_t* tie_from, const int32_t* tie_to, const double* tie_capacity_mw);
+/* chains [first_chain, first_chain + n_chains) of years_per_chain years; policy RELMC_HL1_AREA_*, flow RELMC_HL1_AREA_FLOW_* (read under
+ * INTERCONNECTED only, but always checked).  acc: [n_areas + 1], row n_areas = the system.  years_host: optional
+ * [n_chains * years_per_chain][n_areas + 1], chain-major.  Results depend on (seed, chain, start, years_per_chain, policy, flow, data)
+ * only, not on how a chain range is split into calls; sums are taken in a fixed order, so a repeated call is bitwise identical. */
+int32_t relmc_hl1_area(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain, int32_t start,
+                       int32_t policy, int32_t flow, relmc_hl1_seq_acc* acc, relmc_hl1_seq_year* years_host);
+
 /* ---- HL1 planning model: maintenance, energy-limited units, LFU (generating_adequancy_comparative.jl:15-120, tail_risk.jl:12-91) ---- */
 /* Year y is the global index first_year + i; hour h is 0-based; every year starts with every ELU's energy at 0; years are independent.
  * Block b of hour h of year y: philox4x32_10(ctr = (y_lo, y_hi, 0x20000000 | h, b), key = (seed_lo, seed_hi)); word j = word j & 3 of

@@ -510,6 +510,41 @@ function run_planning_mc(eng::Engine, capacity::Vector{Float64}, for_rate::Vecto
             lole_history=[cum[k] / k for k in 100:100:n_years])                 # comparative.jl:114-116
 end
 
+const AREA_MAX = 8                                                            # RELMC_AREA_MAX
+const HL1_AREA_POLICY = Dict(:isolated => Int32(0), :interconnected => Int32(1))   # RELMC_HL1_AREA_ISOLATED / _INTERCONNECTED
+const HL1_AREA_FLOW = Dict(:reference => Int32(0), :max_flow => Int32(1))         # RELMC_HL1_AREA_FLOW_*
+
+"""
+run_fast_sequential_simulation (AdequacyAssessmentII.jl:185-250): the multi-area chronology on the GPU.  `units_per_area` counts the
+units of each area; `capacity`, `mttf`, `mttr` are area-major; `hourly_load` is n_areas x nhours; ties are 1-based (from, to, capacity)
+as the reference's TieLine.  policy :isolated or :interconnected, flow :reference (the reference's loop) or :max_flow.  Returns per-area
+LOLE, EUE, LOLF, the system row (a loss hour in any area) and the per-year indices (years x (n_areas + 1) x 3, chain-major).
+"""
+function run_fast_sequential_simulation(eng::Engine, units_per_area::Vector{Int32}, capacity::Vector{Float64}, mttf::Vector{Float64},
+                                        mttr::Vector{Float64}, hourly_load::Matrix{Float64}, tie_from::Vector{Int32}, tie_to::Vector{Int32},
+                                        tie_capacity::Vector{Float64}, policy::Symbol, n_years::Integer; seed::Integer=1, chains::Integer=1,
+                                        start::Symbol=:all_up, flow::Symbol=:reference)
+    (n_years >= 1 && chains >= 1 && n_years % chains == 0) || throw(ArgumentError("n_years must be a positive multiple of chains"))
+    n = length(units_per_area)
+    (1 <= n <= AREA_MAX && size(hourly_load, 1) == n) || throw(ArgumentError("1..$AREA_MAX areas, one load row per area"))
+    load = Matrix(permutedims(hourly_load))                                  # column-major n x H -> the C layout [n_areas][nhours]
+    check(ccall((:relmc_hl1_area_load, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32,
+                                                     Ptr{Cdouble}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}),
+                eng.h, n, units_per_area, capacity, mttf, mttr, size(hourly_load, 2), load, length(tie_from), tie_from .- Int32(1),
+                tie_to .- Int32(1), tie_capacity), eng.h, "relmc_hl1_area_load")
+    acc = zeros(Float64, 7, n + 1)           # relmc_hl1_seq_acc[n + 1]: column r = one 56-byte record (row 1 holds the Int64 count)
+    yrs = Vector{Hl1SeqYear}(undef, n_years * (n + 1))
+    check(ccall((:relmc_hl1_area, LIB), Int32, (Ptr{Cvoid}, UInt64, UInt64, Int64, Int32, Int32, Int32, Int32, Ptr{Cdouble},
+                                                Ptr{Hl1SeqYear}),
+                eng.h, seed, 0, chains, n_years ÷ chains, HL1_START[start], HL1_AREA_POLICY[policy], HL1_AREA_FLOW[flow], acc, yrs),
+          eng.h, "relmc_hl1_area")
+    sums = permutedims(acc[2:4, :])                                          # [row, (sum_lole, sum_eue, sum_lolf)]
+    y = reshape(yrs, n + 1, n_years)
+    return (lole=sums[1:n, 1] ./ n_years, eue=sums[1:n, 2] ./ n_years, lolf=sums[1:n, 3] ./ n_years,
+            system_lole=sums[n + 1, 1] / n_years, system_eue=sums[n + 1, 2] / n_years, system_lolf=sums[n + 1, 3] / n_years,
+            year_indices=[getfield(y[r, t], f) for t in 1:n_years, r in 1:n + 1, f in (:lole, :eue, :lolf)])
+end
+
 # Structs the HL1 planning wrappers pass (the planning calls reuse the sequential model's records; no struct of their own), checked
 # against the C compiler by tests/test_hl1_plan_host.py
 const LAYOUT_HL1_PLAN = [

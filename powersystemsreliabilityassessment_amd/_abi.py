@@ -129,6 +129,9 @@ class Hl1SeqAcc(C.Structure):             # relmc_hl1_seq_acc
 
 
 HL1_START_ALL_UP, HL1_START_STATIONARY = 0, 1     # RELMC_HL1_START_*
+AREA_MAX = 8                                       # RELMC_AREA_MAX
+HL1_AREA_ISOLATED, HL1_AREA_INTERCONNECTED = 0, 1  # RELMC_HL1_AREA_*
+HL1_AREA_FLOW_REFERENCE, HL1_AREA_FLOW_MAX_FLOW = 0, 1   # RELMC_HL1_AREA_FLOW_*
 
 
 class SeqOpts(C.Structure):

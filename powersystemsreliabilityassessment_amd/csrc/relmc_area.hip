@@ -1,0 +1,129 @@
+// relmc_area.hip — the HL1 multi-area chronology with tie-line transfers (GeneratingAdequacy/AdequacyAssessmentII.jl:73-250; contract in
+// include/relmc.h).  The per-row year records are summed by relmc_hl1_seq_reduce_kernel (relmc_seq.hip), one row slice at a time.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "relmc_ctx.h"
+#include "relmc_area_kernels.h"
+
+using namespace relmc_host;
+
+static_assert(relmc::AREA_MAX == RELMC_AREA_MAX, "relmc_dev.h and include/relmc.h disagree on the area limit");
+
+extern "C" {
+
+int32_t relmc_hl1_area_load(relmc_ctx* ctx, int32_t n_areas, const int32_t* units_per_area, const double* capacity_mw,
+                            const double* mttf_h, const double* mttr_h, int32_t nhours, const double* hourly_load_mw,
+                            int32_t n_ties, const int32_t* tie_from, const int32_t* tie_to, const double* tie_capacity_mw)
+{
+    if (!ctx) return RELMC_ERR_INVALID;
+    if (!units_per_area || !capacity_mw || !mttf_h || !mttr_h || !hourly_load_mw || n_areas < 1 || nhours < 1 || n_ties < 0 ||
+        (n_ties > 0 && (!tie_from || !tie_to || !tie_capacity_mw)))
+        return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_load: bad arguments");
+    if (n_areas > RELMC_AREA_MAX) return fail(ctx, RELMC_ERR_UNSUPPORTED, "relmc_hl1_area_load: more than 8 areas");
+    relmc::AreaCase A; std::memset(&A, 0, sizeof(A));
+    int64_t ngen = 0;
+    for (int a = 0; a < n_areas; ++a) {
+        if (units_per_area[a] < 1) return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_load: area " + std::to_string(a) + " has no unit");
+        A.lo[a] = (int32_t)std::min<int64_t>(ngen, NCOMPMAX);
+        ngen += units_per_area[a];
+    }
+    if (ngen > NCOMPMAX) return fail(ctx, RELMC_ERR_UNSUPPORTED, "relmc_hl1_area_load: more than 128 units");
+    A.lo[n_areas] = (int32_t)ngen;
+    A.ngen = (int32_t)ngen; A.nhours = nhours; A.n_areas = n_areas;
+    for (int g = 0; g < ngen; ++g) {
+        if (!(std::isfinite(mttf_h[g]) && mttf_h[g] > 0.0 && std::isfinite(mttr_h[g]) && mttr_h[g] > 0.0))
+            return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_load: MTTF / MTTR of unit " + std::to_string(g) + " not finite and positive");
+        A.cap[g] = capacity_mw[g]; A.mttf[g] = mttf_h[g]; A.mttr[g] = mttr_h[g];
+        A.q[g] = mttr_h[g] / (mttf_h[g] + mttr_h[g]);
+    }
+    for (int l = 0; l < n_ties; ++l) {
+        const int i = tie_from[l], j = tie_to[l];
+        if (i < 0 || i >= n_areas || j < 0 || j >= n_areas || i == j)
+            return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_load: tie " + std::to_string(l) + " has a bad endpoint");
+        if (!(std::isfinite(tie_capacity_mw[l]) && tie_capacity_mw[l] >= 0.0))
+            return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_load: capacity of tie " + std::to_string(l) + " not finite and >= 0");
+        A.tie[i * n_areas + j] += tie_capacity_mw[l];              // System(areas, lines), :50-59: parallel ties summed in tie order
+        A.tie[j * n_areas + i] += tie_capacity_mw[l];
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto& S = ctx->hl1_area;
+    ctx->has_hl1_area = false;
+    HIP_TRY(ctx, S.dcase.grow(1));
+    HIP_TRY(ctx, S.load.grow((size_t)n_areas * nhours));
+    HIP_TRY(ctx, hipMemcpy(S.dcase.get(), &A, sizeof(A), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(S.load.get(), hourly_load_mw, sizeof(double) * n_areas * nhours, hipMemcpyHostToDevice));
+    S.ngen = (int)ngen; S.nhours = nhours; S.n_areas = n_areas; ctx->has_hl1_area = true;
+    return RELMC_OK;
+}
+
+int32_t relmc_hl1_area(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain, int32_t start,
+                       int32_t policy, int32_t flow, relmc_hl1_seq_acc* acc, relmc_hl1_seq_year* years_host)
+{
+    if (!ctx) return RELMC_ERR_INVALID;
+    if (!ctx->has_hl1_area) return fail(ctx, RELMC_ERR_NO_CASE, "relmc_hl1_area: relmc_hl1_area_load has not been called");
+    if (!acc || n_chains < 0 || years_per_chain < 1 || (start != RELMC_HL1_START_ALL_UP && start != RELMC_HL1_START_STATIONARY) ||
+        (policy != RELMC_HL1_AREA_ISOLATED && policy != RELMC_HL1_AREA_INTERCONNECTED) ||
+        (flow != RELMC_HL1_AREA_FLOW_REFERENCE && flow != RELMC_HL1_AREA_FLOW_MAX_FLOW))
+        return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area: bad arguments");
+    auto& S = ctx->hl1_area;
+    const int rows = S.n_areas + 1;
+    std::memset(acc, 0, sizeof(*acc) * rows);
+    if (n_chains == 0) return RELMC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // chains go in launches of at most ~4M year records x rows (records [row][chain * years + year][3], rows one slice apart); a chain's
+    // records never depend on the launch it is in
+    const int64_t max_rec = (int64_t)1 << 22;
+    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_chains, max_rec / years_per_chain));
+    const int64_t rec_max = per * years_per_chain;
+    const int64_t rblocks_max = std::min<int64_t>(1024, (rec_max + 255) / 256);
+    HIP_TRY(ctx, S.years.grow((size_t)rec_max * 3 * rows));
+    HIP_TRY(ctx, S.part.grow((size_t)rblocks_max * 6 * rows));
+    const bool inter = policy == RELMC_HL1_AREA_INTERCONNECTED;
+    const int nw = (S.ngen + 31) >> 5;
+    const size_t lds = sizeof(double) * 64 * (2 * S.n_areas + 1 + (inter ? S.n_areas * S.n_areas : 0)) + sizeof(uint32_t) * nw * relmc::HL1_SEQ_WINDOW;
+    std::vector<double> part, stage;
+    std::vector<double> sum((size_t)rows * 6, 0.0);
+    double kernel_ms = 0.0;
+    for (int64_t c0 = 0; c0 < n_chains; c0 += per) {
+        const int64_t nc = std::min(per, n_chains - c0), nrec = nc * years_per_chain;
+        const int64_t rblocks = std::min<int64_t>(1024, (nrec + 255) / 256);
+        (void)hipEventRecord(ctx->ev0, ctx->stream);
+        hipLaunchKernelGGL(relmc::relmc_hl1_area_kernel, dim3((unsigned)nc), dim3(64), lds, ctx->stream, S.dcase.get(), S.load.get(), seed,
+                           first_chain + (uint64_t)c0, years_per_chain, start, policy, flow, nrec, S.years.get());
+        for (int r = 0; r < rows; ++r)
+            if (launch_hl1_seq_reduce(ctx, S.years.get() + (size_t)r * nrec * 3, nrec, S.part.get() + (size_t)r * rblocks * 6, rblocks) != RELMC_OK)
+                return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_area: launch failed");
+        (void)hipEventRecord(ctx->ev1, ctx->stream);
+        part.resize((size_t)rblocks * 6 * rows);
+        HIP_TRY(ctx, hipMemcpyAsync(part.data(), S.part.get(), sizeof(double) * part.size(), hipMemcpyDeviceToHost, ctx->stream));
+        if (years_host) {
+            stage.resize((size_t)nrec * 3 * rows);
+            HIP_TRY(ctx, hipMemcpyAsync(stage.data(), S.years.get(), sizeof(double) * stage.size(), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_area: synchronisation failed");
+        kernel_ms += ctx->last_kernel_ms;
+        for (int r = 0; r < rows; ++r)
+            for (int64_t b = 0; b < rblocks; ++b)
+                for (int j = 0; j < 6; ++j) sum[(size_t)r * 6 + j] += part[((size_t)r * rblocks + b) * 6 + j];
+        if (years_host)                                            // [row][record] -> [record][row]
+            for (int64_t i = 0; i < nrec; ++i)
+                for (int r = 0; r < rows; ++r) {
+                    relmc_hl1_seq_year& o = years_host[(size_t)(c0 * years_per_chain + i) * rows + r];
+                    const double* s = stage.data() + ((size_t)r * nrec + i) * 3;
+                    o.lole = s[0]; o.eue = s[1]; o.lolf = s[2];
+                }
+    }
+    ctx->last_kernel_ms = kernel_ms;
+    for (int r = 0; r < rows; ++r) {
+        const double* s = sum.data() + (size_t)r * 6;
+        acc[r].years = n_chains * years_per_chain;
+        acc[r].sum_lole = s[0]; acc[r].sum_eue = s[1]; acc[r].sum_lolf = s[2];
+        acc[r].sum_lole2 = s[3]; acc[r].sum_eue2 = s[4]; acc[r].sum_lolf2 = s[5];
+    }
+    return RELMC_OK;
+}
+
+}  // extern "C"

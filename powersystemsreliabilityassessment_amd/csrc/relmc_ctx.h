@@ -10,6 +10,7 @@
 //   relmc_database.hip   the reference's dedupe and persistent unique-state database on the device
 //   relmc_comm.hip       the path's single collective: RCCL (bound at run time) or a host-supplied all-reduce, with a wall-clock guard
 //   relmc_seq.hip        sequential track (chronology, scaled-load hours, annual indices, the seqMain loop) and the HL1 copper sheet
+//   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area); its rows are summed by relmc_seq.hip's reduction
 //   relmc_screen.hip     the zero-curtailment pre-screen (relmc_solver_opts.screen): certificate tables, pre-pass kernels, worklists
 //   relmc_debug.hip      introspection and test hooks that are not part of include/relmc.h
 #pragma once
@@ -167,6 +168,9 @@ struct relmc_ctx {
     // hour loss counts and reduction partials
     bool has_hl1_plan = false;
     struct Hl1Plan { int nhours = 0, n_elu = 0; DevBuf<relmc::PlanCase> dcase; DevBuf<double> load, years, elu, part; DevBuf<unsigned long long> hours; } hl1_plan;
+    // HL1 multi-area chronology (relmc_hl1_area): its own areas / ties / load curves, grow-only per-row year records and reduction partials
+    bool has_hl1_area = false;
+    struct Hl1Area { int ngen = 0, nhours = 0, n_areas = 0; DevBuf<relmc::AreaCase> dcase; DevBuf<double> load, years, part; } hl1_area;
     // zero-curtailment pre-screen (relmc_screen.hip): certificate tables of the case (device pointers inside tab), grow-only work buffers of a pre-pass
     struct Screen {
         relmc::ScreenTab tab = {};
@@ -242,6 +246,10 @@ void acc_add_unit(relmc_acc* acc, const FailRec& rec, double dns, int32_t meta, 
 int pipe_run(relmc_ctx* ctx, const uint8_t* states, const double* load_scale, int64_t n, const relmc_solver_opts& o, double fail_threshold,
              double* dns, double* nodal, int32_t* status, int32_t* iters);
 int nsq_accumulate_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t n, const relmc_solver_opts* opts, relmc_acc* acc_out, double* dns_dev);
+
+// ---- relmc_seq.hip ------------------------------------------------------------------------------------------------------------
+// relmc_hl1_seq_reduce_kernel over n records (lole, eue, lolf) into partial[blocks][6], on the context's stream (relmc_hl1_area sums its rows with it)
+int launch_hl1_seq_reduce(relmc_ctx* ctx, const double* rec, int64_t n, double* partial, int64_t blocks);
 
 // ---- relmc_database.hip -------------------------------------------------------------------------------------------------------
 int db_accumulate(relmc_ctx* ctx, relmc_acc* acc_out);

@@ -234,5 +234,17 @@ struct PlanCase {
     PlanUnit unit[NCOMPMAX];
 };
 
+// HL1 multi-area chronology (relmc_hl1_area): the relmc_hl1_seq fleet stored area-major, each area's unit range and the tie topology,
+// mirrored by include/relmc.h's contract (AREA_MAX = RELMC_AREA_MAX)
+constexpr int AREA_MAX = 8;
+constexpr int AREA_MAX_AUG = 4096;   // augmenting paths per step at most (a guard: Edmonds-Karp on 8 areas needs far fewer)
+struct AreaCase {
+    int32_t ngen, nhours, n_areas, pad;
+    int32_t lo[AREA_MAX + 1];        // area a owns units [lo[a], lo[a + 1]); lo[n_areas] = ngen
+    double cap[NCOMPMAX], mttf[NCOMPMAX], mttr[NCOMPMAX];
+    double q[NCOMPMAX];              // mttr / (mttf + mttr), as Hl1SeqCase
+    double tie[AREA_MAX * AREA_MAX]; // T[i][j] at i * n_areas + j: summed tie capacities, symmetric, zero diagonal
+};
+
 
 }  // namespace relmc

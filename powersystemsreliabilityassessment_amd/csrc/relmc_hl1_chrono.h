@@ -1,0 +1,26 @@
+// relmc_hl1_chrono.h — device-only helpers of the HL1 chronology contract (include/relmc.h), shared by relmc_hl1_seq_kernel
+// (relmc_seq_kernels.h) and relmc_hl1_area_kernel (relmc_area_kernels.h).  Inline functions only: no kernel is defined here, so every
+// unit may include it.
+#pragma once
+#include "relmc_devfn.h"
+
+namespace relmc {
+
+// U of draw e of unit k in chain c (the 0x40000000 tag keeps the stream apart from the HL2 chronology and the HL1 non-sequential draws)
+DEVFI double hl1_seq_u(uint64_t chain, int k, int e, uint64_t seed)
+{
+    uint32_t w[4];
+    philox4x32_10((uint32_t)chain, (uint32_t)(chain >> 32), (uint32_t)k | 0x40000000u, (uint32_t)e >> 2, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+    const uint32_t x = (e & 2) ? ((e & 1) ? w[3] : w[2]) : ((e & 1) ? w[1] : w[0]);      // selects, not a dynamic index into w (scratch)
+    return ((double)x + 0.5) * 2.3283064365386963e-10;
+}
+
+// Orders one lane's LDS accesses against the other lanes' of the same wavefront (no workgroup barrier: the four waves run four chains)
+DEVFI void hl1_seq_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+}  // namespace relmc

@@ -29,6 +29,13 @@ int seq_sample(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int n_years, 
 }
 }  // namespace
 
+int launch_hl1_seq_reduce(relmc_ctx* ctx, const double* rec, int64_t n, double* partial, int64_t blocks)
+{
+    hipLaunchKernelGGL(relmc_hl1_seq_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, rec, n, partial);
+    if (hipGetLastError() != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "hl1_seq_reduce: launch failed");
+    return RELMC_OK;
+}
+
 }  // namespace relmc_host
 
 using namespace relmc_host;

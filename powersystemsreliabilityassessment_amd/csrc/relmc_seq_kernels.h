@@ -2,6 +2,7 @@
 // and of the HL1 copper-sheet models (GeneratingAdequacy/PowerSystemAdequacy.jl:169-208 non-sequential, :214-268 sequential).
 #pragma once
 #include "relmc_devfn.h"
+#include "relmc_hl1_chrono.h"
 
 namespace relmc {
 
@@ -159,15 +160,6 @@ __global__ void __launch_bounds__(256) relmc_hl1_kernel(const Hl1Case* __restric
 }
 
 // ---- HL1 sequential chronology (PowerSystemAdequacy.jl:214-268; contract in include/relmc.h): one wavefront per chain --------------
-// U of draw e of unit k in chain c (the 0x40000000 tag keeps the stream apart from the HL2 chronology and the HL1 non-sequential draws)
-DEVFI double hl1_seq_u(uint64_t chain, int k, int e, uint64_t seed)
-{
-    uint32_t w[4];
-    philox4x32_10((uint32_t)chain, (uint32_t)(chain >> 32), (uint32_t)k | 0x40000000u, (uint32_t)e >> 2, (uint32_t)seed, (uint32_t)(seed >> 32), w);
-    const uint32_t x = (e & 2) ? ((e & 1) ? w[3] : w[2]) : ((e & 1) ? w[1] : w[0]);      // selects, not a dynamic index into w (scratch)
-    return ((double)x + 0.5) * 2.3283064365386963e-10;
-}
-
 // The wave's open year: fixed-order butterfly over the lanes' partials, lane 0 stores (lole, eue, lolf); the partials restart at zero
 DEVFI void hl1_seq_close_year(double& l, double& e, double& f, double* __restrict__ out)
 {
@@ -175,14 +167,6 @@ DEVFI void hl1_seq_close_year(double& l, double& e, double& f, double* __restric
     for (int off = 32; off > 0; off >>= 1) { l += __shfl_xor(l, off); e += __shfl_xor(e, off); f += __shfl_xor(f, off); }
     if ((threadIdx.x & 63) == 0) { out[0] = l; out[1] = e; out[2] = f; }
     l = e = f = 0.0;
-}
-
-// Orders one lane's LDS accesses against the other lanes' of the same wavefront (no workgroup barrier: the four waves run four chains)
-DEVFI void hl1_seq_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // Chain c = blockIdx.x * 4 + wave.  Lane l owns units l and l + 64; its cursor (state, next transition time, next draw) stays in

@@ -1,0 +1,269 @@
+"""HL1 multi-area generating adequacy with tie-line transfers — GeneratingAdequacy/AdequacyAssessmentII.jl on the GPU.
+
+Mirror of the reference's module AdequacyAssessmentFast:
+  TieLine / Area / System (.topology_matrix)        (:28-59)   1-based areas, as the reference
+  ISOLATED / INTERCONNECTED                          (:61)
+  solve_curtailment_fast(sys, margins, policy, flow) (:73-179)  host port (numpy), no GPU needed; flow="max_flow" is the full
+                                                                solver the reference's comment at :136-146 leaves out
+  run_fast_sequential_simulation(sys, policy, n_years)(:185-250) the chronological Monte Carlo on the GPU (relmc_hl1_area_load /
+                                                                relmc_hl1_area), with per-area and system LOLF / LOLD
+  comparison_report(res_iso, res_int)                (:280-291)  the demo's final table (text)
+`demo_system()` is the system of `run_demo` (:256-277); `rts96_system()` the three-area IEEE RTS-96 as three RTS-24 fleets joined by
+the summed tie capacities of `case96.TIES`.  The units are `hl1.Generator`s; the chronology and its draws are those of
+`hl1.run_sequential_mc` (include/relmc.h), so both policies under one seed see the same fleet history.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import enum
+import time
+from dataclasses import dataclass, field
+from typing import NamedTuple
+
+import numpy as np
+
+from . import _abi, case96, hl1
+
+
+@dataclass
+class TieLine:                        # :28-32 (1-based areas)
+    from_area: int
+    to_area: int
+    capacity: float
+
+
+@dataclass
+class Area:                           # :34-39
+    id: int
+    name: str
+    generators: list
+    hourly_load: np.ndarray
+
+
+class SupportPolicy(enum.IntEnum):    # :61 (values = RELMC_HL1_AREA_*)
+    ISOLATED = _abi.HL1_AREA_ISOLATED
+    INTERCONNECTED = _abi.HL1_AREA_INTERCONNECTED
+
+
+ISOLATED, INTERCONNECTED = SupportPolicy.ISOLATED, SupportPolicy.INTERCONNECTED
+_FLOW = {"reference": _abi.HL1_AREA_FLOW_REFERENCE, "max_flow": _abi.HL1_AREA_FLOW_MAX_FLOW}
+_EPS = 1e-4                           # the reference's surplus / deficit / residual threshold (:107-108, :129)
+_MAX_AUG = 4096                       # augmentations per step at most (include/relmc.h; a guard)
+
+
+class System:                         # :41-59
+    """Areas and tie lines; topology_matrix[i, j] = summed capacity of the ties between areas i + 1 and j + 1 (both directions)."""
+
+    def __init__(self, areas, tie_lines):
+        self.areas = list(areas)
+        self.tie_lines = list(tie_lines)
+        n = len(self.areas)
+        mat = np.zeros((n, n))
+        for line in self.tie_lines:
+            i, j = int(line.from_area) - 1, int(line.to_area) - 1
+            if not (0 <= i < n and 0 <= j < n) or i == j:
+                raise ValueError(f"System: tie line {line} must join two different areas among 1..{n}")
+            mat[i, j] += line.capacity
+            mat[j, i] += line.capacity
+        self.topology_matrix = mat
+
+
+class AreaResult(NamedTuple):         # the reference's (area = ..., lole = ..., eue = ...) of :243-247
+    area: str
+    lole: float
+    eue: float
+
+
+@dataclass
+class MultiAreaResult:
+    """run_fast_sequential_simulation's result: `results` is the reference's list of (area, lole, eue); per-area LOLF (events per year)
+    and LOLD (hours per event); the system row (a loss hour in any area); per-year indices year_indices[year, row, (loss hours, EUE,
+    loss events)], rows = areas then the system, years in chain-major order."""
+    policy: SupportPolicy
+    flow: str
+    results: list
+    lolf: np.ndarray
+    lold: np.ndarray
+    system_lole: float
+    system_eue: float
+    system_lolf: float
+    system_lold: float
+    computation_time: float
+    year_indices: np.ndarray = field(default_factory=lambda: np.zeros((0, 0, 3)))
+
+
+def _augment(m, R, flow: str):
+    """The INTERCONNECTED loop of :105-167 (flow "reference") or the max-flow variant, in place on margins m and residuals R (0-based)."""
+    n = len(m)
+
+    def bfs(s, t):                    # t >= 0: path to t; t < 0: to the first popped area in deficit
+        parent, marked, queue, head = [0] * n, [False] * n, [s], 0
+        marked[s] = True
+        while head < len(queue):
+            u = queue[head]
+            head += 1
+            if (u == t) if t >= 0 else (m[u] < -_EPS):
+                return u, parent
+            for v in range(n):
+                if R[u][v] > _EPS and not marked[v]:
+                    parent[v] = u
+                    marked[v] = True
+                    queue.append(v)
+        return -1, parent
+
+    for _ in range(_MAX_AUG):
+        if flow == "reference":
+            s = next((i for i in range(n) if m[i] > _EPS), -1)
+            t = next((i for i in range(n) if m[i] < -_EPS), -1)
+            if s < 0 or t < 0:
+                return
+            found, parent = bfs(s, t)
+            if found < 0:
+                return                # the reference's break: no other pair is tried
+        else:
+            t = -1
+            for s in range(n):
+                if m[s] > _EPS:
+                    t, parent = bfs(s, -1)
+                    if t >= 0:
+                        break
+            if t < 0:
+                return
+        f = min(m[s], -m[t])
+        v = t
+        while v != s:
+            f = min(f, R[parent[v]][v])
+            v = parent[v]
+        m[s] -= f
+        m[t] += f
+        v = t
+        while v != s:
+            p = parent[v]
+            R[p][v] -= f
+            R[v][p] += f
+            v = p
+
+
+def solve_curtailment_fast(sys: System, margins, policy, flow: str = "reference") -> np.ndarray:
+    """Curtailment per area for one hour's margins (capacity - load per area, :73-179).  ISOLATED: the negative margins.
+    INTERCONNECTED, flow="reference": the reference's augmenting-path loop, which stops at the first surplus area that cannot reach the
+    first deficit area.  flow="max_flow": every surplus area is tried, so the total curtailment is the least the ties allow."""
+    if flow not in _FLOW:
+        raise ValueError(f"solve_curtailment_fast: flow must be one of {sorted(_FLOW)}, not {flow!r}")
+    m = [float(x) for x in np.asarray(margins, dtype=np.float64).ravel()]
+    if len(m) != len(sys.areas):
+        raise ValueError(f"solve_curtailment_fast: {len(m)} margins for {len(sys.areas)} areas")
+    if all(x >= 0 for x in m):
+        return np.zeros(len(m))
+    if SupportPolicy(policy) == INTERCONNECTED:
+        _augment(m, sys.topology_matrix.tolist(), flow)
+    return np.array([-x if x < 0 else 0.0 for x in m])
+
+
+_START = {"all_up": _abi.HL1_START_ALL_UP, "stationary": _abi.HL1_START_STATIONARY}
+
+
+def _flatten(sys: System):
+    """Validated device arrays: units area-major, loads [n_areas][nhours], 0-based ties."""
+    n = len(sys.areas)
+    if not 1 <= n <= _abi.AREA_MAX:
+        raise ValueError(f"run_fast_sequential_simulation: {n} areas; 1..{_abi.AREA_MAX} are supported")
+    units = np.array([len(a.generators) for a in sys.areas], dtype=np.int32)
+    if units.min() < 1 or units.sum() > 128:
+        raise ValueError("run_fast_sequential_simulation: every area needs a unit, and 128 units at most in total")
+    gens = [g for a in sys.areas for g in a.generators]
+    cap, mttf, mttr = (np.ascontiguousarray([getattr(g, f) for g in gens], dtype=np.float64) for f in ("capacity", "mttf", "mttr"))
+    if not (np.all(np.isfinite(mttf)) and np.all(mttf > 0) and np.all(np.isfinite(mttr)) and np.all(mttr > 0)):
+        raise ValueError("run_fast_sequential_simulation: MTTF and MTTR must be finite and positive")
+    H = {np.asarray(a.hourly_load).size for a in sys.areas}
+    if len(H) != 1 or H == {0}:
+        raise ValueError("run_fast_sequential_simulation: every area needs the same non-empty number of hours")
+    load = np.ascontiguousarray(np.stack([np.asarray(a.hourly_load, dtype=np.float64) for a in sys.areas]))
+    tf = np.ascontiguousarray([int(t.from_area) - 1 for t in sys.tie_lines], dtype=np.int32)
+    tt = np.ascontiguousarray([int(t.to_area) - 1 for t in sys.tie_lines], dtype=np.int32)
+    tc = np.ascontiguousarray([t.capacity for t in sys.tie_lines], dtype=np.float64)
+    if tf.size and (min(tf.min(), tt.min()) < 0 or max(tf.max(), tt.max()) >= n or np.any(tf == tt)):
+        raise ValueError("run_fast_sequential_simulation: a tie line must join two different areas among 1..n")
+    if not (np.all(np.isfinite(tc)) and np.all(tc >= 0)):
+        raise ValueError("run_fast_sequential_simulation: tie capacities must be finite and >= 0")
+    return units, cap, mttf, mttr, load, tf, tt, tc
+
+
+def run_fast_sequential_simulation(sys: System, policy, n_years: int, *, seed: int = 1, chains: int = 1, start: str = "all_up",
+                                   flow: str = "reference", engine=None) -> MultiAreaResult:
+    """AdequacyAssessmentII.jl:185-250 on the GPU: `chains` chronological chains of n_years // chains years each; every step takes each
+    area's margin and, under INTERCONNECTED, the tie-limited transfer solve (`flow` as in solve_curtailment_fast).  The defaults are the
+    reference's shape (one chain, every unit UP at the start).  Runs of both policies under one seed see the same fleet history, so
+    their difference is the interconnection benefit without sampling noise between them."""
+    from . import api
+    n_years, chains = int(n_years), int(chains)
+    if n_years < 1 or chains < 1 or n_years % chains:
+        raise ValueError(f"run_fast_sequential_simulation: n_years ({n_years}) must be a positive multiple of chains ({chains})")
+    if start not in _START:
+        raise ValueError(f"run_fast_sequential_simulation: start must be one of {sorted(_START)}, not {start!r}")
+    if flow not in _FLOW:
+        raise ValueError(f"run_fast_sequential_simulation: flow must be one of {sorted(_FLOW)}, not {flow!r}")
+    if policy not in (ISOLATED, INTERCONNECTED):
+        raise ValueError(f"run_fast_sequential_simulation: policy must be ISOLATED or INTERCONNECTED, not {policy!r}")
+    policy = SupportPolicy(policy)
+    units, cap, mttf, mttr, load, tf, tt, tc = _flatten(sys)
+    eng = engine or api.default_engine()
+    L = eng.L
+    t0 = time.time()
+    n = units.size
+    dp, ip = _abi.c_double_p, _abi.c_int32_p
+    key = tuple(a.tobytes() for a in (units, cap, mttf, mttr, load, tf, tt, tc))
+    if getattr(eng, "_hl1_area_loaded", None) != key:       # areas, ties and loads stay on the device between calls on the same system
+        eng._check(L.relmc_hl1_area_load(eng._h, n, units.ctypes.data_as(ip), cap.ctypes.data_as(dp), mttf.ctypes.data_as(dp),
+                                         mttr.ctypes.data_as(dp), load.shape[1], load.ctypes.data_as(dp), tf.size,
+                                         tf.ctypes.data_as(ip), tt.ctypes.data_as(ip), tc.ctypes.data_as(dp)), "relmc_hl1_area_load")
+        eng._hl1_area_loaded = key
+    acc = (_abi.Hl1SeqAcc * (n + 1))()
+    yr = np.zeros((n_years, n + 1, 3))
+    eng._check(L.relmc_hl1_area(eng._h, int(seed), 0, chains, n_years // chains, _START[start], int(policy), _FLOW[flow], acc,
+                                yr.ctypes.data_as(C.POINTER(_abi.Hl1SeqYear))), "relmc_hl1_area")
+    lole = np.array([a.sum_lole for a in acc]) / n_years
+    eue = np.array([a.sum_eue for a in acc]) / n_years
+    lolf = np.array([a.sum_lolf for a in acc]) / n_years
+    with np.errstate(invalid="ignore", divide="ignore"):
+        lold = np.where(lolf > 0, lole / np.where(lolf > 0, lolf, 1.0), np.nan)
+    return MultiAreaResult(policy, flow, [AreaResult(a.name, float(lole[i]), float(eue[i])) for i, a in enumerate(sys.areas)],
+                           lolf[:n].copy(), lold[:n].copy(), float(lole[n]), float(eue[n]), float(lolf[n]), float(lold[n]),
+                           time.time() - t0, yr)
+
+
+def comparison_report(res_iso: MultiAreaResult, res_int: MultiAreaResult) -> str:
+    """The final table of run_demo (:280-291)."""
+    rule = "-" * 60
+    lines = ["", "=== FINAL COMPARISON (FAST METHOD) ===", "Policy          | Area       | LOLE (h/yr) | EUE (MWh/yr)", rule]
+    lines += ["ISOLATED        | %-10s | %10.2f  | %10.2f" % (r.area, r.lole, r.eue) for r in res_iso.results]
+    lines.append(rule)
+    lines += ["INTERCONNECTED  | %-10s | %10.2f  | %10.2f" % (r.area, r.lole, r.eue) for r in res_int.results]
+    return "\n".join(lines) + "\n"
+
+
+# ---- data ---------------------------------------------------------------------------------------------------------------------
+def demo_system(hours: int = 8760) -> System:
+    """run_demo's system (:259-269): Area_Rich 5 x 400 MW (MTTF 1000 h, MTTR 50 h), Area_Poor 5 x 200 MW (900 h, 60 h), one 200 MW tie;
+    loads c + a sin(linspace(0, 2 pi, hours)) (the last bits may differ from Julia's range)."""
+    x = np.sin(np.linspace(0.0, 2.0 * np.pi, hours))
+    rich = Area(1, "Area_Rich", [hl1.Generator(i, 400.0, 1000.0, 50.0) for i in range(1, 6)], 1000.0 + 500.0 * x)
+    poor = Area(2, "Area_Poor", [hl1.Generator(i, 200.0, 900.0, 60.0) for i in range(1, 6)], 800.0 + 400.0 * x)
+    return System([rich, poor], [TieLine(1, 2, 200.0)])
+
+
+def rts96_ties() -> list:
+    """case96.TIES summed per area pair (bus number // 100 = area; bus 325 is in area 3): A-B 1175 MW, A-C 500 MW, B-C 500 MW.  The
+    323-325 transformer lies inside area C and is dropped."""
+    tot = {}
+    for fb, tb, *_rest in case96.TIES:
+        i, j = sorted((fb // 100, tb // 100))
+        if i != j:
+            tot[(i, j)] = tot.get((i, j), 0.0) + _rest[1]
+    return [TieLine(i, j, c) for (i, j), c in sorted(tot.items())]
+
+
+def rts96_system() -> System:
+    """The three-area IEEE RTS-96: three RTS-24 fleets (32 units each) with the RTS-24 load curve each, joined by rts96_ties()."""
+    areas = [Area(k + 1, name, hl1.rts24_generators(), hl1.rts24_load().hourly_load) for k, name in enumerate(("A", "B", "C"))]
+    return System(areas, rts96_ties())

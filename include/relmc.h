@@ -310,7 +310,12 @@ void relmc_nsq_indices(const relmc_acc* acc, int32_t nb, int32_t ncomp, double h
 /* Mirrors GeneratingAdequacy/PowerSystemAdequacy.jl:169-208 run_non_sequential_mc(gens, load,
  * iterations): per iteration one fleet state (unit g is down iff draw < FOR_g, i.e. up iff
  * rand() >= for_rate, :183-185), available capacity, then the whole hourly load curve is swept:
- * hours with cap < load and their deficit (:191-197). */
+ * hours with cap < load and their deficit (:191-197).  Unit g is down iff draw < thr_g, thr_g = floor(for_rate_g * 2^32) clamped to
+ * [0, 2^32 - 1] (so for_rate 1 leaves a unit up with probability 2^-32).  The deficit of an iteration is the exact sum of
+ * (load - cap) over its loss hours up to a few ulp of the result: the load curve's suffix sums are held in double-double.
+ * Input rule of the four HL1 load calls (relmc_hl1_load, relmc_hl1_seq_load, relmc_hl1_area_load, relmc_hl1_plan_load): every capacity
+ * is finite, every for_rate (relmc_hl1_load, relmc_hl1_plan_load) lies in [0, 1], every hourly load is finite; a call that breaks the
+ * rule changes nothing and returns RELMC_ERR_INVALID with relmc_last_error naming the unit or the hour (and the area). */
 typedef struct {
     int64_t n;                /* iterations                                 */
     double sum_lole;          /* sum over iterations of loss hours          */

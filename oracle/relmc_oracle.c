@@ -872,7 +872,9 @@ int32_t orc_hl1_nsq(int32_t ngen, const double* cap, const double* for_rate, int
             uint32_t ctr[4] = {(uint32_t)gi, (uint32_t)(gi >> 32), (uint32_t)blk, 0u}, r[4];
             philox4x32_10(ctr, key, r);
             for (int e = 0; e < 4 && blk * 4 + e < ngen; ++e) {
-                double t = floor(for_rate[blk * 4 + e] * 4294967296.0);
+                double t = floor(for_rate[blk * 4 + e] * 4294967296.0);   /* clamped to [0, 2^32 - 1] as relmc_hl1_load (include/relmc.h) */
+                if (!(t > 0)) t = 0;
+                if (t > 4294967295.0) t = 4294967295.0;
                 if (!(r[e] < (uint32_t)t)) cap_avail += cap[blk * 4 + e];
             }
         }

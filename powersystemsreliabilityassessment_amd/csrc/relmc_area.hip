@@ -34,11 +34,15 @@ int32_t relmc_hl1_area_load(relmc_ctx* ctx, int32_t n_areas, const int32_t* unit
     A.lo[n_areas] = (int32_t)ngen;
     A.ngen = (int32_t)ngen; A.nhours = nhours; A.n_areas = n_areas;
     for (int g = 0; g < ngen; ++g) {
+        if (!std::isfinite(capacity_mw[g])) return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_load: capacity of unit " + std::to_string(g) + " not finite");
         if (!(std::isfinite(mttf_h[g]) && mttf_h[g] > 0.0 && std::isfinite(mttr_h[g]) && mttr_h[g] > 0.0))
             return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_load: MTTF / MTTR of unit " + std::to_string(g) + " not finite and positive");
         A.cap[g] = capacity_mw[g]; A.mttf[g] = mttf_h[g]; A.mttr[g] = mttr_h[g];
         A.q[g] = mttr_h[g] / (mttf_h[g] + mttr_h[g]);
     }
+    if (const int64_t bad = first_non_finite(hourly_load_mw, (int64_t)n_areas * nhours); bad >= 0)
+        return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_load: load of area " + std::to_string(bad / nhours) + " hour " + std::to_string(bad % nhours) +
+                                            " not finite");
     for (int l = 0; l < n_ties; ++l) {
         const int i = tie_from[l], j = tie_to[l];
         if (i < 0 || i >= n_areas || j < 0 || j >= n_areas || i == j)

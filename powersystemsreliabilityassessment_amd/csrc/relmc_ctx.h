@@ -16,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <functional>
 #include <string>
@@ -191,6 +192,13 @@ using namespace relmc;
 extern const char* const kNoCtx;
 int fail(relmc_ctx* ctx, int code, const std::string& msg);
 bool verbose();                           // RELMC_VERBOSE in the environment (the library's only environment variable), read once
+// index of the first NaN or infinite value of x[0, n), -1 if none (the input rule of the HL1 load calls, include/relmc.h)
+inline int64_t first_non_finite(const double* x, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(x[i])) return i;
+    return -1;
+}
 
 #define HIP_TRY(ctx, expr)                                                                                   \
     do {                                                                                                     \

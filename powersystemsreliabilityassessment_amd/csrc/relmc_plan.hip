@@ -46,6 +46,8 @@ int32_t relmc_hl1_plan_load(relmc_ctx* ctx, int32_t ngen, const double* capacity
             u.slot = P.n_elu; P.elu_cap[P.n_elu] = capacity_mw[g]; P.elu_lim[P.n_elu] = energy_limit_mwh[g]; ++P.n_elu;
         }
     }
+    if (const int64_t bad = first_non_finite(hourly_load_mw, nhours); bad >= 0)
+        return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_plan_load: load of hour " + std::to_string(bad) + " not finite");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     auto& S = ctx->hl1_plan;
     ctx->has_hl1_plan = false;

@@ -306,26 +306,36 @@ int32_t relmc_hl1_load(relmc_ctx* ctx, int32_t ngen, const double* capacity_mw, 
     if (!ctx) return RELMC_ERR_INVALID;
     if (!capacity_mw || !for_rate || !hourly_load_mw || ngen < 1 || nhours < 1) return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_load: bad arguments");
     if (ngen > NCOMPMAX) return fail(ctx, RELMC_ERR_UNSUPPORTED, "relmc_hl1_load: more than 128 units");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     Hl1Case h; std::memset(&h, 0, sizeof(h));
     h.ngen = ngen; h.nhours = nhours;
     for (int g = 0; g < ngen; ++g) {
+        const std::string unit = " of unit " + std::to_string(g);
+        if (!std::isfinite(capacity_mw[g])) return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_load: capacity" + unit + " not finite");
+        if (!(for_rate[g] >= 0.0 && for_rate[g] <= 1.0)) return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_load: for_rate" + unit + " not in [0, 1]");
         double t = std::floor(for_rate[g] * 4294967296.0);
-        if (!(t > 0)) t = 0;
         if (t > 4294967295.0) t = 4294967295.0;
         h.thr[g] = (uint32_t)t; h.cap[g] = capacity_mw[g];
     }
-    std::vector<double> sorted(hourly_load_mw, hourly_load_mw + nhours), suffix(nhours + 1, 0.0);
+    if (const int64_t bad = first_non_finite(hourly_load_mw, nhours); bad >= 0)
+        return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_load: load of hour " + std::to_string(bad) + " not finite");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // suffix[2k], suffix[2k + 1] = sum(sorted[k:]) as a double-double (hi, lo): the kernel's EUE = suffix - cap * hours cancels when the
+    // loads above cap lie close to it, so the sum must carry more than 53 bits (TwoSum per term, then renormalised)
+    std::vector<double> sorted(hourly_load_mw, hourly_load_mw + nhours), suffix(2 * (size_t)nhours + 2, 0.0);
     std::sort(sorted.begin(), sorted.end());
-    for (int k = nhours - 1; k >= 0; --k) suffix[k] = suffix[k + 1] + sorted[k];
+    for (int k = nhours - 1; k >= 0; --k) {
+        const double a = suffix[2 * k + 2], b = sorted[k], s = a + b, bb = s - a, e = (a - (s - bb)) + (b - bb);
+        const double lo = suffix[2 * k + 3] + e, hi = s + lo;
+        suffix[2 * k] = hi; suffix[2 * k + 1] = lo - (hi - s);
+    }
     auto& H = ctx->hl1;
     H.sorted.reset(); H.suffix.reset();
     HIP_TRY(ctx, H.dcase.grow(1));
     HIP_TRY(ctx, H.sorted.grow((size_t)nhours));
-    HIP_TRY(ctx, H.suffix.grow((size_t)nhours + 1));
+    HIP_TRY(ctx, H.suffix.grow(suffix.size()));
     HIP_TRY(ctx, hipMemcpy(ctx->hl1.dcase.get(), &h, sizeof(h), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->hl1.sorted.get(), sorted.data(), sizeof(double) * nhours, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->hl1.suffix.get(), suffix.data(), sizeof(double) * (nhours + 1), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->hl1.suffix.get(), suffix.data(), sizeof(double) * suffix.size(), hipMemcpyHostToDevice));
     ctx->hl1_hours = nhours; ctx->has_hl1 = true;
     return RELMC_OK;
 }
@@ -374,11 +384,14 @@ int32_t relmc_hl1_seq_load(relmc_ctx* ctx, int32_t ngen, const double* capacity_
     Hl1SeqCase h; std::memset(&h, 0, sizeof(h));
     h.ngen = ngen; h.nhours = nhours;
     for (int g = 0; g < ngen; ++g) {
+        if (!std::isfinite(capacity_mw[g])) return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_load: capacity of unit " + std::to_string(g) + " not finite");
         if (!(std::isfinite(mttf_h[g]) && mttf_h[g] > 0.0 && std::isfinite(mttr_h[g]) && mttr_h[g] > 0.0))
             return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_load: MTTF / MTTR of unit " + std::to_string(g) + " not finite and positive");
         h.cap[g] = capacity_mw[g]; h.mttf[g] = mttf_h[g]; h.mttr[g] = mttr_h[g];
         h.q[g] = mttr_h[g] / (mttf_h[g] + mttr_h[g]);
     }
+    if (const int64_t bad = first_non_finite(hourly_load_mw, nhours); bad >= 0)
+        return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_load: load of hour " + std::to_string(bad) + " not finite");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     auto& S = ctx->hl1_seq;
     ctx->has_hl1_seq = false;

@@ -125,7 +125,9 @@ __global__ void __launch_bounds__(256) relmc_seq_annual_kernel(const double* __r
 }
 
 // ---- HL1 copper sheet (PowerSystemAdequacy.jl:169-208): one thread per iteration ------------------
-// sorted[] = hourly loads ascending, suffix[k] = sum(sorted[k:]); loss hours = #{load > cap}, deficit by suffix sums
+// sorted[] = hourly loads ascending, suffix[2k], suffix[2k + 1] = sum(sorted[k:]) as a double-double (hi, lo); loss hours = #{load > cap},
+// deficit = (hi - cap * hours) + lo with the product split exactly by an FMA and the difference by TwoSum: the loads above cap may sum to
+// far more than their excess over cap, and a plain fp64 difference would keep only the bits of the sum
 __global__ void __launch_bounds__(256) relmc_hl1_kernel(const Hl1Case* __restrict__ H, const double* __restrict__ sorted,
                                                         const double* __restrict__ suffix, uint64_t seed, uint64_t first_index,
                                                         int64_t n, double* __restrict__ iter_lole, double* __restrict__ iter_eue,
@@ -146,7 +148,14 @@ __global__ void __launch_bounds__(256) relmc_hl1_kernel(const Hl1Case* __restric
         int lo = 0, hi = nh;                          // first index with sorted[idx] > cap  (cap < load, :192)
         while (lo < hi) { const int mid = (lo + hi) >> 1; if (sorted[mid] > cap) hi = mid; else lo = mid + 1; }
         const double hours = (double)(nh - lo);
-        const double eue = lo < nh ? suffix[lo] - cap * hours : 0.0;
+        double eue = 0.0;
+        if (lo < nh) {
+#pragma clang fp contract(off)
+            const double hi_s = suffix[2 * lo], lo_s = suffix[2 * lo + 1];
+            const double p = cap * hours, pe = __builtin_fma(cap, hours, -p);           // cap * hours = p + pe exactly
+            const double d = hi_s - p, db = d - hi_s, de = (hi_s - (d - db)) + (-p - db);  // hi - p = d + de exactly (TwoSum)
+            eue = d + (de + (lo_s - pe));
+        }
         if (iter_lole) iter_lole[i] = hours;
         if (iter_eue) iter_eue[i] = eue;
         s_l += hours; s_e += eue; s_l2 = __builtin_fma(hours, hours, s_l2); s_e2 = __builtin_fma(eue, eue, s_e2);

@@ -1,0 +1,187 @@
+"""Cases at the edges of the HL1 contracts (include/relmc.h), shared by tests/test_hl1_edges.py (device against the host models) and
+tests/test_hl1_edges_host.py (host models against the reference loops): unit counts around the 4-unit Philox blocks, the 32-bit mask words
+and the two lanes' slots, years shorter than a 64-lane group or straddling the 512-step window, transitions far shorter than a step or far
+longer than the horizon, zero capacities, loads equal to reachable capacity sums, 8 areas on the topologies where augmenting paths are
+long, and the planning model's 8 ELU slots in week 53.  Every value is computed here; nothing is read from disk."""
+from __future__ import annotations
+
+import math
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from oracle.pyoracle import philox4x32_10  # noqa: E402
+
+FOR_EXTREMES = (0.0, 2.0 ** -32, 0.5, 1.0 - 2.0 ** -32, 1.0)
+
+
+def unit_order_sum(cap, up):
+    """Sum of cap[k] over the up units in ascending unit order (the kernels' order), one value per row of up[rows, K]."""
+    s = np.zeros(up.shape[0])
+    for k in range(len(cap)):
+        s = s + np.where(up[:, k], float(cap[k]), 0.0)
+    return s
+
+
+# ---- relmc_hl1_nsq ---------------------------------------------------------------------------------------------------------------
+def nsq_thresholds(for_rate):
+    """The clamped contract: thr = floor(for_rate * 2^32) clamped to [0, 2^32 - 1]."""
+    t = np.floor(np.asarray(for_rate, dtype=np.float64) * 4294967296.0)
+    return np.clip(np.where(t > 0, t, 0.0), 0.0, 4294967295.0).astype(np.uint64)
+
+
+def nsq_up(seed, first_index, n, for_rate):
+    """up[i, g] of iteration first_index + i: draw word g & 3 of philox(ctr = (i_lo, i_hi, g >> 2, 0), key = seed) >= thr_g."""
+    K = len(for_rate)
+    nb = (K + 3) // 4
+    gi = np.uint64(first_index) + np.arange(n, dtype=np.uint64)
+    ctr = np.zeros((n, nb, 4), dtype=np.uint32)
+    ctr[..., 0] = (gi & np.uint64(0xFFFFFFFF)).astype(np.uint32)[:, None]
+    ctr[..., 1] = (gi >> np.uint64(32)).astype(np.uint32)[:, None]
+    ctr[..., 2] = np.arange(nb, dtype=np.uint32)[None, :]
+    key = np.zeros((n, nb, 2), dtype=np.uint32)
+    key[..., 0] = np.uint32(seed & 0xFFFFFFFF)
+    key[..., 1] = np.uint32(seed >> 32)
+    w = philox4x32_10(ctr, key).reshape(n, nb * 4)[:, :K].astype(np.uint64)
+    return w >= nsq_thresholds(for_rate)[None, :]
+
+
+def nsq_fleet(ngen):
+    """ngen units with non-integer capacities; the five FOR extremes cycle through units 0..4, the other units have FOR 0.02 .. 0.3."""
+    rng = np.random.default_rng(1000 + ngen)
+    cap = np.round(rng.uniform(5.0, 80.0, ngen), 3) + 0.0625
+    forr = rng.uniform(0.02, 0.3, ngen)
+    forr[:min(ngen, 5)] = FOR_EXTREMES[:min(ngen, 5)]
+    return cap, forr
+
+
+def nsq_load(cap, forr, nhours, ties=()):
+    """nhours loads spread over the fleet's likely available capacity; the values in `ties` replace the first hours (exact ties)."""
+    rng = np.random.default_rng(nhours + 7 * len(cap))
+    mean = float((np.asarray(cap) * (1.0 - np.asarray(forr))).sum())
+    sd = math.sqrt(float((np.asarray(cap) ** 2 * np.asarray(forr) * (1.0 - np.asarray(forr))).sum())) + 1.0
+    load = mean + sd * rng.uniform(-1.5, 3.0, nhours)
+    t = np.asarray(ties, dtype=np.float64)[:nhours]
+    load[:t.size] = t
+    return load
+
+
+def eue_scales():
+    """(label, base, spread): flat curves base + U(0, spread) just above a fleet whose all-up capacity is exactly `base`."""
+    return (("1000+U(0,1e-3)", 1000.0, 1e-3), ("3000+U(0,1e-6)", 3000.0, 1e-6), ("1e5+U(0,1e-3)", 1e5, 1e-3))
+
+
+def eue_case(base, spread, nhours=8760):
+    """4 units summing to `base` exactly in unit order (FOR 0.01: most iterations are all up) and the flat curve above it."""
+    cap = np.array([0.375, 0.25, 0.125, 0.25]) * base
+    assert cap[0] + cap[1] + cap[2] + cap[3] == base
+    forr = np.full(4, 0.01)
+    load = base + np.random.default_rng(int(base) + 3).uniform(0.0, spread, nhours)
+    return cap, forr, load
+
+
+def exact_eue(caps, load):
+    """math.fsum of the per-hour deficits of every iteration (a deficit load - cap of a flat curve is exact by Sterbenz)."""
+    srt = np.sort(np.asarray(load, dtype=np.float64))
+    uniq, inv = np.unique(np.asarray(caps, dtype=np.float64), return_inverse=True)
+    return np.array([math.fsum((srt[srt > c] - c).tolist()) for c in uniq])[inv]
+
+
+# ---- relmc_hl1_seq ---------------------------------------------------------------------------------------------------------------
+def seq_fleet(ngen, nhours, seed=0):
+    """ngen units with non-integer capacities, a zero-capacity unit, units with MTTR << 1 h (several transitions inside one step, empty
+    intervals) and units with MTTF >> any horizon (no transition); the load curve straddles the mean available capacity and its first
+    hours equal reachable capacity sums (all up; all up but unit j), summed in unit order."""
+    rng = np.random.default_rng(50 + ngen + 1000 * seed)
+    cap = np.round(rng.uniform(5.0, 60.0, ngen), 3) + 0.125
+    mttf = rng.uniform(20.0, 300.0, ngen)
+    mttr = rng.uniform(2.0, 40.0, ngen)
+    if ngen > 1:
+        cap[1] = 0.0
+    mttr[2::5] = rng.uniform(0.01, 0.3, mttr[2::5].size)
+    mttf[2::10] = rng.uniform(1.0, 3.0, mttf[2::10].size)
+    mttf[3::7] = 1e12
+    h = np.arange(nhours)
+    q = mttr / (mttf + mttr)
+    avail = float((cap * (1.0 - q)).sum())
+    sd = math.sqrt(float((cap ** 2 * q * (1.0 - q)).sum())) + 0.5
+    load = avail + sd * (0.3 + 1.2 * np.sin(2 * np.pi * h / 24.0 + 0.3) + 0.4 * np.cos(2 * np.pi * h / max(nhours, 2)))
+    up = np.ones((1 + min(ngen, 4), ngen), dtype=bool)
+    for j in range(1, up.shape[0]):
+        up[j, j - 1] = False
+    ties = unit_order_sum(cap, up)
+    load[:min(nhours, ties.size)] = ties[:nhours]
+    if nhours > 8:
+        load[nhours // 2] = ties[0]
+    return cap, mttf, mttr, load
+
+
+def seq_years(nhours, steps=1600):
+    """Years per chain so that a chain runs about `steps` steps (several 512-step windows), at least 2."""
+    return max(2, -(-steps // nhours))
+
+
+# ---- relmc_hl1_area --------------------------------------------------------------------------------------------------------------
+UNITS8 = [1, 1, 30, 40, 20, 10, 25, 1]                          # 128 units, uneven, three single-unit areas
+
+
+def area_fleet8(nhours=48, seed=0):
+    """128 units in 8 areas (UNITS8, area-major), non-integer capacities, fast repair on some units; loads per area near each area's
+    mean available capacity, area 0 in surplus and area 7 short (the path topology's 7-hop transfers)."""
+    rng = np.random.default_rng(77 + seed)
+    K = sum(UNITS8)
+    cap = np.round(rng.uniform(5.0, 50.0, K), 3) + 0.25
+    mttf = rng.uniform(40.0, 400.0, K)
+    mttr = rng.uniform(3.0, 50.0, K)
+    mttr[5::9] = rng.uniform(0.02, 0.4, mttr[5::9].size)
+    lo = np.concatenate([[0], np.cumsum(UNITS8)])
+    h = np.arange(nhours)
+    loads = np.zeros((8, nhours))
+    for a in range(8):
+        s = slice(lo[a], lo[a + 1])
+        avail = float((cap[s] * mttf[s] / (mttf[s] + mttr[s])).sum())
+        level = 0.6 if a == 0 else (1.08 if a == 7 else 0.95)
+        loads[a] = avail * (level + 0.08 * np.sin(2 * np.pi * (h - 3 * a) / 24.0))
+    return list(UNITS8), cap, mttf, mttr, loads
+
+
+def topologies8():
+    """name -> ties [(from, to, capacity)] on 8 areas."""
+    rng = np.random.default_rng(5)
+    complete = [(i, j, float(np.round(rng.uniform(5.0, 40.0), 2))) for i in range(8) for j in range(i + 1, 8)]
+    complete += [(j, i, 7.5) for i, j, _ in complete[::4]]                                # parallel ties, reversed endpoints
+    return {
+        "complete": complete,
+        "path": [(i, i + 1, 60.0 + 5.0 * i) for i in range(7)],
+        "star": [(0, j, 30.0 + 4.0 * j) for j in range(1, 8)],
+        "two_components": [(0, 1, 25.0), (1, 2, 35.5), (2, 3, 20.0), (0, 3, 10.0), (4, 5, 40.0), (5, 6, 15.25), (6, 7, 30.0), (4, 7, 12.0)],
+        "zero_ties": [(i, i + 1, 0.0) for i in range(7)] + [(0, 7, 0.0)],
+    }
+
+
+# ---- relmc_hl1_plan --------------------------------------------------------------------------------------------------------------
+def plan_fleet(ngen, nhours=8760, n_elu=0, binding=True, sigma_frac=0.03):
+    """ngen units with non-integer capacities, FOR 0.02 .. 0.15, maintenance windows that run past the end of the year or start in
+    week 53 (when nhours reaches it), the last n_elu units energy-limited (small limits when binding, finite but never reached
+    otherwise), a load curve near the mean available capacity; -> (cap, forr, start, weeks, limit, load), sigma."""
+    rng = np.random.default_rng(300 + ngen + 17 * n_elu + (0 if binding else 1))
+    cap = np.round(rng.uniform(10.0, 90.0, ngen), 3) + 0.137
+    forr = rng.uniform(0.02, 0.15, ngen)
+    start = np.zeros(ngen, dtype=np.int32)
+    weeks = np.zeros(ngen, dtype=np.int32)
+    windows = [(52, 3), (53, 1), (53, 5), (1, 2), (51, 2)]
+    for k in [k for k in range(ngen) if k < 3 or k % 3 == 0]:
+        start[k], weeks[k] = windows[k if k < 3 else (k // 3) % len(windows)]
+    limit = np.full(ngen, math.inf)
+    if n_elu:
+        elu = np.arange(ngen - n_elu, ngen)
+        limit[elu] = cap[elu] * (rng.uniform(20.0, 60.0, n_elu) if binding else 1e9)
+    h = np.arange(nhours)
+    avail = float((cap * (1.0 - forr)).sum())
+    load = avail * (0.8 + 0.12 * np.sin(2 * np.pi * h / 24.0) + 0.05 * np.sin(2 * np.pi * h / 8760.0 * 3))
+    return (cap, forr, start, weeks, limit, load), sigma_frac * avail

@@ -407,8 +407,18 @@ class Engine:
         return buf.value.decode()
 
     def debug_set(self, key: str, value: bool = True):
-        """Diagnosis switch of the context (tests): no_retry, retry_dense_first, nsq_no_stretch, db_no_probe (relmc_debug_set)."""
+        """Diagnosis switch of the context (tests): no_retry, retry_dense_first, nsq_no_stretch, db_no_probe, dynamic_shape (relmc_debug_set)."""
         self._check(self.L.relmc_debug_set(self._h, key.encode(), int(bool(value))), "relmc_debug_set")
+
+    def shape_path(self) -> str:
+        """Which evaluation kernel the fused path launches now: "static" (the instantiation with the shipped RTS-24 shape compiled in, chosen
+        by relmc_case_load when every shape field of the case equals it) or "dynamic" (relmc_debug_shape_path)."""
+        f = self.L.relmc_debug_shape_path
+        f.restype, f.argtypes = C.c_int32, [C.c_void_p]
+        rc = f(self._h)
+        if rc < 0:
+            raise RelmcError(f"relmc_debug_shape_path failed ({rc})")
+        return "static" if rc == 1 else "dynamic"
 
     def last_kernel_ms(self) -> float:
         ms = C.c_double()

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <type_traits>
 
 #include "relmc_ctx.h"
 #ifdef RELMC_DEV_SWITCHES
@@ -76,8 +77,19 @@ int launch_eval_t(relmc_ctx* ctx, EvalArgs& a, int* rows_out, hipEvent_t ev_star
     a.timing = nullptr;
 #endif
     HIP_TRY(ctx, hipEventRecord(ev_start ? ev_start : ctx->ev0, ctx->stream));
-    hipLaunchKernelGGL((relmc_eval_kernel<MODE, TL>), dim3(blocks), dim3(64 * TL::WPB), alt ? ctx->alt_lds_bytes[alt - 1] : ctx->lds_bytes, ctx->stream,
-                       reinterpret_cast<const DevCaseT<TL>*>(alt ? ctx->dcase_alt[alt - 1].get() : ctx->dcase.get()), a);
+    // the fused path of a case whose whole shape is the compiled-in one (shape_select) runs the shape-specialised instantiation: same program,
+    // same results; the further orders' images (alt) have other pass counts and stay with the interpreter
+    bool launched = false;
+    if constexpr (MODE == 0 && std::is_same<TL, Tile24>::value) {
+        if (alt == 0 && ctx->shape_static && !ctx->sw.dynamic_shape) {
+            hipLaunchKernelGGL((relmc_eval_kernel<0, Tile24, ShapeRts24>), dim3(blocks), dim3(64 * Tile24::WPB), ctx->lds_bytes, ctx->stream,
+                               reinterpret_cast<const DevCaseT<Tile24>*>(ctx->dcase.get()), a);
+            launched = true;
+        }
+    }
+    if (!launched)
+        hipLaunchKernelGGL((relmc_eval_kernel<MODE, TL>), dim3(blocks), dim3(64 * TL::WPB), alt ? ctx->alt_lds_bytes[alt - 1] : ctx->lds_bytes, ctx->stream,
+                           reinterpret_cast<const DevCaseT<TL>*>(alt ? ctx->dcase_alt[alt - 1].get() : ctx->dcase.get()), a);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ev_stop ? ev_stop : ctx->ev1, ctx->stream));
     *rows_out = blocks * TL::WPB * TL::SPW;
@@ -109,7 +121,17 @@ int eval_set_lds(relmc_ctx* ctx, int bytes)
                           reinterpret_cast<const void*>(&relmc_eval_kernel<4, TL>), reinterpret_cast<const void*>(&relmc_eval_kernel<5, TL>),
                           reinterpret_cast<const void*>(&relmc_eval_kernel<6, TL>), reinterpret_cast<const void*>(&relmc_eval_kernel<7, TL>)})
         HIP_TRY(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    if (std::is_same<TL, Tile24>::value)
+        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&relmc_eval_kernel<0, Tile24, ShapeRts24>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     return RELMC_OK;
+}
+
+// does the primary image of the loaded case have the compiled-in shape, field by field?  (after relmc_case_load built it, and again when the
+// order calibration makes another image the primary)
+void shape_select(relmc_ctx* ctx)
+{
+    ctx->shape_static = ctx->tile == 0 && shape_matches<ShapeRts24>(ctx->hcase24, ctx->stash_off, ctx->scen_doubles);
+    if (verbose()) fprintf(stderr, "relmc: evaluation kernel of the fused path: %s\n", ctx->shape_static ? (ctx->sw.dynamic_shape ? "shape-specialised (RTS-24) available, forced dynamic" : "shape-specialised (RTS-24)") : "dynamic shape");
 }
 }  // namespace
 
@@ -179,6 +201,7 @@ int case_load_impl(relmc_ctx* ctx, const relmc_case_desc* d, DevCaseT<TL>& C, in
     HIP_TRY(ctx, hipMemcpyAsync(ctx->dcase.get(), &C, sizeof(C), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->nb = nb; ctx->ng = ng; ctx->nl = nl; ctx->ncomp = ncomp;
+    ctx->shape_static = false;               // set by relmc_case_load once the host copy of the image is complete (shape_select)
     ctx->has_seq = false;
     ctx->has_case = true;
     return RELMC_OK;
@@ -245,6 +268,7 @@ int order_calibrate(relmc_ctx* ctx)
         if (ctx->tile == 0) HIP_TRY(ctx, hipMemcpy(&ctx->hcase24, ctx->dcase.get(), sizeof(ctx->hcase24), hipMemcpyDeviceToHost));
         else HIP_TRY(ctx, hipMemcpy(&ctx->hcase96, ctx->dcase.get(), sizeof(ctx->hcase96), hipMemcpyDeviceToHost));
         ctx->order_primary = best;
+        shape_select(ctx);
         int bpc = 0; hipError_t e = hipSuccess;
         const int lds = (int)ctx->lds_bytes;
         const int most = lds > (int)ctx->alt_lds_bytes[v] ? lds : (int)ctx->alt_lds_bytes[v];
@@ -368,6 +392,7 @@ int32_t relmc_case_load(relmc_ctx* ctx, const relmc_case_desc* d)
         ctx->tile = 0;
         int rc = case_load_impl<Tile24>(ctx, d, ctx->hcase24);
         ctx->order_hint.clear();                         // a hint is for one relmc_case_load
+        if (rc == RELMC_OK) shape_select(ctx);
         if (rc == RELMC_OK) rc = screen_build(ctx, d);
         return rc ? rc : order_calibrate(ctx);
     }

@@ -32,6 +32,7 @@ struct relmc_switches {
     bool retry_dense_first = false;  // listed units straight to the dense pivoted solve
     bool nsq_no_stretch = false;     // relmc_nsq_run: one launch per batch
     bool db_no_probe = false;        // state database: every batch through the dedupe, no per-sample probe
+    bool dynamic_shape = false;      // fused path: the run-time-shape evaluation kernel even when the case has the compiled-in shape
 };
 
 namespace relmc_host {
@@ -101,6 +102,7 @@ struct relmc_ctx {
     int num_cu = 0;
     int blocks_per_cu = 0;
     uint32_t scen_doubles = 0, lds_bytes = 0, stash_off = 0;
+    bool shape_static = false;           // the primary image has the compiled-in shape (relmc_shape_rts24.h): MODE 0 launches use that instantiation
     DevBuf<unsigned long long> dtiming; int timing_waves = 0;
     struct History { DevBuf<double> d; PinBuf<double> h; } hist;      // per-sample dns of one launch (checkpoint histories of small batches, relmc_nsq_run)
     // distinct-state path: device buffers sized for the samples of a dedupe

@@ -3,8 +3,10 @@
 // per-iteration traces of the profiling builds, the diagnosis switches of a context.
 #include <cstdio>
 #include <cstring>
+#include <memory>
 
 #include "relmc_ctx.h"
+#include "relmc_shape_rts24.h"
 
 using namespace relmc_host;
 
@@ -83,8 +85,43 @@ int32_t relmc_debug_trace(relmc_ctx* ctx, double* out, int32_t n_doubles)
     return RELMC_OK;
 }
 
-// diagnosis switches of the context (tests): "no_retry", "retry_dense_first", "nsq_no_stretch", "db_no_probe"; value 0 / 1.
-// no_retry must be set before relmc_case_load (the order calibration and the list arming must agree).
+// The shape fields of relmc_shape.h (SF_COUNT values, in ShapeField order).  case_out: what relmc_case_load computes for this case under the
+// given primary order (host only: no device, no context; null = skip); static_out: the shape compiled into the specialised fused kernel
+// (relmc_shape_rts24.h; null = skip).  Returns the number of fields, or a negative error.
+int32_t relmc_debug_shape(const relmc_case_desc* d, const int32_t* order_hint, int32_t n_hint, int32_t* case_out, int32_t* static_out)
+{
+    if (static_out) ShapeRts24::values(static_out);
+    if (case_out) {
+        if (!d) return RELMC_ERR_INVALID;
+        SymOpts so = sym_opts_default();
+        if (order_hint && n_hint > 0) { so.order_hint = order_hint; so.n_hint = n_hint; }
+        std::string err;
+        SymGeom g;
+        int rc;
+        if (fits_tile24(d)) {
+            auto C = std::make_unique<DevCaseT<Tile24>>();
+            rc = case_symbolic<Tile24>(d, *C, 0, so, g, err);
+            if (rc == RELMC_OK) shape_of(*C, g.stash_off, g.scen_doubles, case_out);
+        } else {
+            auto C = std::make_unique<DevCaseT<Tile96>>();
+            rc = case_symbolic<Tile96>(d, *C, 0, so, g, err);
+            if (rc == RELMC_OK) shape_of(*C, g.stash_off, g.scen_doubles, case_out);
+        }
+        if (rc) return rc < 0 ? rc : -rc;
+    }
+    return SF_COUNT;
+}
+
+// which evaluation kernel the fused path of this context launches now: 1 = the shape-specialised instantiation, 0 = the run-time-shape one
+int32_t relmc_debug_shape_path(const relmc_ctx* ctx)
+{
+    if (!ctx || !ctx->has_case) return RELMC_ERR_INVALID;
+    return ctx->shape_static && !ctx->sw.dynamic_shape ? 1 : 0;
+}
+
+// diagnosis switches of the context (tests): "no_retry", "retry_dense_first", "nsq_no_stretch", "db_no_probe", "dynamic_shape"; value 0 / 1.
+// no_retry must be set before relmc_case_load (the order calibration and the list arming must agree).  dynamic_shape may change between
+// launches: the fused path then runs the run-time-shape kernel on a case that has the compiled-in shape (tests/test_shape_paths.py).
 int32_t relmc_debug_set(relmc_ctx* ctx, const char* key, int32_t value)
 {
     if (!ctx || !key) return RELMC_ERR_INVALID;
@@ -93,6 +130,7 @@ int32_t relmc_debug_set(relmc_ctx* ctx, const char* key, int32_t value)
     else if (!std::strcmp(key, "retry_dense_first")) ctx->sw.retry_dense_first = v;
     else if (!std::strcmp(key, "nsq_no_stretch")) ctx->sw.nsq_no_stretch = v;
     else if (!std::strcmp(key, "db_no_probe")) ctx->sw.db_no_probe = v;
+    else if (!std::strcmp(key, "dynamic_shape")) ctx->sw.dynamic_shape = v;
     else return fail(ctx, RELMC_ERR_INVALID, std::string("relmc_debug_set: unknown switch ") + key);
     return RELMC_OK;
 }

@@ -15,6 +15,7 @@
 //    are computed once per case on the host: the kernel only interprets a static list of
 //    passes (16 independent block tasks per pass and scenario) on a ~4 KB LDS workspace.
 #include "relmc_devfn.h"
+#include "relmc_shape_rts24.h"
 
 namespace relmc {
 
@@ -32,6 +33,14 @@ constexpr int kMinWaves = 2;       // waves per SIMD the register allocator must
 #define RELOAD_FENCE() __asm__ volatile("" ::: "memory")
 // keeps the unrolled per-slot bodies from being interleaved (each body has ~20 live temporaries)
 #define SLOT_FENCE() __builtin_amdgcn_sched_barrier(0)
+// The solver's pass loops get constant trip counts from a static shape and the compiler unrolls them (measured: -2.2 % kernel time, scratch
+// 176 -> 144 B/lane; kept as loops the same shape gives -0.5 %, DESIGN_HISTORY.md).  Ablation builds: -DRELMC_PASS_NOUNROLL keeps them loops;
+// on the run-time trip counts of ShapeDynamic the pragma changes nothing.
+#ifdef RELMC_PASS_NOUNROLL
+#define PASS_LOOP _Pragma("nounroll")
+#else
+#define PASS_LOOP
+#endif
 // (round 3 re-measured every one of the six fence sites: removing any of them is neutral on the 16-lane tile and 0.3-2.7 % slower on the
 // wide one, profiles/r3_pf/c11_*.log)
 // LDS round trips of the vector phases taken off the wavefront's critical path (kPfMask, bit k = site k): table words are requested
@@ -76,7 +85,9 @@ constexpr int kPfMaskWide = 0xc6;    // 64-lane tile: sites 1, 2, 6, 7 (-2.9 %)
 // MODE 6: MODE 4 with a dense, partially pivoted Newton solve in global scratch (a.dense): the last resort of the retry path
 // MODE 7: the fused path behind the zero-curtailment pre-screen (relmc_screen.hip): scenario u = sample memo_perm[u] of the launch's range, the
 //         ones the certificate did not cover, state = memo_keys[memo_perm[u]]; accumulators as MODE 0, per-sample dns at the sample's own index
-template <int MODE_, class TL>
+// SH: where the case's shape comes from (relmc_shape.h) -- ShapeDynamic reads it at run time (any case of the tile), a static shape compiles it
+// in (pass loops with constant trip counts, gathers without their early exits, guards and LDS sub-array offsets folded away).
+template <int MODE_, class TL, class SH = ShapeDynamic>
 __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(const DevCaseT<TL>* __restrict__ gcase, const EvalArgs a)
 {
     constexpr int MODE = MODE_ == 5 ? 0 : (MODE_ == 6 ? 4 : MODE_);     // 5: the order-calibration probe = the fused path under a kernel name of its own (profiles stay clean)
@@ -115,24 +126,24 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
         for (uint32_t i = tid; i < case_bytes / 4; i += 64 * WPB) dst[i] = src[i];
     }
     __syncthreads();
-    double* const W = reinterpret_cast<double*>(smem + OPT_BYTES + ((case_bytes + 15u) & ~15u)) + (size_t)row * a.scen_doubles;
+    double* const W = reinterpret_cast<double*>(smem + OPT_BYTES + ((case_bytes + 15u) & ~15u)) + (size_t)row * SHAPE(scen_doubles, a.scen_doubles);
     // The evaluation arrays ALIAS the solver workspace: they are dead once the bus gathers have been
     // taken into registers, and only then are the KKT blocks written (see "assemble" below).
     // line record l = {g, lx, q, F} at LR + 4l; injection j: its p at IR[j], its {1/D, Np/D} in the stash pair j (the stash is indexed
     // by injection and survives the solve, so the pair is stored once for the gathers and for the step); record nl / entry ninj is an
     // all-zero dummy that unused gather slots point to.
-    const int nlp = C.nl, nip = C.ninj;
+    const int nlp = SHAPE(nl, C.nl), nip = SHAPE(ninj, C.ninj);
     double* const LR = W;
     double* const IR = W + 4 * (nlp + 1);
-    const int maxdeg0 = C.maxdeg_s[0], maxdeg1 = C.maxdeg_s[1], maxinj0 = C.maxinj_s[0], maxinj1 = C.maxinj_s[1];   // longest incidence lists per bus slot
-    double* const Stash = W + a.stash_off + 2 * rlane;      // [IS][RW] pairs {1/D, Np/D} of this lane's injections (one b128 access each)
-    const double* const StashJ = W + a.stash_off;          // pair j of the stash, read by the bus that gathers injection j (pair IS * RW: zeros)
-    double* const Lam = W + a.stash_off + 2 * IS * RW + 2;   // [NBT]: bus multipliers lambda_i (kept across the solve)
+    const int maxdeg0 = SHAPE(maxdeg0, C.maxdeg_s[0]), maxdeg1 = SHAPE(maxdeg1, C.maxdeg_s[1]), maxinj0 = SHAPE(maxinj0, C.maxinj_s[0]), maxinj1 = SHAPE(maxinj1, C.maxinj_s[1]);   // longest incidence lists per bus slot
+    double* const Stash = W + SHAPE(stash_off, a.stash_off) + 2 * rlane;      // [IS][RW] pairs {1/D, Np/D} of this lane's injections (one b128 access each)
+    const double* const StashJ = W + SHAPE(stash_off, a.stash_off);          // pair j of the stash, read by the bus that gathers injection j (pair IS * RW: zeros)
+    double* const Lam = W + SHAPE(stash_off, a.stash_off) + 2 * IS * RW + 2;   // [NBT]: bus multipliers lambda_i (kept across the solve)
     uint32_t* const OB = reinterpret_cast<uint32_t*>(Lam + NBT);   // [OW]: outage mask of the scenario
 
-    const int ng = C.ng, ncomp = C.ncomp, nb = C.nb;
-    const bool bwd_all_half = __builtin_amdgcn_readfirstlane((uint32_t)(C.bwd_half != 0 ? 1u : 0u)) != 0;      // all back-substitution passes in half form (relmc_dev.h)
-    const int off_rhs = C.off_rhs, npu = C.npass_upd, npi = C.npass_inv, npass = C.npass, nzero = C.nzero, npuh = C.npass_upd - C.npass_updq, npuf = npuh - C.npass_updh;
+    const int ng = SHAPE(ng, C.ng), ncomp = C.ncomp, nb = SHAPE(nb, C.nb);
+    const bool bwd_all_half = SHAPE(bwd_all_half, __builtin_amdgcn_readfirstlane((uint32_t)(C.bwd_half != 0 ? 1u : 0u)) != 0);      // all back-substitution passes in half form (relmc_dev.h)
+    const int off_rhs = SHAPE(off_rhs, C.off_rhs), npu = SHAPE(npass_upd, C.npass_upd), npi = SHAPE(npass_inv, C.npass_inv), npass = SHAPE(npass, C.npass), nzero = SHAPE(nzero, C.nzero), npuh = SHAPE(npass_upd, C.npass_upd) - SHAPE(npass_updq, C.npass_updq), npuf = npuh - SHAPE(npass_updh, C.npass_updh);
     const double base = C.base_mva;
     const double eps = 2.220446049250313e-16;
 
@@ -201,10 +212,10 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
     // wavefront iterates until the slowest of its four rows has converged (mean of the maximum 12.9 vs mean 12.19).
     constexpr bool WINDOWED = (MODE == 0 && RW == 16);
     uint32_t* const WIN = reinterpret_cast<uint32_t*>(smem + OPT_BYTES + ((case_bytes + 15u) & ~15u)) +
-                          (size_t)SPW * WPB * a.scen_doubles * 2 + (size_t)(tid >> 6) * 256;      // [64 slots][4 words] per wavefront
+                          (size_t)SPW * WPB * SHAPE(scen_doubles, a.scen_doubles) * 2 + (size_t)(tid >> 6) * 256;      // [64 slots][4 words] per wavefront
     // slot -> sampling lane of the window (the scenario's position in the sampled range), read only when per-scenario dns is asked for
     uint8_t* const WINL = reinterpret_cast<uint8_t*>(smem + OPT_BYTES + ((case_bytes + 15u) & ~15u)) +
-                          ((size_t)SPW * WPB * a.scen_doubles * 2 + (size_t)WPB * 256) * 4 + (size_t)(tid >> 6) * 64;
+                          ((size_t)SPW * WPB * SHAPE(scen_doubles, a.scen_doubles) * 2 + (size_t)WPB * 256) * 4 + (size_t)(tid >> 6) * 64;
     int64_t wb_begin = gwave, wb_end = ngroups, wb_step = gstride;
     if (WINDOWED) {
         wb_begin = ngroups * gwave / gstride; wb_end = ngroups * (gwave + 1) / gstride; wb_step = 16;
@@ -639,7 +650,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
             }
 #pragma unroll
             for (int t = 0; t < BS; ++t) if (vb[t] < nb) Lam[vb[t]] = 0.0;
-            if (rlane == 0) st2(W + a.stash_off + 2 * IS * RW, 0.0, 0.0);     // the stash pair behind the last lane's: the dummy entry when every lane holds an injection
+            if (rlane == 0) st2(W + SHAPE(stash_off, a.stash_off) + 2 * IS * RW, 0.0, 0.0);     // the stash pair behind the last lane's: the dummy entry when every lane holds an injection
             niq = row_add<RW>(nq);
             fval = row_sum<RW>(fl);
             f0 = fval;
@@ -947,6 +958,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 unsigned char* const W8 = reinterpret_cast<unsigned char*>(W);
 #define WP(off) reinterpret_cast<double*>(W8 + (off))
                 uint2 dsc = *reinterpret_cast<const uint2*>(&TASKSRC.task[0][rlane][0]);
+                PASS_LOOP
                 for (int p = 0; p < npuf; ++p) {             // T -= Wa * inv(D) * Wb'   (T: 2x2 block, or 1x2 rhs row)
                     const uint2 nxt = *reinterpret_cast<const uint2*>(&TASKSRC.task[p + 1][rlane][0]);
                     if ((dsc.x & 0xffffu) != 0xffffu) {
@@ -976,6 +988,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                     }
                     dsc = nxt;
                 }
+                PASS_LOOP
                 for (int p = npuf; p < npuh; ++p) {          // the same update, one row of T per lane (passes filled to at most a half, relmc_dev.h)
                     const uint2 nxt = *reinterpret_cast<const uint2*>(&TASKSRC.task[p + 1][rlane][0]);
                     if ((dsc.x & 0xffffu) != 0xffffu) {
@@ -995,6 +1008,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                     }
                     dsc = nxt;
                 }
+                PASS_LOOP
                 for (int p = npuh; p < npu; ++p) {           // the same update, one element of T per lane (sparsely filled passes, relmc_dev.h)
                     const uint2 nxt = *reinterpret_cast<const uint2*>(&TASKSRC.task[p + 1][rlane][0]);
                     if ((dsc.x & 0xffffu) != 0xffffu) {
@@ -1015,6 +1029,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                     dsc = nxt;
                 }
                 PT_MARK(4)
+                PASS_LOOP
                 for (int p = npu; p < npu + npi; ++p) {      // D <- P = inv(D) in place; y <- P*y
                     const uint2 nxt = *reinterpret_cast<const uint2*>(&TASKSRC.task[p + 1][rlane][0]);
                     if ((dsc.x & 0xffffu) != 0xffffu) {
@@ -1031,6 +1046,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 }
                 PT_MARK(5)
                 if (RW == 64 && bwd_all_half) {               // every back-substitution pass is filled to at most a half: one component of y_i per lane (wide tile only)
+                PASS_LOOP
                     for (int p = npu + npi; p < npass; ++p) {
                         const uint2 nxt = *reinterpret_cast<const uint2*>(&TASKSRC.task[p + 1][rlane][0]);
                         if ((dsc.x & 0xffffu) != 0xffffu) {
@@ -1047,6 +1063,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                         dsc = nxt;
                     }
                 } else
+                PASS_LOOP
                 for (int p = npu + npi; p < npass; ++p) {    // y_i -= P_i * W' * x_a
                     const uint2 nxt = *reinterpret_cast<const uint2*>(&TASKSRC.task[p + 1][rlane][0]);
                     if ((dsc.x & 0xffffu) != 0xffffu) {

@@ -1,7 +1,9 @@
 """Which device functions of a unit changed between two source states?  Compiles the unit's gfx950 assembly for a git revision (default HEAD,
 via `git stash`-free `git show` into a temp tree) and for the working tree, strips comments / directives and compares function by function:
     python scripts/device_asm_diff.py [unit.hip] [rev]
-Used in round 5 to show that a change to relmc_finalize_kernel left all 14 relmc_eval_kernel instantiations byte-identical."""
+Used in round 5 to show that a change to relmc_finalize_kernel left all 14 relmc_eval_kernel instantiations byte-identical.
+A defaulted template argument that one side lacks (relmc_eval_kernel's ShapeDynamic) is dropped from the mangled names, so such an instantiation
+is compared with its predecessor and not listed as one function gone and one new."""
 import hashlib, os, re, shutil, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "powersystemsreliabilityassessment_amd", "csrc")
@@ -19,7 +21,7 @@ def funcs(path):
     for ln in open(path):
         m = re.match(r"^(_Z\w+):", ln)
         if m:
-            cur, buf = m.group(1), []
+            cur, buf = m.group(1).replace("NS_12ShapeDynamicE", ""), []
         elif cur is not None:
             if ln.startswith(".Lfunc_end"):
                 out[cur] = buf; cur = None

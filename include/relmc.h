@@ -362,7 +362,8 @@ int32_t relmc_hl1_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64
  * A one-area run without ties therefore has relmc_hl1_seq's chronology, and ISOLATED / INTERCONNECTED runs of one seed see the same fleet.
  * Per step (every area shares nhours H, 0-based areas):
  *   m_i = cap_i - load_i[h], cap_i = sum of area i's UP units' capacities in ascending unit order.
- *   T[i][j] = T[j][i] = sum of the capacities of the ties between i and j (parallel ties summed; ties never fail).
+ *   T[i][j] = T[j][i] = sum of the capacities of the ties between i and j (parallel ties summed in tie order; a tie fails only with
+ *     relmc_hl1_area_tie_outages' data, below).
  *   every m_i >= 0: nothing is curtailed.  ISOLATED: no transfer.
  *   INTERCONNECTED, RELMC_HL1_AREA_FLOW_REFERENCE (:105-167): R = T; loop { s = lowest i with m_i > 1e-4, t = lowest i with m_i < -1e-4,
  *     stop if either is missing; BFS from s (FIFO queue [s], s marked; pop u, u == t: path found; else for v = 0..n-1 ascending, if
@@ -392,6 +393,24 @@ int32_t relmc_hl1_area_load(relmc_ctx* ctx, int32_t n_areas, const int32_t* unit
  * only, not on how a chain range is split into calls; sums are taken in a fixed order, so a repeated call is bitwise identical. */
 int32_t relmc_hl1_area(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain, int32_t start,
                        int32_t policy, int32_t flow, relmc_hl1_seq_acc* acc, relmc_hl1_seq_year* years_host);
+/* Tie outages (an extension: the reference's ties never fail).  Tie t (0-based, in relmc_hl1_area_load's order) is a two-state component
+ * with tie_mttf_h[t] / tie_mttr_h[t] hours.  Its chronology is relmc_hl1_seq's, word for word (draws, -m ln U in fp64, product and sum each
+ * rounded, DOWN on steps [ceil(T_odd), ceil(T_even)), both start rules with DOWN iff U < mttr / (mttf + mttr) under STATIONARY), with
+ * component index k = RELMC_HL1_TIE_DRAW_BASE + t in the counter word ((128 + t) | 0x40000000).  Units use k < 128, so the fleet's history
+ * does not depend on whether ties fail: runs with and without tie outages under one seed see the same unit states.
+ *   tie_mttf_h[t] = +INFINITY: tie t never fails; it takes no draws and tie_mttr_h[t] is not read.  Every other mttf, and its mttr, must be
+ *   finite and > 0.
+ *   Per step, T[i][j] = T[j][i] = the sum, from 0.0 in ascending tie order, of the capacities of the ties between i and j that are UP in
+ *   that step (with every tie UP: the matrix relmc_hl1_area_load holds).  Everything after T is unchanged; ISOLATED never reads T.
+ * At most RELMC_HL1_TIE_MAX ties when outage data is set.  RELMC_ERR_INVALID, with relmc_last_error naming the tie: more ties than that, a
+ * count that differs from the loaded model's, a mttf that is NaN, <= 0 or -INFINITY, a mttr of a failing tie that is not finite and > 0.
+ * A refused call changes nothing.  RELMC_ERR_NO_CASE before relmc_hl1_area_load. */
+#define RELMC_HL1_TIE_MAX 32
+#define RELMC_HL1_TIE_DRAW_BASE 128
+/* Forced outages of the ties of the loaded multi-area model.  n_ties = the loaded count.  NULL, NULL (or n_ties = 0) removes
+ * the outage data.  relmc_hl1_area_load removes it too.  Read by relmc_hl1_area under INTERCONNECTED; the split / repeat guarantees of
+ * relmc_hl1_area hold with it as they are. */
+int32_t relmc_hl1_area_tie_outages(relmc_ctx* ctx, int32_t n_ties, const double* tie_mttf_h, const double* tie_mttr_h);
 
 /* ---- HL1 planning model: maintenance, energy-limited units, LFU (generating_adequancy_comparative.jl:15-120, tail_risk.jl:12-91) ---- */
 /* Year y is the global index first_year + i; hour h is 0-based; every year starts with every ELU's energy at 0; years are independent.

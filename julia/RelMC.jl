@@ -513,18 +513,26 @@ end
 const AREA_MAX = 8                                                            # RELMC_AREA_MAX
 const HL1_AREA_POLICY = Dict(:isolated => Int32(0), :interconnected => Int32(1))   # RELMC_HL1_AREA_ISOLATED / _INTERCONNECTED
 const HL1_AREA_FLOW = Dict(:reference => Int32(0), :max_flow => Int32(1))         # RELMC_HL1_AREA_FLOW_*
+const HL1_TIE_MAX = 32                                                        # RELMC_HL1_TIE_MAX
+const HL1_TIE_DRAW_BASE = 128                                                 # RELMC_HL1_TIE_DRAW_BASE
 
 """
 run_fast_sequential_simulation (AdequacyAssessmentII.jl:185-250): the multi-area chronology on the GPU.  `units_per_area` counts the
 units of each area; `capacity`, `mttf`, `mttr` are area-major; `hourly_load` is n_areas x nhours; ties are 1-based (from, to, capacity)
 as the reference's TieLine.  policy :isolated or :interconnected, flow :reference (the reference's loop) or :max_flow.  Returns per-area
 LOLE, EUE, LOLF, the system row (a loss hour in any area) and the per-year indices (years x (n_areas + 1) x 3, chain-major).
+`tie_mttf` / `tie_mttr` (hours, one per tie; an extension, the reference's ties never fail): ties with a finite MTTF fail and repair like
+units (relmc_hl1_area_tie_outages), `Inf` = never; without them no tie fails.
 """
 function run_fast_sequential_simulation(eng::Engine, units_per_area::Vector{Int32}, capacity::Vector{Float64}, mttf::Vector{Float64},
                                         mttr::Vector{Float64}, hourly_load::Matrix{Float64}, tie_from::Vector{Int32}, tie_to::Vector{Int32},
                                         tie_capacity::Vector{Float64}, policy::Symbol, n_years::Integer; seed::Integer=1, chains::Integer=1,
-                                        start::Symbol=:all_up, flow::Symbol=:reference)
+                                        start::Symbol=:all_up, flow::Symbol=:reference,
+                                        tie_mttf::Union{Nothing,Vector{Float64}}=nothing, tie_mttr::Union{Nothing,Vector{Float64}}=nothing)
     (n_years >= 1 && chains >= 1 && n_years % chains == 0) || throw(ArgumentError("n_years must be a positive multiple of chains"))
+    (tie_mttf === nothing) == (tie_mttr === nothing) || throw(ArgumentError("tie_mttf and tie_mttr go together"))
+    tie_mttf === nothing || (length(tie_mttf) == length(tie_mttr) == length(tie_from) <= HL1_TIE_MAX) ||
+        throw(ArgumentError("one tie_mttf / tie_mttr per tie, $HL1_TIE_MAX ties at most"))
     n = length(units_per_area)
     (1 <= n <= AREA_MAX && size(hourly_load, 1) == n) || throw(ArgumentError("1..$AREA_MAX areas, one load row per area"))
     load = Matrix(permutedims(hourly_load))                                  # column-major n x H -> the C layout [n_areas][nhours]
@@ -532,6 +540,10 @@ function run_fast_sequential_simulation(eng::Engine, units_per_area::Vector{Int3
                                                      Ptr{Cdouble}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}),
                 eng.h, n, units_per_area, capacity, mttf, mttr, size(hourly_load, 2), load, length(tie_from), tie_from .- Int32(1),
                 tie_to .- Int32(1), tie_capacity), eng.h, "relmc_hl1_area_load")
+    if tie_mttf !== nothing && any(isfinite, tie_mttf)                        # the load has removed any earlier outage data
+        check(ccall((:relmc_hl1_area_tie_outages, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}),
+                    eng.h, length(tie_mttf), tie_mttf, tie_mttr), eng.h, "relmc_hl1_area_tie_outages")
+    end
     acc = zeros(Float64, 7, n + 1)           # relmc_hl1_seq_acc[n + 1]: column r = one 56-byte record (row 1 holds the Int64 count)
     yrs = Vector{Hl1SeqYear}(undef, n_years * (n + 1))
     check(ccall((:relmc_hl1_area, LIB), Int32, (Ptr{Cvoid}, UInt64, UInt64, Int64, Int32, Int32, Int32, Int32, Ptr{Cdouble},

@@ -132,6 +132,7 @@ HL1_START_ALL_UP, HL1_START_STATIONARY = 0, 1     # RELMC_HL1_START_*
 AREA_MAX = 8                                       # RELMC_AREA_MAX
 HL1_AREA_ISOLATED, HL1_AREA_INTERCONNECTED = 0, 1  # RELMC_HL1_AREA_*
 HL1_AREA_FLOW_REFERENCE, HL1_AREA_FLOW_MAX_FLOW = 0, 1   # RELMC_HL1_AREA_FLOW_*
+HL1_TIE_MAX, HL1_TIE_DRAW_BASE = 32, 128           # RELMC_HL1_TIE_MAX, RELMC_HL1_TIE_DRAW_BASE
 
 
 class SeqOpts(C.Structure):

@@ -11,6 +11,9 @@
 using namespace relmc_host;
 
 static_assert(relmc::AREA_MAX == RELMC_AREA_MAX, "relmc_dev.h and include/relmc.h disagree on the area limit");
+static_assert(relmc::AREA_TIE_MAX == RELMC_HL1_TIE_MAX && relmc::AREA_TIE_DRAW_BASE == RELMC_HL1_TIE_DRAW_BASE,
+              "relmc_dev.h and include/relmc.h disagree on the tie limits");
+static_assert(relmc::AREA_TIE_DRAW_BASE >= relmc::NCOMPMAX, "tie draws must not share a component index with a unit");
 
 extern "C" {
 
@@ -60,6 +63,42 @@ int32_t relmc_hl1_area_load(relmc_ctx* ctx, int32_t n_areas, const int32_t* unit
     HIP_TRY(ctx, hipMemcpy(S.dcase.get(), &A, sizeof(A), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(S.load.get(), hourly_load_mw, sizeof(double) * n_areas * nhours, hipMemcpyHostToDevice));
     S.ngen = (int)ngen; S.nhours = nhours; S.n_areas = n_areas; ctx->has_hl1_area = true;
+    S.tie_from.assign(tie_from, tie_from + n_ties); S.tie_to.assign(tie_to, tie_to + n_ties);
+    S.tie_cap.assign(tie_capacity_mw, tie_capacity_mw + n_ties);
+    S.tie_outages = S.tie_fail = false;                            // a new model has no outage data
+    return RELMC_OK;
+}
+
+int32_t relmc_hl1_area_tie_outages(relmc_ctx* ctx, int32_t n_ties, const double* tie_mttf_h, const double* tie_mttr_h)
+{
+    if (!ctx) return RELMC_ERR_INVALID;
+    if (!ctx->has_hl1_area) return fail(ctx, RELMC_ERR_NO_CASE, "relmc_hl1_area_tie_outages: relmc_hl1_area_load has not been called");
+    auto& S = ctx->hl1_area;
+    if (n_ties < 0 || (!tie_mttf_h) != (!tie_mttr_h)) return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_tie_outages: bad arguments");
+    if (n_ties == 0 || !tie_mttf_h) { S.tie_outages = S.tie_fail = false; return RELMC_OK; }
+    if (n_ties > RELMC_HL1_TIE_MAX) return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_tie_outages: more than 32 ties");
+    if ((size_t)n_ties != S.tie_cap.size())
+        return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_tie_outages: " + std::to_string(n_ties) + " ties, the loaded model has " +
+                                            std::to_string(S.tie_cap.size()));
+    relmc::AreaTies TL; std::memset(&TL, 0, sizeof(TL));
+    TL.n_ties = n_ties;
+    bool any = false;
+    for (int t = 0; t < n_ties; ++t) {
+        const double f = tie_mttf_h[t];
+        if (!(f > 0.0)) return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_tie_outages: MTTF of tie " + std::to_string(t) + " not > 0 or +inf");
+        TL.from[t] = S.tie_from[t]; TL.to[t] = S.tie_to[t]; TL.cap[t] = S.tie_cap[t];
+        TL.mttf[t] = f; TL.mttr[t] = 1.0; TL.q[t] = 0.0;
+        if (std::isinf(f)) continue;                               // never fails: mttr is not read
+        const double r = tie_mttr_h[t];
+        if (!(std::isfinite(r) && r > 0.0))
+            return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_tie_outages: MTTR of tie " + std::to_string(t) + " not finite and positive");
+        TL.mttr[t] = r; TL.q[t] = r / (f + r);
+        any = true;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, S.dties.grow(1));
+    HIP_TRY(ctx, hipMemcpy(S.dties.get(), &TL, sizeof(TL), hipMemcpyHostToDevice));
+    S.tie_outages = true; S.tie_fail = any;
     return RELMC_OK;
 }
 
@@ -87,7 +126,9 @@ int32_t relmc_hl1_area(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int6
     HIP_TRY(ctx, S.part.grow((size_t)rblocks_max * 6 * rows));
     const bool inter = policy == RELMC_HL1_AREA_INTERCONNECTED;
     const int nw = (S.ngen + 31) >> 5;
-    const size_t lds = sizeof(double) * 64 * (2 * S.n_areas + 1 + (inter ? S.n_areas * S.n_areas : 0)) + sizeof(uint32_t) * nw * relmc::HL1_SEQ_WINDOW;
+    const bool ties = inter && S.tie_outages && S.tie_fail;       // the tie-outage kernel: one more mask row
+    const size_t lds = sizeof(double) * 64 * (2 * S.n_areas + 1 + (inter ? S.n_areas * S.n_areas : 0)) +
+                       sizeof(uint32_t) * (nw + (ties ? 1 : 0)) * relmc::HL1_SEQ_WINDOW;
     std::vector<double> part, stage;
     std::vector<double> sum((size_t)rows * 6, 0.0);
     double kernel_ms = 0.0;
@@ -95,8 +136,12 @@ int32_t relmc_hl1_area(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int6
         const int64_t nc = std::min(per, n_chains - c0), nrec = nc * years_per_chain;
         const int64_t rblocks = std::min<int64_t>(1024, (nrec + 255) / 256);
         (void)hipEventRecord(ctx->ev0, ctx->stream);
-        hipLaunchKernelGGL(relmc::relmc_hl1_area_kernel, dim3((unsigned)nc), dim3(64), lds, ctx->stream, S.dcase.get(), S.load.get(), seed,
-                           first_chain + (uint64_t)c0, years_per_chain, start, policy, flow, nrec, S.years.get());
+        if (ties)
+            hipLaunchKernelGGL(relmc::relmc_hl1_area_tie_kernel, dim3((unsigned)nc), dim3(64), lds, ctx->stream, S.dcase.get(), S.dties.get(),
+                               S.load.get(), seed, first_chain + (uint64_t)c0, years_per_chain, start, policy, flow, nrec, S.years.get());
+        else
+            hipLaunchKernelGGL(relmc::relmc_hl1_area_kernel, dim3((unsigned)nc), dim3(64), lds, ctx->stream, S.dcase.get(), S.load.get(), seed,
+                               first_chain + (uint64_t)c0, years_per_chain, start, policy, flow, nrec, S.years.get());
         for (int r = 0; r < rows; ++r)
             if (launch_hl1_seq_reduce(ctx, S.years.get() + (size_t)r * nrec * 3, nrec, S.part.get() + (size_t)r * rblocks * 6, rblocks) != RELMC_OK)
                 return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_area: launch failed");

@@ -173,7 +173,12 @@ struct relmc_ctx {
     struct Hl1Plan { int nhours = 0, n_elu = 0; DevBuf<relmc::PlanCase> dcase; DevBuf<double> load, years, elu, part; DevBuf<unsigned long long> hours; } hl1_plan;
     // HL1 multi-area chronology (relmc_hl1_area): its own areas / ties / load curves, grow-only per-row year records and reduction partials
     bool has_hl1_area = false;
-    struct Hl1Area { int ngen = 0, nhours = 0, n_areas = 0; DevBuf<relmc::AreaCase> dcase; DevBuf<double> load, years, part; } hl1_area;
+    // ties: the loaded ties one by one; tie_outages: relmc_hl1_area_tie_outages' data is in force (dties), tie_fail: with a finite mttf
+    struct Hl1Area {
+        int ngen = 0, nhours = 0, n_areas = 0; DevBuf<relmc::AreaCase> dcase; DevBuf<double> load, years, part;
+        std::vector<int32_t> tie_from, tie_to; std::vector<double> tie_cap;
+        bool tie_outages = false, tie_fail = false; DevBuf<relmc::AreaTies> dties;
+    } hl1_area;
     // zero-curtailment pre-screen (relmc_screen.hip): certificate tables of the case (device pointers inside tab), grow-only work buffers of a pre-pass
     struct Screen {
         relmc::ScreenTab tab = {};

@@ -245,6 +245,16 @@ struct AreaCase {
     double q[NCOMPMAX];              // mttr / (mttf + mttr), as Hl1SeqCase
     double tie[AREA_MAX * AREA_MAX]; // T[i][j] at i * n_areas + j: summed tie capacities, symmetric, zero diagonal
 };
+// The ties one by one, for relmc_hl1_area_tie_outages (AREA_TIE_MAX = RELMC_HL1_TIE_MAX: one mask word; AREA_TIE_DRAW_BASE =
+// RELMC_HL1_TIE_DRAW_BASE: tie t draws as component 128 + t).  mttf = +inf: the tie never fails (mttr and q unused, stored as 1 and 0).
+constexpr int AREA_TIE_MAX = 32;
+constexpr int AREA_TIE_DRAW_BASE = 128;
+struct AreaTies {
+    int32_t n_ties, pad;
+    int32_t from[AREA_TIE_MAX], to[AREA_TIE_MAX];            // 0-based areas
+    double cap[AREA_TIE_MAX], mttf[AREA_TIE_MAX], mttr[AREA_TIE_MAX];
+    double q[AREA_TIE_MAX];                                  // mttr / (mttf + mttr)
+};
 
 
 }  // namespace relmc

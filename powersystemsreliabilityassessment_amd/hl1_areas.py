@@ -11,11 +11,17 @@ Mirror of the reference's module AdequacyAssessmentFast:
 `demo_system()` is the system of `run_demo` (:256-277); `rts96_system()` the three-area IEEE RTS-96 as three RTS-24 fleets joined by
 the summed tie capacities of `case96.TIES`.  The units are `hl1.Generator`s; the chronology and its draws are those of
 `hl1.run_sequential_mc` (include/relmc.h), so both policies under one seed see the same fleet history.
+
+An extension the reference does not have: a `TieLine` with a finite `mttf` / `mttr` fails and repairs like a unit
+(relmc_hl1_area_tie_outages); its draws are apart from the units', so runs with and without tie outages under one seed see the same
+fleet too.  `rts96_tie_lines()` / `rts96_system(tie_outages=True)` carry the outage data of `case96.TIES`; `tie_outage_report` is the
+table of what tie unreliability costs.
 """
 from __future__ import annotations
 
 import ctypes as C
 import enum
+import math
 import time
 from dataclasses import dataclass, field
 from typing import NamedTuple
@@ -30,6 +36,8 @@ class TieLine:                        # :28-32 (1-based areas)
     from_area: int
     to_area: int
     capacity: float
+    mttf: float = math.inf            # hours, as hl1.Generator; inf: the tie never fails (the reference's tie)
+    mttr: float = math.inf
 
 
 @dataclass
@@ -90,6 +98,7 @@ class MultiAreaResult:
     system_lold: float
     computation_time: float
     year_indices: np.ndarray = field(default_factory=lambda: np.zeros((0, 0, 3)))
+    tie_unavailability: np.ndarray = field(default_factory=lambda: np.zeros(0))   # per tie, mttr / (mttf + mttr); 0: never fails
 
 
 def _augment(m, R, flow: str):
@@ -144,19 +153,36 @@ def _augment(m, R, flow: str):
             v = p
 
 
-def solve_curtailment_fast(sys: System, margins, policy, flow: str = "reference") -> np.ndarray:
+def _topology_up(sys: System, ties_up) -> list:
+    """The per-step T of include/relmc.h: from 0.0, the capacities of the ties that are UP in ascending tie order."""
+    up = np.asarray(ties_up, dtype=bool).ravel()
+    if up.size != len(sys.tie_lines):
+        raise ValueError(f"solve_curtailment_fast: {up.size} tie states for {len(sys.tie_lines)} tie lines")
+    n = len(sys.areas)
+    T = [[0.0] * n for _ in range(n)]
+    for line, u in zip(sys.tie_lines, up):
+        if u:
+            i, j = int(line.from_area) - 1, int(line.to_area) - 1
+            T[i][j] += line.capacity
+            T[j][i] += line.capacity
+    return T
+
+
+def solve_curtailment_fast(sys: System, margins, policy, flow: str = "reference", ties_up=None) -> np.ndarray:
     """Curtailment per area for one hour's margins (capacity - load per area, :73-179).  ISOLATED: the negative margins.
     INTERCONNECTED, flow="reference": the reference's augmenting-path loop, which stops at the first surplus area that cannot reach the
-    first deficit area.  flow="max_flow": every surplus area is tried, so the total curtailment is the least the ties allow."""
+    first deficit area.  flow="max_flow": every surplus area is tried, so the total curtailment is the least the ties allow.
+    ties_up: optional boolean per tie line, the ties in service this hour (default: all of them)."""
     if flow not in _FLOW:
         raise ValueError(f"solve_curtailment_fast: flow must be one of {sorted(_FLOW)}, not {flow!r}")
     m = [float(x) for x in np.asarray(margins, dtype=np.float64).ravel()]
     if len(m) != len(sys.areas):
         raise ValueError(f"solve_curtailment_fast: {len(m)} margins for {len(sys.areas)} areas")
+    T = sys.topology_matrix.tolist() if ties_up is None else _topology_up(sys, ties_up)
     if all(x >= 0 for x in m):
         return np.zeros(len(m))
     if SupportPolicy(policy) == INTERCONNECTED:
-        _augment(m, sys.topology_matrix.tolist(), flow)
+        _augment(m, T, flow)
     return np.array([-x if x < 0 else 0.0 for x in m])
 
 
@@ -189,6 +215,20 @@ def _flatten(sys: System):
     return units, cap, mttf, mttr, load, tf, tt, tc
 
 
+def _tie_outages(sys: System):
+    """Validated (mttf, mttr) of the tie lines, or (None, None) when no tie fails (every mttf = inf)."""
+    kf = np.ascontiguousarray([t.mttf for t in sys.tie_lines], dtype=np.float64)
+    kr = np.ascontiguousarray([t.mttr for t in sys.tie_lines], dtype=np.float64)
+    fails = np.isfinite(kf)
+    if np.any(np.isnan(kf)) or np.any(kf <= 0) or not (np.all(np.isfinite(kr[fails])) and np.all(kr[fails] > 0)):
+        raise ValueError("run_fast_sequential_simulation: a tie's MTTF must be > 0 (inf: it never fails), a failing tie's MTTR finite and > 0")
+    if not fails.any():
+        return None, None
+    if kf.size > _abi.HL1_TIE_MAX:
+        raise ValueError(f"run_fast_sequential_simulation: {kf.size} tie lines with outage data; {_abi.HL1_TIE_MAX} at most")
+    return kf, np.where(fails, kr, 1.0)                  # a tie that never fails: its MTTR is not read
+
+
 def run_fast_sequential_simulation(sys: System, policy, n_years: int, *, seed: int = 1, chains: int = 1, start: str = "all_up",
                                    flow: str = "reference", engine=None) -> MultiAreaResult:
     """AdequacyAssessmentII.jl:185-250 on the GPU: `chains` chronological chains of n_years // chains years each; every step takes each
@@ -207,16 +247,19 @@ def run_fast_sequential_simulation(sys: System, policy, n_years: int, *, seed: i
         raise ValueError(f"run_fast_sequential_simulation: policy must be ISOLATED or INTERCONNECTED, not {policy!r}")
     policy = SupportPolicy(policy)
     units, cap, mttf, mttr, load, tf, tt, tc = _flatten(sys)
+    kf, kr = _tie_outages(sys)
     eng = engine or api.default_engine()
     L = eng.L
     t0 = time.time()
     n = units.size
     dp, ip = _abi.c_double_p, _abi.c_int32_p
-    key = tuple(a.tobytes() for a in (units, cap, mttf, mttr, load, tf, tt, tc))
-    if getattr(eng, "_hl1_area_loaded", None) != key:       # areas, ties and loads stay on the device between calls on the same system
+    key = tuple(a.tobytes() for a in (units, cap, mttf, mttr, load, tf, tt, tc)) + ((kf.tobytes(), kr.tobytes()) if kf is not None else ())
+    if getattr(eng, "_hl1_area_loaded", None) != key:       # areas, ties, outage data and loads stay on the device between calls on the same system
         eng._check(L.relmc_hl1_area_load(eng._h, n, units.ctypes.data_as(ip), cap.ctypes.data_as(dp), mttf.ctypes.data_as(dp),
                                          mttr.ctypes.data_as(dp), load.shape[1], load.ctypes.data_as(dp), tf.size,
                                          tf.ctypes.data_as(ip), tt.ctypes.data_as(ip), tc.ctypes.data_as(dp)), "relmc_hl1_area_load")
+        if kf is not None:                                  # the load has cleared any earlier outage data
+            eng._check(L.relmc_hl1_area_tie_outages(eng._h, kf.size, kf.ctypes.data_as(dp), kr.ctypes.data_as(dp)), "relmc_hl1_area_tie_outages")
         eng._hl1_area_loaded = key
     acc = (_abi.Hl1SeqAcc * (n + 1))()
     yr = np.zeros((n_years, n + 1, 3))
@@ -229,7 +272,8 @@ def run_fast_sequential_simulation(sys: System, policy, n_years: int, *, seed: i
         lold = np.where(lolf > 0, lole / np.where(lolf > 0, lolf, 1.0), np.nan)
     return MultiAreaResult(policy, flow, [AreaResult(a.name, float(lole[i]), float(eue[i])) for i, a in enumerate(sys.areas)],
                            lolf[:n].copy(), lold[:n].copy(), float(lole[n]), float(eue[n]), float(lolf[n]), float(lold[n]),
-                           time.time() - t0, yr)
+                           time.time() - t0, yr,
+                           np.zeros(tf.size) if kf is None else np.where(np.isfinite(kf), kr / (np.where(np.isfinite(kf), kf, 1.0) + kr), 0.0))
 
 
 def comparison_report(res_iso: MultiAreaResult, res_int: MultiAreaResult) -> str:
@@ -239,6 +283,23 @@ def comparison_report(res_iso: MultiAreaResult, res_int: MultiAreaResult) -> str
     lines += ["ISOLATED        | %-10s | %10.2f  | %10.2f" % (r.area, r.lole, r.eue) for r in res_iso.results]
     lines.append(rule)
     lines += ["INTERCONNECTED  | %-10s | %10.2f  | %10.2f" % (r.area, r.lole, r.eue) for r in res_int.results]
+    return "\n".join(lines) + "\n"
+
+
+def tie_outage_report(res_perfect: MultiAreaResult, res_outage: MultiAreaResult) -> str:
+    """INTERCONNECTED with ties that never fail against INTERCONNECTED with failing ties, per area and for the system.  Under one seed both
+    runs see the same fleet history, so the differences are the cost of tie unreliability without fleet sampling noise between the runs."""
+    rule = "-" * 76
+    lines = ["", "=== TIE OUTAGES (INTERCONNECTED) ===", "Ties            | Area       | LOLE (h/yr) | EUE (MWh/yr) | LOLF (occ/yr)", rule]
+    for label, res in (("PERFECT", res_perfect), ("FAILING", res_outage)):
+        lines += ["%-15s | %-10s | %10.2f  | %11.2f  | %10.4f" % (label, r.area, r.lole, r.eue, f) for r, f in zip(res.results, res.lolf)]
+        lines.append("%-15s | %-10s | %10.2f  | %11.2f  | %10.4f" % (label, "SYSTEM", res.system_lole, res.system_eue, res.system_lolf))
+        lines.append(rule)
+    lines += ["DIFFERENCE      | %-10s | %10.2f  | %11.2f  | %10.4f" % (a.area, b.lole - a.lole, b.eue - a.eue, fb - fa)
+              for a, b, fa, fb in zip(res_perfect.results, res_outage.results, res_perfect.lolf, res_outage.lolf)]
+    lines.append("DIFFERENCE      | %-10s | %10.2f  | %11.2f  | %10.4f" % ("SYSTEM", res_outage.system_lole - res_perfect.system_lole,
+                                                                      res_outage.system_eue - res_perfect.system_eue,
+                                                                      res_outage.system_lolf - res_perfect.system_lolf))
     return "\n".join(lines) + "\n"
 
 
@@ -263,7 +324,20 @@ def rts96_ties() -> list:
     return [TieLine(i, j, c) for (i, j), c in sorted(tot.items())]
 
 
-def rts96_system() -> System:
-    """The three-area IEEE RTS-96: three RTS-24 fleets (32 units each) with the RTS-24 load curve each, joined by rts96_ties()."""
+def rts96_tie_lines(outages: bool = True) -> list:
+    """The five inter-area lines of case96.TIES one by one (107-203, 113-215, 123-217, 325-121, 318-223; the 323-325 transformer lies
+    inside area C), capacity = column 4; with `outages`, MTTF = 8760 / lambda and MTTR = the outage duration (columns 5 and 6, the
+    conventions of seqmeantime.m:21-36 that seq.py uses)."""
+    out = []
+    for fb, tb, _x, cap, lam, dur in case96.TIES:
+        i, j = sorted((fb // 100, tb // 100))
+        if i != j:
+            out.append(TieLine(i, j, cap, 8760.0 / lam, dur) if outages else TieLine(i, j, cap))
+    return out
+
+
+def rts96_system(tie_outages: bool = False) -> System:
+    """The three-area IEEE RTS-96: three RTS-24 fleets (32 units each) with the RTS-24 load curve each, joined by rts96_ties(), or with
+    `tie_outages` by the five failing lines of rts96_tie_lines()."""
     areas = [Area(k + 1, name, hl1.rts24_generators(), hl1.rts24_load().hourly_load) for k, name in enumerate(("A", "B", "C"))]
-    return System(areas, rts96_ties())
+    return System(areas, rts96_tie_lines() if tie_outages else rts96_ties())

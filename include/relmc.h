@@ -230,13 +230,18 @@ int32_t relmc_last_kernel_ms(const relmc_ctx* ctx, double* ms);
  *                        accumulators of the WHOLE database afterwards (cumulative, not the batch's increment)
  *   relmc_db_accumulate  the accumulators of the whole database again (no sampling)
  *   relmc_db_size        rows and samples held
- *   relmc_db_export      rows [first_row, first_row + n_rows) in the reference's column layout; any output may be NULL:
+ *   relmc_db_export      rows [first_row, first_row + n_rows) in the reference's column layout (RELMC_ERR_INVALID, database untouched, unless
+ *                        0 <= first_row, 0 <= n_rows and first_row + n_rows <= rows; an empty range is fine); any output may be NULL:
  *                        states[n x (ng+nl)], count[n], dns[n], flag[n] (dns > 1e-4, :270), nodal[n x nb], status[n], iters[n],
  *                        relaxed[n] (bit 0 = an island rule relaxed Pmin or decommitted units: the row counts in n_infeasible; bit 1 = the row was
  *                        certified by the pre-screen and never solved: it counts in n_screened)
  *   relmc_db_import      resume: exported rows back into an EMPTY database, same order (the table of row ids is rebuilt); the next
  *                        relmc_nsq_db_batch / relmc_nsq_run(distinct_states = 2) continues as if the run had never stopped.
- *                        opts = the solver options the rows were computed under (NULL = defaults); status / iters / relaxed may be NULL
+ *                        opts = the solver options the rows were computed under (NULL = defaults); status / iters / relaxed may be NULL.
+ *                        Every row is checked on the host before anything is copied: one row per state (a state on two rows would split its
+ *                        count and break the independence of the batch size), iters in [0, 2^23) (the row's meta word keeps it above bit 8),
+ *                        counts >= 1.  A violation returns RELMC_ERR_INVALID with relmc_last_error naming the first offending row and leaves
+ *                        the database empty and usable.
  * After an error return of relmc_nsq_db_batch on a non-empty database the counts of known rows may have advanced without their
  * samples: the database then refuses every call but relmc_db_reset (and relmc_case_load) with RELMC_ERR_INVALID. */
 typedef struct {

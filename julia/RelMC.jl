@@ -246,7 +246,8 @@ function db_export(eng::Engine, first_row::Integer, n_rows::Integer)
     return hcat(Float64.(permutedims(states)), Float64.(count), dns, Float64.(flag), permutedims(nodal))     # the reference's matrix
 end
 
-"Resume: a state_database matrix in the reference's column layout (as db_export returns it) back into the EMPTY database."
+"Resume: a state_database matrix in the reference's column layout (as db_export returns it) back into the EMPTY database.
+One row per state and counts >= 1: otherwise the call fails naming the first offending row and the database stays empty."
 function db_import(eng::Engine, db::AbstractMatrix{Float64}; mpopt::SolverOpts = mpoption())
     ncomp = eng.sys.ng + eng.sys.nl; nb = eng.sys.nb; n = size(db, 1)
     states = Matrix{UInt8}(permutedims(db[:, 1:ncomp] .!= 0)); count = Vector{Int64}(round.(Int64, db[:, ncomp + 1]))

@@ -368,6 +368,8 @@ class Engine:
         rows, _ = self.db_size()
         n = rows - first_row if n_rows is None else int(n_rows)
         nc, nb = self.case.ncomp, self.case.nb
+        if n < 0 or first_row < 0:              # no buffers for a range the library is going to refuse: its error is the answer
+            self._check(self.L.relmc_db_export(self._h, int(first_row), n, None, None, None, None, None, None, None, None), "relmc_db_export")
         out = dict(states=np.zeros((n, nc), dtype=np.uint8), count=np.zeros(n, dtype=np.int64), dns=np.zeros(n),
                    flag=np.zeros(n, dtype=np.int32), nodal=np.zeros((n, nb)), status=np.zeros(n, dtype=np.int32),
                    iters=np.zeros(n, dtype=np.int32), relaxed=np.zeros(n, dtype=np.uint8))
@@ -381,7 +383,8 @@ class Engine:
 
     def db_import(self, rows: dict, mpopt=None):
         """Resume: the rows of an earlier `db_export()` (same case) back into the EMPTY database, in the same order; `mpopt` = the solver
-        options they were computed under.  The next `nsq_db_batch` / `nsqMain(distinct_states=2)` continues the run."""
+        options they were computed under.  The next `nsq_db_batch` / `nsqMain(distinct_states=2)` continues the run.
+        One row per state, `iters` in [0, 2**23), counts >= 1: otherwise RelmcError names the first offending row and the database stays empty."""
         o = mpopt if mpopt is not None else mpoption()
         f = lambda a, dt: np.ascontiguousarray(a, dtype=dt)
         st, cnt, dns, nod = f(rows["states"], np.uint8), f(rows["count"], np.int64), f(rows["dns"], np.float64), f(rows["nodal"], np.float64)

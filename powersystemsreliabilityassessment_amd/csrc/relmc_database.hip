@@ -2,6 +2,7 @@
 // the device: outage masks sorted and run-length encoded with rocPRIM, rows in HBM behind an open-addressing table of row ids, only new
 // states evaluated, the indices as count-weighted sums over all rows (nsqMain.m:282-301, 348-349, 366-376).
 #include <chrono>
+#include <cstdio>
 #include <cstring>
 
 #include <rocprim/rocprim.hpp>
@@ -441,7 +442,7 @@ int32_t relmc_db_export(relmc_ctx* ctx, int64_t first_row, int64_t n_rows, uint8
     if (!ctx) return RELMC_ERR_INVALID;
     if (!ctx->has_case) return fail(ctx, RELMC_ERR_NO_CASE, "relmc_db_export: no case loaded");
     if (ctx->db.invalid) return fail(ctx, RELMC_ERR_INVALID, kDbInvalid);
-    if (first_row < 0 || n_rows < 0 || first_row + n_rows > ctx->db.n) return fail(ctx, RELMC_ERR_INVALID, "relmc_db_export: row range outside the database");
+    if (first_row < 0 || n_rows < 0 || first_row > ctx->db.n || n_rows > ctx->db.n - first_row) return fail(ctx, RELMC_ERR_INVALID, "relmc_db_export: row range outside the database");
     if (n_rows == 0) return RELMC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int ow = ctx->tile == 0 ? Tile24::OW : Tile96::OW;
@@ -480,16 +481,44 @@ int32_t relmc_db_import(relmc_ctx* ctx, const relmc_solver_opts* opts, int64_t n
     const int ow = ctx->tile == 0 ? Tile24::OW : Tile96::OW;
     const int ncomp = ctx->ncomp, nb = ctx->nb;
     const size_t n = (size_t)n_rows;
-    int rc = db_ensure(ctx, n_rows);
-    if (rc) return rc;
+    if (n_rows >= (int64_t)0xfffffff0ll) return fail(ctx, RELMC_ERR_UNSUPPORTED, "state database: more than 2^32 rows");
+    // every row is checked on the host before anything reaches the device: a refused import leaves the database empty and usable
     std::vector<uint32_t> keys(n * ow, 0u); std::vector<unsigned long long> cnt(n); std::vector<int32_t> meta(n);
     int64_t samples = 0;
+    char msg[160];
     for (size_t r = 0; r < n; ++r) {
         for (int k = 0; k < ncomp; ++k) if (states_host[r * ncomp + k]) keys[r * ow + (k >> 5)] |= 1u << (k & 31);
         if (count_host[r] <= 0) return fail(ctx, RELMC_ERR_INVALID, "relmc_db_import: a row with a count below 1");
+        // meta keeps the iterations in its upper 24 bits (sign bit included): anything outside [0, 2^23) would spill into them or be lost
+        const int32_t it = iters_host ? iters_host[r] : 0;
+        if (it < 0 || it >= (1 << 23)) {
+            snprintf(msg, sizeof msg, "relmc_db_import: row %lld has iters = %d, outside [0, 2^23)", (long long)r, (int)it);
+            return fail(ctx, RELMC_ERR_INVALID, msg);
+        }
         cnt[r] = (unsigned long long)count_host[r]; samples += count_host[r];
-        meta[r] = (status_host ? (status_host[r] & 3) : 0) | ((relaxed_host && (relaxed_host[r] & 1)) ? 4 : 0) | ((relaxed_host && (relaxed_host[r] & 2)) ? 8 : 0) | ((iters_host ? iters_host[r] : 0) << 8);
+        meta[r] = (status_host ? (status_host[r] & 3) : 0) | ((relaxed_host && (relaxed_host[r] & 1)) ? 4 : 0) | ((relaxed_host && (relaxed_host[r] & 2)) ? 8 : 0) | (it << 8);
     }
+    // one row per state: a state on two rows would split its count, and the row that the table finds would depend on the order of arrival.
+    // Host-side open-addressing set of row ids over the packed mask words.
+    {
+        size_t tcap = 16; while (tcap < 2 * n) tcap <<= 1;
+        std::vector<uint32_t> seen(tcap, DB_EMPTY);
+        for (size_t r = 0; r < n; ++r) {
+            const uint32_t* k = &keys[r * ow];
+            uint64_t hk = 0x9E3779B97F4A7C15ull;
+            for (int q = 0; q < ow; ++q) { hk = (hk ^ k[q]) * 0xff51afd7ed558ccdull; hk ^= hk >> 29; }
+            size_t h = (size_t)hk & (tcap - 1);
+            for (; seen[h] != DB_EMPTY; h = (h + 1) & (tcap - 1)) {
+                if (std::memcmp(&keys[(size_t)seen[h] * ow], k, sizeof(uint32_t) * ow) == 0) {
+                    snprintf(msg, sizeof msg, "relmc_db_import: row %lld repeats the state of row %lld (one row per state)", (long long)r, (long long)seen[h]);
+                    return fail(ctx, RELMC_ERR_INVALID, msg);
+                }
+            }
+            seen[h] = (uint32_t)r;
+        }
+    }
+    int rc = db_ensure(ctx, n_rows);
+    if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->db.keys.get(), keys.data(), sizeof(uint32_t) * n * ow, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->db.count.get(), cnt.data(), sizeof(unsigned long long) * n, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->db.dns.get(), dns_host, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));

@@ -1,5 +1,5 @@
 // relmc_area.hip — the HL1 multi-area chronology with tie-line transfers (GeneratingAdequacy/AdequacyAssessmentII.jl:73-250; contract in
-// include/relmc.h).  The per-row year records are summed by relmc_hl1_seq_reduce_kernel (relmc_seq.hip), one row slice at a time.
+// include/relmc.h).  The per-row year records are summed by relmc_hl1_reduce_kernel (hl1_reduce_queue, relmc_seq.hip), one row slice at a time.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -36,13 +36,7 @@ int32_t relmc_hl1_area_load(relmc_ctx* ctx, int32_t n_areas, const int32_t* unit
     if (ngen > NCOMPMAX) return fail(ctx, RELMC_ERR_UNSUPPORTED, "relmc_hl1_area_load: more than 128 units");
     A.lo[n_areas] = (int32_t)ngen;
     A.ngen = (int32_t)ngen; A.nhours = nhours; A.n_areas = n_areas;
-    for (int g = 0; g < ngen; ++g) {
-        if (!std::isfinite(capacity_mw[g])) return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_load: capacity of unit " + std::to_string(g) + " not finite");
-        if (!(std::isfinite(mttf_h[g]) && mttf_h[g] > 0.0 && std::isfinite(mttr_h[g]) && mttr_h[g] > 0.0))
-            return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_load: MTTF / MTTR of unit " + std::to_string(g) + " not finite and positive");
-        A.cap[g] = capacity_mw[g]; A.mttf[g] = mttf_h[g]; A.mttr[g] = mttr_h[g];
-        A.q[g] = mttr_h[g] / (mttf_h[g] + mttr_h[g]);
-    }
+    if (const int rc = hl1_units_fill(ctx, "relmc_hl1_area_load", (int)ngen, capacity_mw, mttf_h, mttr_h, A.cap, A.mttf, A.mttr, A.q)) return rc;
     if (const int64_t bad = first_non_finite(hourly_load_mw, (int64_t)n_areas * nhours); bad >= 0)
         return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area_load: load of area " + std::to_string(bad / nhours) + " hour " + std::to_string(bad % nhours) +
                                             " not finite");
@@ -121,9 +115,8 @@ int32_t relmc_hl1_area(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int6
     const int64_t max_rec = (int64_t)1 << 22;
     const int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_chains, max_rec / years_per_chain));
     const int64_t rec_max = per * years_per_chain;
-    const int64_t rblocks_max = std::min<int64_t>(1024, (rec_max + 255) / 256);
     HIP_TRY(ctx, S.years.grow((size_t)rec_max * 3 * rows));
-    HIP_TRY(ctx, S.part.grow((size_t)rblocks_max * 6 * rows));
+    HIP_TRY(ctx, S.part.grow((size_t)hl1_reduce_blocks(rec_max) * 6 * rows));
     const bool inter = policy == RELMC_HL1_AREA_INTERCONNECTED;
     const int nw = (S.ngen + 31) >> 5;
     const bool ties = inter && S.tie_outages && S.tie_fail;       // the tie-outage kernel: one more mask row
@@ -134,29 +127,18 @@ int32_t relmc_hl1_area(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int6
     double kernel_ms = 0.0;
     for (int64_t c0 = 0; c0 < n_chains; c0 += per) {
         const int64_t nc = std::min(per, n_chains - c0), nrec = nc * years_per_chain;
-        const int64_t rblocks = std::min<int64_t>(1024, (nrec + 255) / 256);
         (void)hipEventRecord(ctx->ev0, ctx->stream);
-        if (ties)
-            hipLaunchKernelGGL(relmc::relmc_hl1_area_tie_kernel, dim3((unsigned)nc), dim3(64), lds, ctx->stream, S.dcase.get(), S.dties.get(),
-                               S.load.get(), seed, first_chain + (uint64_t)c0, years_per_chain, start, policy, flow, nrec, S.years.get());
-        else
-            hipLaunchKernelGGL(relmc::relmc_hl1_area_kernel, dim3((unsigned)nc), dim3(64), lds, ctx->stream, S.dcase.get(), S.load.get(), seed,
-                               first_chain + (uint64_t)c0, years_per_chain, start, policy, flow, nrec, S.years.get());
-        for (int r = 0; r < rows; ++r)
-            if (launch_hl1_seq_reduce(ctx, S.years.get() + (size_t)r * nrec * 3, nrec, S.part.get() + (size_t)r * rblocks * 6, rblocks) != RELMC_OK)
-                return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_area: launch failed");
-        (void)hipEventRecord(ctx->ev1, ctx->stream);
-        part.resize((size_t)rblocks * 6 * rows);
-        HIP_TRY(ctx, hipMemcpyAsync(part.data(), S.part.get(), sizeof(double) * part.size(), hipMemcpyDeviceToHost, ctx->stream));
+        const auto kernel = ties ? relmc::relmc_hl1_area_kernel<true> : relmc::relmc_hl1_area_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)nc), dim3(64), lds, ctx->stream, S.dcase.get(), ties ? S.dties.get() : nullptr, S.load.get(), seed,
+                           first_chain + (uint64_t)c0, years_per_chain, start, policy, flow, nrec, S.years.get());
+        if (const int rc = hl1_reduce_queue(ctx, "relmc_hl1_area", S.years.get(), nrec, rows, S.part.get(), part)) return rc;
         if (years_host) {
             stage.resize((size_t)nrec * 3 * rows);
             HIP_TRY(ctx, hipMemcpyAsync(stage.data(), S.years.get(), sizeof(double) * stage.size(), hipMemcpyDeviceToHost, ctx->stream));
         }
         if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_area: synchronisation failed");
         kernel_ms += ctx->last_kernel_ms;
-        for (int r = 0; r < rows; ++r)
-            for (int64_t b = 0; b < rblocks; ++b)
-                for (int j = 0; j < 6; ++j) sum[(size_t)r * 6 + j] += part[((size_t)r * rblocks + b) * 6 + j];
+        hl1_reduce_add(part, rows, sum.data());
         if (years_host)                                            // [row][record] -> [record][row]
             for (int64_t i = 0; i < nrec; ++i)
                 for (int r = 0; r < rows; ++r) {
@@ -166,12 +148,7 @@ int32_t relmc_hl1_area(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int6
                 }
     }
     ctx->last_kernel_ms = kernel_ms;
-    for (int r = 0; r < rows; ++r) {
-        const double* s = sum.data() + (size_t)r * 6;
-        acc[r].years = n_chains * years_per_chain;
-        acc[r].sum_lole = s[0]; acc[r].sum_eue = s[1]; acc[r].sum_lolf = s[2];
-        acc[r].sum_lole2 = s[3]; acc[r].sum_eue2 = s[4]; acc[r].sum_lolf2 = s[5];
-    }
+    for (int r = 0; r < rows; ++r) hl1_acc_fill(acc + r, n_chains * years_per_chain, sum.data() + (size_t)r * 6);
     return RELMC_OK;
 }
 

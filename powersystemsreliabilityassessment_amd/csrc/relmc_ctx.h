@@ -9,8 +9,10 @@
 //   relmc_simulate.hip   mc_simulation (host-buffer pipeline), the fused nsq_accumulate, the nsqMain loop (relmc_nsq_run)
 //   relmc_database.hip   the reference's dedupe and persistent unique-state database on the device
 //   relmc_comm.hip       the path's single collective: RCCL (bound at run time) or a host-supplied all-reduce, with a wall-clock guard
-//   relmc_seq.hip        sequential track (chronology, scaled-load hours, annual indices, the seqMain loop) and the HL1 copper sheet
-//   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area); its rows are summed by relmc_seq.hip's reduction
+//   relmc_seq.hip        sequential track (chronology, scaled-load hours, annual indices, the seqMain loop), the HL1 copper sheet, the HL1
+//                        sequential chronology (relmc_hl1_seq) and the record reduction and unit check of every HL1 chronology track
+//   relmc_plan.hip       the HL1 planning model's Monte Carlo (relmc_hl1_plan)
+//   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area); its rows are summed by relmc_seq.hip's record reduction
 //   relmc_screen.hip     the zero-curtailment pre-screen (relmc_solver_opts.screen): certificate tables, pre-pass kernels, worklists
 //   relmc_debug.hip      introspection and test hooks that are not part of include/relmc.h
 #pragma once
@@ -263,8 +265,29 @@ int pipe_run(relmc_ctx* ctx, const uint8_t* states, const double* load_scale, in
 int nsq_accumulate_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t n, const relmc_solver_opts* opts, relmc_acc* acc_out, double* dns_dev);
 
 // ---- relmc_seq.hip ------------------------------------------------------------------------------------------------------------
-// relmc_hl1_seq_reduce_kernel over n records (lole, eue, lolf) into partial[blocks][6], on the context's stream (relmc_hl1_area sums its rows with it)
-int launch_hl1_seq_reduce(relmc_ctx* ctx, const double* rec, int64_t n, double* partial, int64_t blocks);
+// Host code the HL1 tracks share; `who` is the calling function's name, for the message.
+// relmc_hl1_seq_load and relmc_hl1_area_load: the per-unit rule of the chronology models (capacity finite, MTTF and MTTR finite and
+// positive); fills cap / mttf / mttr and q = mttr / (mttf + mttr)
+int hl1_units_fill(relmc_ctx* ctx, const char* who, int ngen, const double* capacity_mw, const double* mttf_h, const double* mttr_h,
+                   double* cap, double* mttf, double* mttr, double* q);
+inline int64_t hl1_reduce_blocks(int64_t n) { const int64_t b = (n + 255) / 256; return b < 1024 ? b : 1024; }   // workgroups over a slice of n records
+// relmc_hl1_seq, relmc_hl1_plan and relmc_hl1_area: the tail of a launch, after the model kernel: relmc_hl1_reduce_kernel over each of `rows` slices of n records (rec[row][n][3], fixed
+// order) into dpart[row][blocks][6], ev1 behind the last reduction, then the copy of the partials to `part` queued on the context's stream
+int hl1_reduce_queue(relmc_ctx* ctx, const char* who, const double* rec, int64_t n, int rows, double* dpart, std::vector<double>& part);
+// After finish_timing: sum[row][6] += the partials, block by block (the order is part of the results)
+inline void hl1_reduce_add(const std::vector<double>& part, int rows, double* sum)
+{
+    const size_t blocks = part.size() / 6 / (size_t)rows;
+    for (int r = 0; r < rows; ++r)
+        for (size_t b = 0; b < blocks; ++b)
+            for (int j = 0; j < 6; ++j) sum[(size_t)r * 6 + j] += part[((size_t)r * blocks + b) * 6 + j];
+}
+inline void hl1_acc_fill(relmc_hl1_seq_acc* acc, int64_t years, const double* sum)
+{
+    acc->years = years;
+    acc->sum_lole = sum[0]; acc->sum_eue = sum[1]; acc->sum_lolf = sum[2];
+    acc->sum_lole2 = sum[3]; acc->sum_eue2 = sum[4]; acc->sum_lolf2 = sum[5];
+}
 
 // ---- relmc_database.hip -------------------------------------------------------------------------------------------------------
 int db_accumulate(relmc_ctx* ctx, relmc_acc* acc_out);

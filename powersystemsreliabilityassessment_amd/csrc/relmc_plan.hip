@@ -74,11 +74,10 @@ int32_t relmc_hl1_plan(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int64
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // years go in launches of at most 2^20 (24 MB of records, 64 MB of ELU energies); a year's records never depend on the launch it is in
     const int64_t per = std::min<int64_t>(n_years, (int64_t)1 << 20);
-    const int64_t rblocks_max = std::min<int64_t>(1024, (per + 255) / 256);
     const bool want_elu = elu_energy_host && S.n_elu > 0;
     HIP_TRY(ctx, S.years.grow((size_t)per * 3));
     if (want_elu) HIP_TRY(ctx, S.elu.grow((size_t)per * S.n_elu));
-    HIP_TRY(ctx, S.part.grow((size_t)rblocks_max * 6));
+    HIP_TRY(ctx, S.part.grow((size_t)hl1_reduce_blocks(per) * 6));
     HIP_TRY(ctx, S.hours.grow((size_t)S.nhours));
     HIP_TRY(ctx, hipMemsetAsync(S.hours.get(), 0, sizeof(unsigned long long) * S.nhours, ctx->stream));
     std::vector<double> part;
@@ -86,32 +85,24 @@ int32_t relmc_hl1_plan(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int64
     double kernel_ms = 0.0;
     for (int64_t y0 = 0; y0 < n_years; y0 += per) {
         const int64_t ny = std::min(per, n_years - y0);
-        const int64_t rblocks = std::min<int64_t>(1024, (ny + 255) / 256);
         (void)hipEventRecord(ctx->ev0, ctx->stream);
         hipLaunchKernelGGL(relmc_hl1_plan_kernel, dim3((unsigned)((ny + 255) / 256)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
                            first_year + (uint64_t)y0, ny, S.years.get(), want_elu ? S.elu.get() : nullptr, S.hours.get());
-        hipLaunchKernelGGL(relmc_hl1_plan_reduce_kernel, dim3((unsigned)rblocks), dim3(256), 0, ctx->stream, S.years.get(), ny, S.part.get());
-        (void)hipEventRecord(ctx->ev1, ctx->stream);
-        if (hipGetLastError() != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_plan: launch failed");
-        part.resize((size_t)rblocks * 6);
-        HIP_TRY(ctx, hipMemcpyAsync(part.data(), S.part.get(), sizeof(double) * 6 * rblocks, hipMemcpyDeviceToHost, ctx->stream));
+        if (const int rc = hl1_reduce_queue(ctx, "relmc_hl1_plan", S.years.get(), ny, 1, S.part.get(), part)) return rc;
         if (years_host)
             HIP_TRY(ctx, hipMemcpyAsync(years_host + y0, S.years.get(), sizeof(double) * 3 * ny, hipMemcpyDeviceToHost, ctx->stream));
         if (want_elu)
             HIP_TRY(ctx, hipMemcpyAsync(elu_energy_host + y0 * S.n_elu, S.elu.get(), sizeof(double) * S.n_elu * ny, hipMemcpyDeviceToHost, ctx->stream));
         if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_plan: synchronisation failed");
         kernel_ms += ctx->last_kernel_ms;
-        for (int64_t b = 0; b < rblocks; ++b)
-            for (int j = 0; j < 6; ++j) sum[j] += part[(size_t)b * 6 + j];
+        hl1_reduce_add(part, 1, sum);
     }
     if (hour_loss_count_host) {
         static_assert(sizeof(unsigned long long) == sizeof(int64_t), "hour counts are 64-bit");
         HIP_TRY(ctx, hipMemcpy(hour_loss_count_host, S.hours.get(), sizeof(int64_t) * S.nhours, hipMemcpyDeviceToHost));
     }
     ctx->last_kernel_ms = kernel_ms;
-    acc->years = n_years;
-    acc->sum_lole = sum[0]; acc->sum_eue = sum[1]; acc->sum_lolf = sum[2];
-    acc->sum_lole2 = sum[3]; acc->sum_eue2 = sum[4]; acc->sum_lolf2 = sum[5];
+    hl1_acc_fill(acc, n_years, sum);
     return RELMC_OK;
 }
 

@@ -17,7 +17,8 @@ DEVFI void plan_unit(const PlanUnit& u, int h, uint32_t w, uint32_t exh, double&
 // One lane per year: all lanes of a wavefront step through the same hour, so the load and every unit's record are scalar loads; the
 // ELU energies and the loss flag stay in registers (ELU slots are addressed through bit masks and unrolled loops, never a run-time
 // register index).  The per-hour loss count is ballot + popcount, added by lane 0 with a 64-bit integer atomic when nonzero.
-// Records: year_out[year][3] = (loss hours, EUE, loss events), elu_out[year][n_elu] (optional).
+// Records: year_out[year][3] = (loss hours, EUE, loss events), summed by relmc_hl1_reduce_kernel (relmc_seq_kernels.h);
+// elu_out[year][n_elu] (optional).
 __global__ void __launch_bounds__(256) relmc_hl1_plan_kernel(const PlanCase* __restrict__ P, const double* __restrict__ load, uint64_t seed,
                                                              uint64_t first_year, int64_t n_years, double* __restrict__ year_out,
                                                              double* __restrict__ elu_out, unsigned long long* __restrict__ hour_count)
@@ -82,30 +83,6 @@ __global__ void __launch_bounds__(256) relmc_hl1_plan_kernel(const PlanCase* __r
         for (int e = 0; e < PLAN_MAX_ELU; ++e)
             if (e < nelu) elu_out[(size_t)i * nelu + e] = en[e];
     }
-}
-
-// Sums of relmc_hl1_seq_acc over n records (loss hours, EUE, loss events): grid-stride in a fixed order, then a fixed tree; partial[block][6]
-__global__ void __launch_bounds__(256) relmc_hl1_plan_reduce_kernel(const double* __restrict__ rec, int64_t n, double* __restrict__ partial)
-{
-    __shared__ double red[6][256];
-    const int tid = threadIdx.x;
-    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < n; i += (int64_t)gridDim.x * 256) {
-        const double l = rec[3 * i], e = rec[3 * i + 1], f = rec[3 * i + 2];
-        s[0] += l; s[1] += e; s[2] += f;
-        s[3] = __builtin_fma(l, l, s[3]); s[4] = __builtin_fma(e, e, s[4]); s[5] = __builtin_fma(f, f, s[5]);
-    }
-#pragma unroll
-    for (int j = 0; j < 6; ++j) red[j][tid] = s[j];
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (tid < off) {
-#pragma unroll
-            for (int j = 0; j < 6; ++j) red[j][tid] += red[j][tid + off];
-        }
-        __syncthreads();
-    }
-    if (tid < 6) partial[(size_t)blockIdx.x * 6 + tid] = red[tid][0];
 }
 
 }  // namespace relmc

@@ -4,6 +4,8 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <string>
+#include <vector>
 
 #include "relmc_ctx.h"
 #include "relmc_seq_kernels.h"
@@ -29,10 +31,29 @@ int seq_sample(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int n_years, 
 }
 }  // namespace
 
-int launch_hl1_seq_reduce(relmc_ctx* ctx, const double* rec, int64_t n, double* partial, int64_t blocks)
+int hl1_units_fill(relmc_ctx* ctx, const char* who, int ngen, const double* capacity_mw, const double* mttf_h, const double* mttr_h,
+                   double* cap, double* mttf, double* mttr, double* q)
 {
-    hipLaunchKernelGGL(relmc_hl1_seq_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, rec, n, partial);
-    if (hipGetLastError() != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "hl1_seq_reduce: launch failed");
+    for (int g = 0; g < ngen; ++g) {
+        if (!std::isfinite(capacity_mw[g])) return fail(ctx, RELMC_ERR_INVALID, std::string(who) + ": capacity of unit " + std::to_string(g) + " not finite");
+        if (!(std::isfinite(mttf_h[g]) && mttf_h[g] > 0.0 && std::isfinite(mttr_h[g]) && mttr_h[g] > 0.0))
+            return fail(ctx, RELMC_ERR_INVALID, std::string(who) + ": MTTF / MTTR of unit " + std::to_string(g) + " not finite and positive");
+        cap[g] = capacity_mw[g]; mttf[g] = mttf_h[g]; mttr[g] = mttr_h[g];
+        q[g] = mttr_h[g] / (mttf_h[g] + mttr_h[g]);
+    }
+    return RELMC_OK;
+}
+
+int hl1_reduce_queue(relmc_ctx* ctx, const char* who, const double* rec, int64_t n, int rows, double* dpart, std::vector<double>& part)
+{
+    const int64_t blocks = hl1_reduce_blocks(n);
+    for (int r = 0; r < rows; ++r)
+        hipLaunchKernelGGL(relmc_hl1_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, rec + (size_t)r * n * 3, n,
+                           dpart + (size_t)r * blocks * 6);
+    (void)hipEventRecord(ctx->ev1, ctx->stream);
+    if (hipGetLastError() != hipSuccess) return fail(ctx, RELMC_ERR_HIP, std::string(who) + ": launch failed");
+    part.resize((size_t)blocks * 6 * rows);
+    HIP_TRY(ctx, hipMemcpyAsync(part.data(), dpart, sizeof(double) * part.size(), hipMemcpyDeviceToHost, ctx->stream));
     return RELMC_OK;
 }
 
@@ -383,13 +404,7 @@ int32_t relmc_hl1_seq_load(relmc_ctx* ctx, int32_t ngen, const double* capacity_
     if (ngen > NCOMPMAX) return fail(ctx, RELMC_ERR_UNSUPPORTED, "relmc_hl1_seq_load: more than 128 units");
     Hl1SeqCase h; std::memset(&h, 0, sizeof(h));
     h.ngen = ngen; h.nhours = nhours;
-    for (int g = 0; g < ngen; ++g) {
-        if (!std::isfinite(capacity_mw[g])) return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_load: capacity of unit " + std::to_string(g) + " not finite");
-        if (!(std::isfinite(mttf_h[g]) && mttf_h[g] > 0.0 && std::isfinite(mttr_h[g]) && mttr_h[g] > 0.0))
-            return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_load: MTTF / MTTR of unit " + std::to_string(g) + " not finite and positive");
-        h.cap[g] = capacity_mw[g]; h.mttf[g] = mttf_h[g]; h.mttr[g] = mttr_h[g];
-        h.q[g] = mttr_h[g] / (mttf_h[g] + mttr_h[g]);
-    }
+    if (const int rc = hl1_units_fill(ctx, "relmc_hl1_seq_load", ngen, capacity_mw, mttf_h, mttr_h, h.cap, h.mttf, h.mttr, h.q)) return rc;
     if (const int64_t bad = first_non_finite(hourly_load_mw, nhours); bad >= 0)
         return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_load: load of hour " + std::to_string(bad) + " not finite");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -418,34 +433,25 @@ int32_t relmc_hl1_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64
     const int64_t max_rec = (int64_t)1 << 22;
     const int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_chains, max_rec / years_per_chain));
     const int64_t rec_max = per * years_per_chain;
-    const int64_t rblocks_max = std::min<int64_t>(1024, (rec_max + 255) / 256);
     HIP_TRY(ctx, S.years.grow((size_t)rec_max * 3));
-    HIP_TRY(ctx, S.part.grow((size_t)rblocks_max * 6));
+    HIP_TRY(ctx, S.part.grow((size_t)hl1_reduce_blocks(rec_max) * 6));
     std::vector<double> part;
     double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     double kernel_ms = 0.0;
     for (int64_t c0 = 0; c0 < n_chains; c0 += per) {
         const int64_t nc = std::min(per, n_chains - c0), nrec = nc * years_per_chain;
-        const int64_t rblocks = std::min<int64_t>(1024, (nrec + 255) / 256);
         (void)hipEventRecord(ctx->ev0, ctx->stream);
         hipLaunchKernelGGL(relmc_hl1_seq_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
                            first_chain + (uint64_t)c0, nc, years_per_chain, start, S.years.get());
-        hipLaunchKernelGGL(relmc_hl1_seq_reduce_kernel, dim3((unsigned)rblocks), dim3(256), 0, ctx->stream, S.years.get(), nrec, S.part.get());
-        (void)hipEventRecord(ctx->ev1, ctx->stream);
-        if (hipGetLastError() != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_seq: launch failed");
-        part.resize((size_t)rblocks * 6);
-        HIP_TRY(ctx, hipMemcpyAsync(part.data(), S.part.get(), sizeof(double) * 6 * rblocks, hipMemcpyDeviceToHost, ctx->stream));
+        if (const int rc = hl1_reduce_queue(ctx, "relmc_hl1_seq", S.years.get(), nrec, 1, S.part.get(), part)) return rc;
         if (years_host)
             HIP_TRY(ctx, hipMemcpyAsync(years_host + c0 * years_per_chain, S.years.get(), sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
         if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_seq: synchronisation failed");
         kernel_ms += ctx->last_kernel_ms;
-        for (int64_t b = 0; b < rblocks; ++b)
-            for (int j = 0; j < 6; ++j) sum[j] += part[(size_t)b * 6 + j];
+        hl1_reduce_add(part, 1, sum);
     }
     ctx->last_kernel_ms = kernel_ms;
-    acc->years = n_chains * years_per_chain;
-    acc->sum_lole = sum[0]; acc->sum_eue = sum[1]; acc->sum_lolf = sum[2];
-    acc->sum_lole2 = sum[3]; acc->sum_eue2 = sum[4]; acc->sum_lolf2 = sum[5];
+    hl1_acc_fill(acc, n_chains * years_per_chain, sum);
     return RELMC_OK;
 }
 

@@ -292,8 +292,9 @@ __global__ void __launch_bounds__(256) relmc_hl1_seq_kernel(const Hl1SeqCase* __
     hl1_seq_close_year(aL, aE, aF, out + (size_t)ycur * 3);
 }
 
-// Sums of relmc_hl1_seq_acc over n records (lole, eue, lolf): grid-stride in a fixed order, then a fixed tree; partial[block][6]
-__global__ void __launch_bounds__(256) relmc_hl1_seq_reduce_kernel(const double* __restrict__ rec, int64_t n, double* __restrict__ partial)
+// Sums of relmc_hl1_seq_acc over n year records (lole, eue, lolf) of any HL1 track (hl1_reduce_queue, relmc_seq.hip): grid-stride in a
+// fixed order, then a fixed tree; partial[block][6]
+__global__ void __launch_bounds__(256) relmc_hl1_reduce_kernel(const double* __restrict__ rec, int64_t n, double* __restrict__ partial)
 {
     __shared__ double red[6][256];
     const int tid = threadIdx.x;

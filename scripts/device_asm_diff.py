@@ -3,12 +3,17 @@ via `git stash`-free `git show` into a temp tree) and for the working tree, stri
     python scripts/device_asm_diff.py [unit.hip] [rev]
 Used in round 5 to show that a change to relmc_finalize_kernel left all 14 relmc_eval_kernel instantiations byte-identical.
 A defaulted template argument that one side lacks (relmc_eval_kernel's ShapeDynamic) is dropped from the mangled names, so such an instantiation
-is compared with its predecessor and not listed as one function gone and one new."""
+is compared with its predecessor and not listed as one function gone and one new.  The HL1 kernels that were renamed or became instantiations
+of a template (RENAMED) are compared with their predecessors in the same way."""
 import hashlib, os, re, shutil, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "powersystemsreliabilityassessment_amd", "csrc")
 unit = sys.argv[1] if len(sys.argv) > 1 else "relmc_core.hip"
 rev = sys.argv[2] if len(sys.argv) > 2 else "HEAD"
+AREA_ARGS = "PKNS_8AreaCaseEPKNS_8AreaTiesEPKdmmiiiilPd"
+RENAMED = {"_ZN5relmc21relmc_hl1_area_kernelEPKNS_8AreaCaseEPKdmmiiiilPd": "_ZN5relmc21relmc_hl1_area_kernelILb0EEEv" + AREA_ARGS,
+           "_ZN5relmc25relmc_hl1_area_tie_kernelE" + AREA_ARGS: "_ZN5relmc21relmc_hl1_area_kernelILb1EEEv" + AREA_ARGS,
+           "_ZN5relmc27relmc_hl1_seq_reduce_kernelEPKdlPd": "_ZN5relmc23relmc_hl1_reduce_kernelEPKdlPd"}
 
 
 def asm(csrc, out):
@@ -22,6 +27,7 @@ def funcs(path):
         m = re.match(r"^(_Z\w+):", ln)
         if m:
             cur, buf = m.group(1).replace("NS_12ShapeDynamicE", ""), []
+            cur = RENAMED.get(cur, cur)
         elif cur is not None:
             if ln.startswith(".Lfunc_end"):
                 out[cur] = buf; cur = None

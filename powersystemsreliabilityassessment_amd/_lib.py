@@ -200,6 +200,9 @@ def load():
     if hasattr(L, "relmc_debug_screen_states"):
         L.relmc_debug_screen_states.argtypes = [vp, u8p, dp, C.c_int64, u8p]
         L.relmc_debug_screen_states.restype = C.c_int32
+    if hasattr(L, "relmc_debug_stretch_len"):
+        L.relmc_debug_stretch_len.argtypes = [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int64, i32p]
+        L.relmc_debug_stretch_len.restype = C.c_int64
     if hasattr(L, "relmc_debug_set"):
         L.relmc_debug_set.argtypes = [vp, C.c_char_p, C.c_int32]
         L.relmc_debug_set.restype = C.c_int32

@@ -6,7 +6,8 @@
 //   relmc_schedule.hip   symbolic analysis of a case and the static solver schedule (host arithmetic only), the order tuner
 //   relmc_core.hip       context lifetime, relmc_case_load + order calibration, the evaluation-kernel launcher, mc_sampling, estimators
 //   relmc_retry.hip      units the primary elimination order does not converge on: further static orders, dense pivoted last resort
-//   relmc_simulate.hip   mc_simulation (host-buffer pipeline), the fused nsq_accumulate, the nsqMain loop (relmc_nsq_run)
+//   relmc_simulate.hip   mc_simulation (host-buffer pipeline), the fused nsq_accumulate
+//   relmc_nsq_run.hip    the nsqMain loop for any number of ranks (relmc_nsq_run) and its stretch-length rule
 //   relmc_database.hip   the reference's dedupe and persistent unique-state database on the device
 //   relmc_comm.hip       the path's single collective: RCCL (bound at run time) or a host-supplied all-reduce, with a wall-clock guard
 //   relmc_seq.hip        sequential track (chronology, scaled-load hours, annual indices, the seqMain loop), the HL1 copper sheet, the HL1
@@ -194,6 +195,18 @@ struct relmc_ctx {
     std::string err;
 };
 
+// The retry counters of a context at one moment.  A pass that is evaluated, cut and taken again over its used part (a stretch of relmc_nsq_run,
+// a batch of relmc_seq_run) puts them back in between, so that relmc_retry_stats and its kin do not count the discarded pass.
+struct RetryMark {
+    int64_t units, converged, dense_units, dense_converged, overflow;
+    explicit RetryMark(const relmc_ctx* c)
+        : units(c->retry_units), converged(c->retry_converged), dense_units(c->retry_dense_units), dense_converged(c->retry_dense_converged), overflow(c->retry_overflow) {}
+    void restore(relmc_ctx* c) const
+    {
+        c->retry_units = units; c->retry_converged = converged; c->retry_dense_units = dense_units; c->retry_dense_converged = dense_converged; c->retry_overflow = overflow;
+    }
+};
+
 namespace relmc_host {
 
 using namespace relmc;
@@ -263,6 +276,14 @@ void acc_add_unit(relmc_acc* acc, const FailRec& rec, double dns, int32_t meta, 
 int pipe_run(relmc_ctx* ctx, const uint8_t* states, const double* load_scale, int64_t n, const relmc_solver_opts& o, double fail_threshold,
              double* dns, double* nodal, int32_t* status, int32_t* iters);
 int nsq_accumulate_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t n, const relmc_solver_opts* opts, relmc_acc* acc_out, double* dns_dev);
+
+// ---- relmc_nsq_run.hip --------------------------------------------------------------------------------------------------------
+constexpr int64_t kStretch = 1 << 18, kStretchMaxBatch = 32768;      // samples a stretch holds at most; batches above the second are not stretched
+inline int64_t stretch_per(int64_t batch) { return kStretch / batch * batch; }      // the longest stretch in whole batches
+// Length of the stretch that follows `done` samples at `beta` (no context, no HIP); final: sized to end the run.  per: the longest allowed;
+// round: samples of one round of the fused grid, below whose multiples other stretches end (0 = do not snap: the database form)
+struct Stretch { int64_t len; bool final; };
+Stretch stretch_length(int64_t batch, int64_t done, double beta, double beta_limit, int64_t per, int64_t round);
 
 // ---- relmc_seq.hip ------------------------------------------------------------------------------------------------------------
 // Host code the HL1 tracks share; `who` is the calling function's name, for the message.

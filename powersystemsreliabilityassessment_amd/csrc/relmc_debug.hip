@@ -1,6 +1,6 @@
 // relmc_debug.hip — introspection and test hooks that are not part of include/relmc.h (bound by the Python test suite and the profiling
 // scripts through ctypes): the active schedule's shape, every Newton step through the dense pivoted solve, per-phase cycle counters and
-// per-iteration traces of the profiling builds, the diagnosis switches of a context.
+// per-iteration traces of the profiling builds, the stretch-length rule of relmc_nsq_run, the diagnosis switches of a context.
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -110,6 +110,16 @@ int32_t relmc_debug_shape(const relmc_case_desc* d, const int32_t* order_hint, i
         if (rc) return rc < 0 ? rc : -rc;
     }
     return SF_COUNT;
+}
+
+// relmc_nsq_run's stretch-length rule (stretch_length, relmc_nsq_run.hip; host only) with the library's own longest stretch for this batch:
+// the length of the stretch after `done` samples at `beta`, *final_out (optional) = 1 if it is sized to end the run; negative = bad arguments
+int64_t relmc_debug_stretch_len(int64_t batch, int64_t done, double beta, double beta_limit, int64_t round, int32_t* final_out)
+{
+    if (batch <= 0 || batch > kStretchMaxBatch || done < 0 || round < 0) return RELMC_ERR_INVALID;
+    const Stretch s = stretch_length(batch, done, beta, beta_limit, stretch_per(batch), round);
+    if (final_out) *final_out = s.final ? 1 : 0;
+    return s.len;
 }
 
 // which evaluation kernel the fused path of this context launches now: 1 = the shape-specialised instantiation, 0 = the run-time-shape one

@@ -249,7 +249,7 @@ int32_t relmc_seq_run(relmc_ctx* ctx, const relmc_seq_opts* o, relmc_seq_result*
         const int64_t lo = done + m * r / R, cnt = done + m * (r + 1) / R - lo;
         relmc_acc acc;
         // what a batch that is cut at the stopping year and taken again must not count twice (as relmc_nsq_run): second attempts, kernel time
-        const int64_t ru0 = ctx->retry_units, rcv0 = ctx->retry_converged, rd0 = ctx->retry_dense_units, rdc0 = ctx->retry_dense_converged, ro0 = ctx->retry_overflow;
+        const RetryMark mark(ctx);
         const double kernel_ms0 = kernel_ms;
         int rc = eval(lo, cnt, &acc);
         const std::string local_err = ctx->err;
@@ -290,7 +290,7 @@ int32_t relmc_seq_run(relmc_ctx* ctx, const relmc_seq_opts* o, relmc_seq_result*
             const int64_t hi = done + used;
             const int64_t cnt2 = (lo + cnt < hi ? lo + cnt : hi) - lo;
             // the discarded pass leaves no trace in the bookkeeping: kernel_seconds and relmc_retry_stats do not depend on batch_years
-            ctx->retry_units = ru0; ctx->retry_converged = rcv0; ctx->retry_dense_units = rd0; ctx->retry_dense_converged = rdc0; ctx->retry_overflow = ro0;
+            mark.restore(ctx);
             kernel_ms = kernel_ms0;
             rc = eval(lo, cnt2 > 0 ? cnt2 : 0, &acc);
         }

@@ -320,9 +320,31 @@ def nsq_run_distributed(accumulate_fn, nb: int, ncomp: int, *, seed: int = 1, be
     return idx, total, hist
 
 
+def stretch_len(batch: int, done: int, beta: float, beta_limit: float, round_samples: int = 0):
+    """Python restatement of relmc_nsq_run's stretch-length rule (stretch_length, csrc/relmc_nsq_run.hip): (samples of the stretch that follows
+    `done` samples at `beta`, whether it is sized to end the run).  round_samples: one round of the fused grid, 0 = do not snap (the database form).
+    tests/test_host.py compares it with the library's own (relmc_debug_stretch_len)."""
+    per = (1 << 18) // batch * batch
+    first = max(25600 // batch * batch, batch); least = max(1600 // batch * batch, batch)
+    ln = done // batch * batch if done > first else first
+    final = False
+    if done > 0 and beta_limit > 0 and beta < 1e6 and beta > beta_limit:
+        need = done * (beta / beta_limit) * (beta / beta_limit)       # in the library's order: (done * q) * q, not done * q ** 2 (one ulp apart)
+        target = 0.9 * need if done < 0.85 * need else 1.03 * need
+        l = math.ceil((target - done) / batch) * batch
+        ln = least if l < least else (per if l > per else int(l))
+        final = not (done < 0.85 * need)
+    ln = min(ln, per)
+    if not final and round_samples > 0:
+        snapped = (ln // round_samples) * round_samples // batch * batch
+        if ln >= 2 * round_samples and snapped >= least:
+            ln = snapped
+    return ln, final
+
+
 def nsq_run_stretches(sample_dns_fn, accumulate_fn, nb: int, ncomp: int, *, seed: int = 1, beta_limit: float = 0.0017, max_samples: int = 100000,
                       batch: int = 100, hours_per_year: float = 8760.0, rank: int | None = None, world: int | None = None, round_samples: int = 8192):
-    """Python restatement of relmc_nsq_run's CHECKPOINT STRETCHES over `world` ranks (csrc/relmc_simulate.hip): what the CPU gloo
+    """Python restatement of relmc_nsq_run's CHECKPOINT STRETCHES over `world` ranks (csrc/relmc_nsq_run.hip): what the CPU gloo
     test checks the stretch arithmetic with (which checkpoints two ranks share, the packed all-reduce, the cut-and-retake rule).
 
     sample_dns_fn(seed, first, n) -> dns of every sample of the range in sampling order; accumulate_fn(seed, first, n) -> _abi.Acc.
@@ -333,7 +355,6 @@ def nsq_run_stretches(sample_dns_fn, accumulate_fn, nb: int, ncomp: int, *, seed
     import torch.distributed as dist
     if rank is None or world is None:
         rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
-    per = (1 << 18) // batch * batch
     n_coll = 0
 
     def shared(lo0, ln, with_trip):
@@ -354,22 +375,8 @@ def nsq_run_stretches(sample_dns_fn, accumulate_fn, nb: int, ncomp: int, *, seed
         return box[:3 * ncp].reshape(-1, 3), _abi.Acc.from_arrays(ints, box[3 * ncp + ai.size:])
 
     total, done, beta, hist = _abi.Acc(), 0, float("inf"), []
-    first = max(25600 // batch * batch, batch); least = max(1600 // batch * batch, batch)
     while beta > beta_limit and done < max_samples:
-        ln = done // batch * batch if done > first else first
-        final = False
-        if done > 0 and beta_limit > 0 and beta < 1e6 and beta > beta_limit:
-            need = done * (beta / beta_limit) ** 2
-            target = 0.9 * need if done < 0.85 * need else 1.03 * need
-            l = math.ceil((target - done) / batch) * batch
-            ln = least if l < least else (per if l > per else int(l))
-            final = not (done < 0.85 * need)
-        ln = min(ln, per)
-        if not final:
-            snapped = (ln // round_samples) * round_samples // batch * batch
-            if ln >= 2 * round_samples and snapped >= least:
-                ln = snapped
-        m = min(max_samples - done, ln)
+        m = min(max_samples - done, stretch_len(batch, done, beta, beta_limit, round_samples)[0])
         trip, part = shared(done, m, True)
         run_n, run_f, run_s, run_s2 = int(total.n), int(total.n_fail), float(total.sum_dns), float(total.sum_dns2)
         used = 0

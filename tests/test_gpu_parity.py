@@ -223,6 +223,46 @@ def test_nsqmain_with_the_references_batch_of_100(engine):
     engine.db_reset()
 
 
+def test_nsqmain_stretches_equal_the_per_batch_loop(engine, case):
+    """relmc_nsq_run's two loops against each other at the reference's batch of 100, every sample solved and through the state database: the
+    stretch loop on one engine, the per-batch loop (`nsq_no_stretch`) on a second one.  Runs that end inside the first batch-sized stretch (100,
+    150: a ragged second checkpoint), at the end of the first stretch and one batch past it (25 600, 25 700), in a ragged tail (30 050), and
+    one that beta ends inside a stretch, which is cut and taken again.  Same stopping point, checkpoint count and verdict, the same integers, the
+    four histories to 1e-9 (the per-batch loop sums each batch on the device, the stretch loop on the host), and the same second attempts
+    counted: a cut stretch puts the retry counters back before it is taken again (RetryMark).  On RTS-24 with seed 7 no unit of these ranges
+    needs a second attempt, so the last comparison is of zeros there."""
+    batch, seed, hists = 100, 7, ("beta_history", "edns_history", "lole_history", "plc_history")
+    slow = api.Engine(case, device=0)
+    try:
+        slow.debug_set("nsq_no_stretch")
+        counters = lambda e: (e.retry_stats(), e.retry_dense_stats(), e.retry_overflow())
+        delta = lambda a, b: tuple(np.subtract(y, x).tolist() for x, y in zip(a, b))
+        for limit, n in ((0.0, 100), (0.0, 150), (0.0, 25_600), (0.0, 25_700), (0.0, 30_050), (0.05, 100_000)):
+            for form in (False, "database"):
+                c0, s0 = counters(engine), counters(slow)
+                a = engine.nsqMain(beta_limit=limit, max_iterations=n, samples_per_batch=batch, seed=seed, distinct_states=form)
+                b = slow.nsqMain(beta_limit=limit, max_iterations=n, samples_per_batch=batch, seed=seed, distinct_states=form)
+                da, db = delta(c0, counters(engine)), delta(s0, counters(slow))
+                k = min(len(a.beta_history), len(b.beta_history))
+                with np.errstate(invalid="ignore"):
+                    worst = [float(np.nanmax(np.abs(getattr(a, h)[:k] - getattr(b, h)[:k]) / np.maximum(np.abs(getattr(b, h)[:k]), 1e-300), initial=0.0)) for h in hists]
+                print(f"limit {limit} max {n} form {form}: stops at {a.current_iteration} / {b.current_iteration}, checkpoints {len(a.beta_history)} / "
+                      f"{len(b.beta_history)}, converged {a.converged} / {b.converged}, retry counters {da} / {db}, largest relative history differences {worst}")
+                assert (a.current_iteration, len(a.beta_history), a.converged) == (b.current_iteration, len(b.beta_history), b.converged)
+                assert len(a.beta_history) == -(-a.current_iteration // batch)
+                assert np.array_equal(a.acc.to_arrays()[0], b.acc.to_arrays()[0])
+                for h in hists:
+                    np.testing.assert_allclose(getattr(a, h), getattr(b, h), rtol=1e-9, err_msg=h)
+                assert da == db
+                if limit > 0:
+                    assert a.converged and 0 < a.current_iteration < n         # beta ended the run inside a stretch
+                else:
+                    assert a.current_iteration == n and not a.converged
+    finally:
+        slow.close()
+        engine.db_reset()
+
+
 def test_full_size_properties(engine, golden):
     """BASELINE config 2 (1e6 samples) through size-independent properties + the reference's golden run."""
     n = 1_000_000

@@ -198,6 +198,46 @@ def test_checkpoint_stretches_gloo_world2(tmp_path, oracle):
     np.testing.assert_allclose(h1[:, 2], ref["edns_history"], rtol=1e-11)
 
 
+def test_stretch_rule_is_the_python_restatements():
+    """The one stretch-length rule of relmc_nsq_run (stretch_length, through the host-only hook relmc_debug_stretch_len) against its independent
+    Python restatement dist.stretch_len -- the rule dist.nsq_run_stretches walks: the same length and the same final flag, exactly, over
+    batches either side of 1600 and 25 600 (where `least` and `first` stop being several batches), runs before / at / past the first stretch
+    and past the longest one, no prediction (beta infinite, NaN, >= 1e6, limit 0), predictions either side of the 85 % threshold between the
+    90 % and the 103 % stretch, and lengths either side of two rounds, below which a stretch is not snapped."""
+    import math
+    L = _lib.load()
+    fin = C.c_int32()
+    checked = snapped = unsnapped = finals = 0
+    for batch in (1, 7, 100, 500, 1600, 1601, 25600, 25601, 32768):
+        per, first = (1 << 18) // batch * batch, max(25600 // batch * batch, batch)
+        for limit in (0.0, 0.01, 0.0017):
+            for rnd in (0, 8192, 24576):
+                dones = {0, batch, first, first + batch, 100000 // batch * batch, per, 5_000_000 // batch * batch}
+                if rnd:                                                    # no prediction: the length is `done` in whole batches
+                    dones |= {d for d in ((2 * rnd) // batch * batch + k * batch for k in (-1, 0, 1, 2)) if d >= 0}
+                for done in sorted(dones):
+                    betas = [math.inf, math.nan, 1e6, 999999.0, 0.5, 0.02, 0.0101]
+                    if limit > 0:
+                        edge = limit / math.sqrt(0.85)                     # done / need = (limit / beta)^2 = 0.85
+                        betas += [edge * (1 - 1e-9), math.nextafter(edge, 0.0), edge, math.nextafter(edge, 1.0), edge * (1 + 1e-9)]
+                        if rnd and done:                                   # 90 % of the prediction ends two rounds, give or take a batch, after `done`
+                            betas += [limit * math.sqrt((done + 2 * rnd + k * batch) / 0.9 / done) for k in (-1, 0, 1)]
+                    for beta in betas:
+                        want, want_final = rdist.stretch_len(batch, done, beta, limit, rnd)
+                        got = L.relmc_debug_stretch_len(batch, done, beta, limit, rnd, C.byref(fin))
+                        assert (got, bool(fin.value)) == (want, want_final), (batch, done, beta, limit, rnd)
+                        assert 0 < got <= per and got % batch == 0
+                        plain = rdist.stretch_len(batch, done, beta, limit, 0)[0]
+                        checked += 1; finals += want_final
+                        if rnd and plain >= 2 * rnd:
+                            snapped += want != plain
+                        elif rnd:
+                            unsnapped += 1
+                            assert want == plain
+    assert checked > 5000 and snapped > 100 and unsnapped > 100 and finals > 100       # the grid reaches every branch of the rule
+    assert L.relmc_debug_stretch_len(0, 0, 1.0, 0.01, 0, None) < 0 and L.relmc_debug_stretch_len(32769, 0, 1.0, 0.01, 0, None) < 0
+
+
 _AR_WORKER = r"""
 import os, sys
 sys.path.insert(0, {root!r})

@@ -1,8 +1,8 @@
 """The four HL1 GPU engines at the edges of their contracts (include/relmc.h): relmc_hl1_nsq against the C oracle and exact sums,
-relmc_hl1_seq / relmc_hl1_area / relmc_hl1_plan against their host models (tests/tools/hl1_{seq,area,plan}_model.py) at the unit counts,
-year lengths, area counts, topologies, index ranges and launch splits where the kernels take paths the other tests never reach, and the
-input rule of the four load calls.  The cases are tests/tools/hl1_edge_cases.py's; tests/test_hl1_edges_host.py ties the host models to
-the reference loops on the same cases."""
+relmc_hl1_seq / relmc_hl1_area / relmc_hl1_plan against their host models (tests/tools/hl1_{seq,area,tie,plan}_model.py) at the unit
+counts, year lengths, area counts, topologies, tie counts, index ranges and launch splits where the kernels take paths the other tests
+never reach, and the input rule of the four load calls.  The cases are tests/tools/hl1_edge_cases.py's; tests/test_hl1_edges_host.py
+ties the host models to the reference loops on the same cases."""
 import ctypes as C
 import importlib.util
 import os
@@ -22,7 +22,7 @@ def _tool(name):
     return m
 
 
-E, SEQ, AREA, PLAN = (_tool(n) for n in ("hl1_edge_cases", "hl1_seq_model", "hl1_area_model", "hl1_plan_model"))
+E, SEQ, AREA, TIE, PLAN = (_tool(n) for n in ("hl1_edge_cases", "hl1_seq_model", "hl1_area_model", "hl1_tie_model", "hl1_plan_model"))
 
 dp, ip = _abi.c_double_p, _abi.c_int32_p
 POL = [(AREA.ISOLATED, AREA.REFERENCE), (AREA.INTERCONNECTED, AREA.REFERENCE), (AREA.INTERCONNECTED, AREA.MAX_FLOW)]
@@ -302,6 +302,28 @@ def test_area_eight_areas_topologies(engine, topo, policy, flow):
         _assert_records(yr, model)
         for r in range(9):
             assert acc[r].years == 16 and acc[r].sum_lole == pytest.approx(model[:, r, 0].sum(), rel=1e-12)
+
+
+@pytest.mark.parametrize("flow", [AREA.REFERENCE, AREA.MAX_FLOW])
+@pytest.mark.parametrize("start", [AREA.ALL_UP, AREA.STATIONARY])
+@pytest.mark.parametrize("ngen", [64, 65])
+@pytest.mark.parametrize("nhours", [511, 512, 513])
+def test_area_tie_slot_at_the_window_edges(engine, nhours, ngen, start, flow):
+    """The tie slot of the chronology with all 32 tie lanes busy (MTTR << 1 h, MTTF of a few hours, mttf = inf and 1e30, parallel and
+    reversed ties), with one unit slot (64 units) and two (65), on years at and around the 512-step window, 4 chains of ~2000 steps
+    (year boundaries inside 64-step groups): every record against hl1_tie_model."""
+    units, cap, mttf, mttr, loads, ties, kf, kr = E.area_tie_edges(ngen, nhours)
+    years = E.seq_years(nhours)
+    engine._check(_area_load(engine.L, engine._h, units, cap, mttf, mttr, loads, ties), "relmc_hl1_area_load")
+    kf_, kr_ = _f64(kf, kr)
+    engine._check(engine.L.relmc_hl1_area_tie_outages(engine._h, kf_.size, _ptr(kf_), _ptr(kr_)), "relmc_hl1_area_tie_outages")
+    engine._hl1_area_loaded = None
+    pol = (years, start, AREA.INTERCONNECTED, flow)
+    _, yr = _area(engine, 5, 17, 2, 4, *pol)
+    model = TIE.interval_model(17, range(2, 6), units, cap, mttf, mttr, loads, ties, kf, kr, *pol)
+    perfect = AREA.interval_model(17, range(2, 6), units, cap, mttf, mttr, loads, AREA.topology(4, ties), *pol)
+    assert model[:, 4, 0].sum() > perfect[:, 4, 0].sum() > 0      # the chains need transfers, and the outages are seen in them
+    _assert_records(yr, model)
 
 
 def test_area_two_launches(engine):

@@ -1,5 +1,6 @@
 """The HL1 host models at the edges tests/test_hl1_edges.py runs the device on (no GPU): the interval / vectorised forms against the
-literal transliterations of the reference loops (hl1_seq_model.literal_chain, hl1_area_model.literal_chain, hl1_plan_model.literal_year),
+literal transliterations of the reference loops (hl1_seq_model.literal_chain, hl1_area_model.literal_chain, hl1_tie_model.literal_chain,
+hl1_plan_model.literal_year),
 MAX_FLOW against min-cut enumeration on 7 and 8 areas and the edge topologies, and the oracle's clamped HL1 threshold against a numpy
 restatement of the contract."""
 import importlib.util
@@ -19,7 +20,7 @@ def _tool(name):
     return m
 
 
-E, SEQ, AREA, PLAN = (_tool(n) for n in ("hl1_edge_cases", "hl1_seq_model", "hl1_area_model", "hl1_plan_model"))
+E, SEQ, AREA, TIE, PLAN = (_tool(n) for n in ("hl1_edge_cases", "hl1_seq_model", "hl1_area_model", "hl1_tie_model", "hl1_plan_model"))
 
 
 def _assert_same(a, b):
@@ -51,6 +52,22 @@ def test_area_interval_form_equals_the_reference_loop_on_8_areas(topo, policy):
     b = np.concatenate([AREA.literal_chain(4, c, units, cap, mttf, mttr, loads, T, 2, AREA.STATIONARY, policy) for c in chains])
     _assert_same(a, b)
     assert a[:, 8, 0].sum() > 0
+
+
+@pytest.mark.parametrize("flow", [AREA.REFERENCE, AREA.MAX_FLOW])
+@pytest.mark.parametrize("start", [AREA.ALL_UP, AREA.STATIONARY])
+@pytest.mark.parametrize("ngen", [64, 65])
+@pytest.mark.parametrize("nhours", [511, 512, 513])
+def test_tie_interval_form_equals_the_hour_loop_at_the_window_edges(nhours, ngen, start, flow):
+    """test_hl1_edges.py's tie cases (32 ties with MTTR << 1 h, MTTF of a few hours, mttf = inf and 1e30; 64 and 65 units in 4 areas;
+    years around 512 hours): the expected values of the device test come from the hour loop as well."""
+    units, cap, mttf, mttr, loads, ties, kf, kr = E.area_tie_edges(ngen, nhours)
+    pol = (E.seq_years(nhours), start, AREA.INTERCONNECTED, flow)
+    chains = range(2, 6)
+    a = TIE.interval_model(17, chains, units, cap, mttf, mttr, loads, ties, kf, kr, *pol)
+    b = np.concatenate([TIE.literal_chain(17, c, units, cap, mttf, mttr, loads, ties, kf, kr, *pol) for c in chains])
+    _assert_same(a, b)
+    assert a[:, 4, 0].sum() > 0
 
 
 @pytest.mark.parametrize("ngen,n_elu,binding", [(1, 0, True), (2, 1, True), (3, 2, True), (10, 8, True), (10, 8, False)])

@@ -2,7 +2,8 @@
 tests/test_hl1_edges_host.py (host models against the reference loops): unit counts around the 4-unit Philox blocks, the 32-bit mask words
 and the two lanes' slots, years shorter than a 64-lane group or straddling the 512-step window, transitions far shorter than a step or far
 longer than the horizon, zero capacities, loads equal to reachable capacity sums, 8 areas on the topologies where augmenting paths are
-long, and the planning model's 8 ELU slots in week 53.  Every value is computed here; nothing is read from disk."""
+long, 32 failing ties on years around the window length, and the planning model's 8 ELU slots in week 53.  Every value is computed
+here; nothing is read from disk."""
 from __future__ import annotations
 
 import math
@@ -162,6 +163,33 @@ def topologies8():
         "two_components": [(0, 1, 25.0), (1, 2, 35.5), (2, 3, 20.0), (0, 3, 10.0), (4, 5, 40.0), (5, 6, 15.25), (6, 7, 30.0), (4, 7, 12.0)],
         "zero_ties": [(i, i + 1, 0.0) for i in range(7)] + [(0, 7, 0.0)],
     }
+
+
+def area_tie_edges(ngen, nhours):
+    """The tie slot of the chronology at its edges: seq_fleet(ngen) split over 4 areas (the second has one unit), a year of nhours hours
+    and 32 ties on the 6 area pairs (every tie lane busy; parallel ties, every second one with its endpoints reversed): some with
+    MTTR << 1 h (several transitions inside one step, empty intervals), some with an MTTF of a few hours, tie 7 with mttf = inf (no
+    cursor) and tie 12 with mttf = 1e30 (a T without an int64 image).  Area loads near each area's mean available capacity, so that the
+    small tie capacities decide about loss hours.  -> units, cap, mttf, mttr, loads[4][nhours], ties [(from, to, capacity)], kf, kr."""
+    cap, mttf, mttr, _ = seq_fleet(ngen, nhours)
+    units = [20, 1, 25, ngen - 46]
+    lo = np.concatenate([[0], np.cumsum(units)])
+    h = np.arange(nhours)
+    loads = np.zeros((4, nhours))
+    for a, level in enumerate((0.6, 0.7, 0.8, 0.85)):
+        s = slice(lo[a], lo[a + 1])
+        avail = float((cap[s] * mttf[s] / (mttf[s] + mttr[s])).sum())
+        loads[a] = avail * (level + 0.1 * np.sin(2 * np.pi * (h - 5 * a) / 24.0))
+    rng = np.random.default_rng(900 + ngen)
+    pairs = [(i, j) for i in range(4) for j in range(i + 1, 4)]
+    tcap = np.round(rng.uniform(1.0, 6.0, 32), 2)
+    ties = [pairs[t % 6][::-1 if t % 2 else 1] + (float(tcap[t]),) for t in range(32)]
+    kf = rng.uniform(30.0, 200.0, 32)
+    kr = rng.uniform(3.0, 30.0, 32)
+    kr[2::5] = rng.uniform(0.01, 0.3, kr[2::5].size)
+    kf[1::6] = rng.uniform(2.0, 6.0, kf[1::6].size)
+    kf[7], kf[12] = math.inf, 1e30
+    return units, cap, mttf, mttr, loads, ties, kf, kr
 
 
 # ---- relmc_hl1_plan --------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,7 @@
 
   (a) interval_model: hl1_area_model.interval_model with a chronology per tie.  Tie t is component 128 + t of hl1_seq_model's draws; its
       start state and transition times come from hl1_seq_model.chronology itself (one chronology, not two).  Per step T is summed from
-      0.0 over the UP ties in ascending tie order; the steps go through hl1_area_model.solve_batch grouped by tie state.
+      0.0 over the UP ties in ascending tie order; the steps in deficit go through hl1_area_model.solve_batch with their own T.
   (b) literal_chain: the reference's hour loop (`ttf -= 1; while ttf <= 0: toggle`) for units and ties alike, driven by the same draws.
   (c) joint_stationary_ties: exact stationary LOLE / EUE per row as the sum over the 2^n_ties tie states of P(state) x
       hl1_area_model.joint_stationary(..., T(state), ...).  Exact because tie states are independent of the fleets and LOLE / EUE are
@@ -72,16 +72,18 @@ def unit_down(seed, chains, mttf, mttr, start, nsteps):
 
 
 def solve_steps(m, n, ties, tdown, policy, flow):
-    """Curtailments c[S, n] of the margins m[S, n] with tdown[t, S] the ties' DOWN flags: the per-step rule of include/relmc.h."""
+    """Curtailments c[S, n] of the margins m[S, n] with tdown[t, S] the ties' DOWN flags: the per-step rule of include/relmc.h.  Steps
+    with every m_i >= 0 curtail nothing whatever the ties' states; the others go through one solve_batch call with a T per step."""
     if policy != INTERCONNECTED or len(ties) == 0:
         return AM.solve_batch(m, AM.topology(n, ties), policy, flow)
-    code = np.zeros(m.shape[0], dtype=np.int64)
-    for t in range(len(ties)):
-        code |= tdown[t].astype(np.int64) << t
     c = np.zeros_like(m)
-    for v in np.unique(code):
-        idx = np.nonzero(code == v)[0]
-        c[idx] = AM.solve_batch(m[idx], topology_up(n, ties, [not (int(v) >> t) & 1 for t in range(len(ties))]), policy, flow)
+    idx = np.nonzero((m < 0).any(1))[0]
+    T = np.zeros((idx.size, n, n))
+    for t, (i, j, cap) in enumerate(ties):                         # from 0.0 in ascending tie order; + 0.0 for a DOWN tie is exact
+        up = np.where(tdown[t][idx], 0.0, float(cap))
+        T[:, i, j] += up
+        T[:, j, i] += up
+    c[idx] = AM.solve_batch(m[idx], T, policy, flow)
     return c
 
 

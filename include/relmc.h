@@ -361,6 +361,39 @@ int32_t relmc_hl1_seq_load(relmc_ctx* ctx, int32_t ngen, const double* capacity_
 int32_t relmc_hl1_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain,
                       int32_t start, relmc_hl1_seq_acc* acc, relmc_hl1_seq_year* years_host);
 
+/* ---- loss events of the HL1 sequential chronology: how often failures occur and how long they last (seqMain.m:15-16) ---- */
+/* The chronology is relmc_hl1_seq's, word for word (model of relmc_hl1_seq_load, draws, start rules, no FMA, DOWN on steps
+ * [ceil(T_odd), ceil(T_even)), cap_avail over the UP units in ascending order, loss iff cap_avail < load[(n-1) mod H], deficit
+ * load - cap_avail): under one seed, chain c sees exactly the fleet history of chain c of relmc_hl1_seq.
+ * A loss event of a chain is a maximal run of consecutive loss steps among its steps 1 .. Y*H.  start_step n0 is 1-based along the chain,
+ * duration D the number of steps, energy E the sum of the steps' deficits, peak P the largest of them.  A run continues across a year
+ * boundary (it belongs to the year it starts in, as relmc_hl1_seq's lolf); a run that reaches step Y*H ends there and is counted as
+ * censored (it is an event like any other in every other field).  So `events` equals relmc_hl1_seq's sum_lolf and sum_dur its sum_lole
+ * exactly, and sum_energy its sum_eue up to the order of summation. */
+typedef struct {
+    int64_t chain;            /* index relative to first_chain */
+    int64_t start_step;       /* 1-based along the chain */
+    int64_t duration;         /* steps */
+    double energy_mwh, peak_mw;
+} relmc_hl1_event;
+typedef struct {
+    int64_t years, events, censored, sum_dur, sum_dur2, max_dur;            /* years = simulated years; sums and maxima over the events */
+    double sum_energy, sum_energy2, max_energy, max_peak;
+} relmc_hl1_event_acc;
+/* chains [first_chain, first_chain + n_chains), each years_per_chain consecutive years, of the model loaded by relmc_hl1_seq_load
+ * (RELMC_ERR_NO_CASE before that call); arguments are checked as relmc_hl1_seq checks them, n_chains == 0 zeroes the outputs.
+ *   dur_hist_host  optional [n_dur_bins], 1 <= n_dur_bins <= 4096 when given (else RELMC_ERR_INVALID): dur_hist_host[d - 1] = events with
+ *                  D = d for d < n_dur_bins, the last bin counts D >= n_dur_bins; overwritten with this call's counts
+ *   events_host    optional [events_cap], events_cap >= 0 (else RELMC_ERR_INVALID): the first min(acc->events, events_cap) events in
+ *                  (chain, start_step) order; acc->events is always the true count, so a caller sees that its buffer was short
+ * Every output depends on (seed, chain, start, years_per_chain, data) only: splitting a chain range into calls gives lists that concatenate
+ * (with `chain` rebased), integer fields and histograms that add exactly and maxima that combine by max; the floating-point sums are
+ * taken in a fixed order, so a repeated call is bitwise identical.  Long chain ranges go in launches of at most ~4M chain years, as in
+ * relmc_hl1_seq; relmc_last_kernel_ms covers every launch of the call (the list costs a second walk of the chains). */
+int32_t relmc_hl1_seq_events(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain,
+                             int32_t start, relmc_hl1_event_acc* acc, int32_t n_dur_bins, int64_t* dur_hist_host,
+                             int64_t events_cap, relmc_hl1_event* events_host);
+
 /* ---- HL1 multi-area chronology with tie-line transfers (AdequacyAssessmentII.jl:73-250 solve_curtailment_fast / run_fast_sequential_simulation) ---- */
 /* The chronology is relmc_hl1_seq's, word for word: draws (seed, chain, k | 0x40000000, event) with k the GLOBAL unit index (units stored
  * area-major: area 0's units, then area 1's, ...), the same start rules, steps n = 1 .. Y*H with the state carried across years, no FMA.

@@ -479,6 +479,40 @@ function run_sequential_mc(eng::Engine, capacity::Vector{Float64}, mttf::Vector{
             convergence_history=[cum[k] / k for k in 10:10:years])                  # :263-265
 end
 
+"relmc_hl1_event / relmc_hl1_event_acc (include/relmc.h); tests/test_hl1_events_host.py compares the fields with the C compiler's layout"
+struct Hl1Event
+    chain::Int64; start_step::Int64; duration::Int64; energy_mwh::Cdouble; peak_mw::Cdouble
+end
+mutable struct Hl1EventAcc
+    years::Int64; events::Int64; censored::Int64; sum_dur::Int64; sum_dur2::Int64; max_dur::Int64
+    sum_energy::Cdouble; sum_energy2::Cdouble; max_energy::Cdouble; max_peak::Cdouble
+    Hl1EventAcc() = new()
+end
+
+"""
+run_sequential_events: the loss events (maximal runs of consecutive loss hours) of run_sequential_mc's chronology, same arguments and
+same chains under one seed.  Returns LOLF, LOLD (sum of the durations / events), the mean / maximum energy, the maximum duration and
+peak, the censored count, the duration histogram (duration_bins bins, the last one counts that many hours or more) and the first
+max_events events in (chain, start_step) order.
+"""
+function run_sequential_events(eng::Engine, capacity::Vector{Float64}, mttf::Vector{Float64}, mttr::Vector{Float64},
+                               hourly_load::Vector{Float64}, years::Integer; seed::Integer=1, chains::Integer=1, start::Symbol=:all_up,
+                               duration_bins::Integer=168, max_events::Integer=0)
+    (years >= 1 && chains >= 1 && years % chains == 0) || throw(ArgumentError("years must be a positive multiple of chains"))
+    (1 <= duration_bins <= 4096 && max_events >= 0) || throw(ArgumentError("duration_bins must lie in 1:4096, max_events must not be negative"))
+    check(ccall((:relmc_hl1_seq_load, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}),
+                eng.h, length(capacity), capacity, mttf, mttr, length(hourly_load), hourly_load), eng.h, "relmc_hl1_seq_load")
+    acc = Hl1EventAcc(); hist = zeros(Int64, duration_bins); evs = Vector{Hl1Event}(undef, max_events)
+    check(ccall((:relmc_hl1_seq_events, LIB), Int32,
+                (Ptr{Cvoid}, UInt64, UInt64, Int64, Int32, Int32, Ref{Hl1EventAcc}, Int32, Ptr{Int64}, Int64, Ptr{Hl1Event}),
+                eng.h, seed, 0, chains, years ÷ chains, HL1_START[start], acc, duration_bins, hist, max_events, evs), eng.h, "relmc_hl1_seq_events")
+    n = acc.events
+    return (lolf_occ_yr=n / years, lold_hours=n > 0 ? acc.sum_dur / n : NaN, mean_energy_mwh=n > 0 ? acc.sum_energy / n : NaN,
+            lole_hours_yr=acc.sum_dur / years, eue_mwh_yr=acc.sum_energy / years,
+            max_duration=acc.max_dur, max_energy_mwh=acc.max_energy, max_peak_mw=acc.max_peak, censored=acc.censored,
+            n_events=n, duration_hist=hist, events=evs[1:min(n, max_events)])
+end
+
 # Layout of the HL1 sequential structs, kept apart from LAYOUT (tests/test_hl1_seq_host.py compares it with the C compiler's)
 const LAYOUT_HL1_SEQ = [
     ("relmc_hl1_seq_year", 24, [("lole", 0), ("eue", 8), ("lolf", 16)]),

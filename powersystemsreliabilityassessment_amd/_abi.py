@@ -128,6 +128,16 @@ class Hl1SeqAcc(C.Structure):             # relmc_hl1_seq_acc
                 ("sum_lole2", C.c_double), ("sum_eue2", C.c_double), ("sum_lolf2", C.c_double)]
 
 
+class Hl1Event(C.Structure):              # relmc_hl1_event
+    _fields_ = [("chain", C.c_int64), ("start_step", C.c_int64), ("duration", C.c_int64), ("energy_mwh", C.c_double), ("peak_mw", C.c_double)]
+
+
+class Hl1EventAcc(C.Structure):           # relmc_hl1_event_acc
+    _fields_ = [("years", C.c_int64), ("events", C.c_int64), ("censored", C.c_int64), ("sum_dur", C.c_int64), ("sum_dur2", C.c_int64),
+                ("max_dur", C.c_int64), ("sum_energy", C.c_double), ("sum_energy2", C.c_double), ("max_energy", C.c_double),
+                ("max_peak", C.c_double)]
+
+
 HL1_START_ALL_UP, HL1_START_STATIONARY = 0, 1     # RELMC_HL1_START_*
 AREA_MAX = 8                                       # RELMC_AREA_MAX
 HL1_AREA_ISOLATED, HL1_AREA_INTERCONNECTED = 0, 1  # RELMC_HL1_AREA_*

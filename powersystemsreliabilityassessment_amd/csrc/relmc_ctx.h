@@ -11,7 +11,8 @@
 //   relmc_database.hip   the reference's dedupe and persistent unique-state database on the device
 //   relmc_comm.hip       the path's single collective: RCCL (bound at run time) or a host-supplied all-reduce, with a wall-clock guard
 //   relmc_seq.hip        sequential track (chronology, scaled-load hours, annual indices, the seqMain loop), the HL1 copper sheet, the HL1
-//                        sequential chronology (relmc_hl1_seq) and the record reduction and unit check of every HL1 chronology track
+//                        sequential chronology (relmc_hl1_seq), its loss events (relmc_hl1_seq_events, kernels in relmc_event_kernels.h) and
+//                        the record reduction and unit check of every HL1 chronology track
 //   relmc_plan.hip       the HL1 planning model's Monte Carlo (relmc_hl1_plan)
 //   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area); its rows are summed by relmc_seq.hip's record reduction
 //   relmc_screen.hip     the zero-curtailment pre-screen (relmc_solver_opts.screen): certificate tables, pre-pass kernels, worklists
@@ -170,6 +171,10 @@ struct relmc_ctx {
     // HL1 sequential chronology (relmc_hl1_seq): its own fleet / load curve, grow-only per-year records and reduction partials
     bool has_hl1_seq = false;
     struct Hl1Seq { int ngen = 0, nhours = 0; DevBuf<relmc::Hl1SeqCase> dcase; DevBuf<double> load, years, part; } hl1_seq;
+    // loss events of that model (relmc_hl1_seq_events): grow-only chain records / counts / list offsets, reduction partials, histogram, list
+    struct Hl1Events {
+        DevBuf<relmc::Hl1EventRec> rec, part; DevBuf<long long> count, offset; DevBuf<unsigned long long> hist; DevBuf<relmc_hl1_event> list;
+    } hl1_events;
     // HL1 planning model (relmc_hl1_plan): its own fleet / maintenance / ELUs / load curve, grow-only per-year records, ELU energies,
     // hour loss counts and reduction partials
     bool has_hl1_plan = false;

@@ -213,6 +213,12 @@ struct Hl1SeqCase {
     double q[NCOMPMAX];              // mttr / (mttf + mttr): RELMC_HL1_START_STATIONARY starts unit k DOWN iff draw 0 < q[k]
 };
 constexpr int HL1_SEQ_WINDOW = 512;  // hours per LDS window of relmc_hl1_seq_kernel (a wavefront's masks: WINDOW x 4 x u32 = 8 KB)
+// Loss events of the HL1 sequential chronology (relmc_hl1_seq_events) in summary: one chain's, or one reduction slice's.  The integer
+// fields add exactly, the maxima combine by max.
+struct Hl1EventRec {
+    long long events, sum_dur, sum_dur2, max_dur, censored;
+    double sum_energy, sum_energy2, max_energy, max_peak;
+};
 
 // HL1 planning model (relmc_hl1_plan): maintenance windows, ELU slots and Bernoulli thresholds, mirrored by include/relmc.h's contract
 constexpr int PLAN_MAX_ELU = 8;

@@ -9,6 +9,7 @@
 
 #include "relmc_ctx.h"
 #include "relmc_seq_kernels.h"
+#include "relmc_event_kernels.h"
 
 namespace relmc_host {
 
@@ -452,6 +453,87 @@ int32_t relmc_hl1_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64
     }
     ctx->last_kernel_ms = kernel_ms;
     hl1_acc_fill(acc, n_chains * years_per_chain, sum);
+    return RELMC_OK;
+}
+
+// Loss events of the chronology above: per chunk of chains one launch for the chain records, the counts and the histogram and one for
+// their fixed-order reduction; when a list is wanted and not yet full, a scan of the counts and a second walk of the chains that writes
+// each chain's events at its offset (no per-chain cap, no atomics on the list, step order inside a chain).
+int32_t relmc_hl1_seq_events(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain, int32_t start,
+                             relmc_hl1_event_acc* acc, int32_t n_dur_bins, int64_t* dur_hist_host, int64_t events_cap, relmc_hl1_event* events_host)
+{
+    if (!ctx) return RELMC_ERR_INVALID;
+    if (!ctx->has_hl1_seq) return fail(ctx, RELMC_ERR_NO_CASE, "relmc_hl1_seq_events: relmc_hl1_seq_load has not been called");
+    if (!acc || n_chains < 0 || years_per_chain < 1 || (start != RELMC_HL1_START_ALL_UP && start != RELMC_HL1_START_STATIONARY) ||
+        (dur_hist_host && (n_dur_bins < 1 || n_dur_bins > 4096)) || events_cap < 0)
+        return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_events: bad arguments");
+    std::memset(acc, 0, sizeof(*acc));
+    if (dur_hist_host) std::memset(dur_hist_host, 0, sizeof(int64_t) * n_dur_bins);
+    if (n_chains == 0) return RELMC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto& S = ctx->hl1_seq;
+    auto& E = ctx->hl1_events;
+    // the chunks of relmc_hl1_seq: at most ~4M chain years per launch; a chain's events never depend on the launch it is in
+    const int64_t max_rec = (int64_t)1 << 22;
+    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_chains, max_rec / years_per_chain));
+    const int64_t pblocks = hl1_reduce_blocks(per);
+    HIP_TRY(ctx, E.rec.grow((size_t)per));
+    HIP_TRY(ctx, E.count.grow((size_t)per));
+    HIP_TRY(ctx, E.part.grow((size_t)pblocks));
+    unsigned long long* dhist = nullptr;
+    if (dur_hist_host) {
+        HIP_TRY(ctx, E.hist.grow((size_t)n_dur_bins));
+        dhist = E.hist.get();
+        HIP_TRY(ctx, hipMemsetAsync(dhist, 0, sizeof(unsigned long long) * n_dur_bins, ctx->stream));
+    }
+    std::vector<Hl1EventRec> part;
+    Hl1EventRec sum; std::memset(&sum, 0, sizeof(sum));
+    double kernel_ms = 0.0;
+    int64_t listed = 0;
+    for (int64_t c0 = 0; c0 < n_chains; c0 += per) {
+        const int64_t nc = std::min(per, n_chains - c0), blocks = hl1_reduce_blocks(nc);
+        const dim3 grid((unsigned)((nc + 3) / 4));
+        (void)hipEventRecord(ctx->ev0, ctx->stream);
+        hipLaunchKernelGGL(relmc_hl1_event_kernel<false>, grid, dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
+                           first_chain + (uint64_t)c0, nc, years_per_chain, start, dur_hist_host ? n_dur_bins : 0, dhist, E.rec.get(), E.count.get(),
+                           (const long long*)nullptr, c0, (int64_t)0, (relmc_hl1_event*)nullptr);
+        hipLaunchKernelGGL(relmc_hl1_event_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, E.rec.get(), nc, E.part.get());
+        (void)hipEventRecord(ctx->ev1, ctx->stream);
+        if (hipGetLastError() != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_seq_events: launch failed");
+        part.resize((size_t)blocks);
+        HIP_TRY(ctx, hipMemcpyAsync(part.data(), E.part.get(), sizeof(Hl1EventRec) * blocks, hipMemcpyDeviceToHost, ctx->stream));
+        if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_seq_events: synchronisation failed");
+        kernel_ms += ctx->last_kernel_ms;
+        int64_t chunk_events = 0;
+        for (const Hl1EventRec& p : part) {                  // block by block: the order is part of the results
+            chunk_events += p.events;
+            sum.events += p.events; sum.sum_dur += p.sum_dur; sum.sum_dur2 += p.sum_dur2; sum.censored += p.censored;
+            sum.max_dur = std::max(sum.max_dur, p.max_dur);
+            sum.sum_energy += p.sum_energy; sum.sum_energy2 += p.sum_energy2;
+            sum.max_energy = std::max(sum.max_energy, p.max_energy); sum.max_peak = std::max(sum.max_peak, p.max_peak);
+        }
+        const int64_t want = events_host ? std::min(chunk_events, events_cap - listed) : 0;
+        if (want > 0) {
+            HIP_TRY(ctx, E.offset.grow((size_t)per));
+            HIP_TRY(ctx, E.list.grow((size_t)want));
+            (void)hipEventRecord(ctx->ev0, ctx->stream);
+            hipLaunchKernelGGL(relmc_hl1_event_scan_kernel, dim3(1), dim3(256), 0, ctx->stream, E.count.get(), nc, E.offset.get());
+            hipLaunchKernelGGL(relmc_hl1_event_kernel<true>, grid, dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
+                               first_chain + (uint64_t)c0, nc, years_per_chain, start, 0, (unsigned long long*)nullptr, (Hl1EventRec*)nullptr,
+                               (long long*)nullptr, (const long long*)E.offset.get(), c0, want, E.list.get());
+            (void)hipEventRecord(ctx->ev1, ctx->stream);
+            if (hipGetLastError() != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_seq_events: launch failed");
+            HIP_TRY(ctx, hipMemcpyAsync(events_host + listed, E.list.get(), sizeof(relmc_hl1_event) * want, hipMemcpyDeviceToHost, ctx->stream));
+            if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_seq_events: synchronisation failed");
+            kernel_ms += ctx->last_kernel_ms;
+            listed += want;
+        }
+    }
+    if (dur_hist_host) HIP_TRY(ctx, hipMemcpy(dur_hist_host, dhist, sizeof(int64_t) * n_dur_bins, hipMemcpyDeviceToHost));
+    ctx->last_kernel_ms = kernel_ms;
+    acc->years = n_chains * years_per_chain;
+    acc->events = sum.events; acc->censored = sum.censored; acc->sum_dur = sum.sum_dur; acc->sum_dur2 = sum.sum_dur2; acc->max_dur = sum.max_dur;
+    acc->sum_energy = sum.sum_energy; acc->sum_energy2 = sum.sum_energy2; acc->max_energy = sum.max_energy; acc->max_peak = sum.max_peak;
     return RELMC_OK;
 }
 

@@ -8,6 +8,10 @@ Mirror of the reference's Julia module GeneratingAdequacy/PowerSystemAdequacy.jl
   run_sequential_mc(gens, load, years)         (:214-268)  chronological Monte Carlo on the GPU, with loss-of-load
                                                             frequency (relmc_hl1_seq_load / relmc_hl1_seq)
   compare_results(results)                     (:275-290)  the comparison table (text; no plot)
+  run_sequential_events(gens, load, years)     the loss events of that chronology: durations, energies, peaks, histogram, event list
+                                                            (relmc_hl1_seq_events)
+  run_frequency_duration(gens, load_mw)        generating_adequacy_frequency.jl:53-186: the frequency-and-duration recursion (host)
+  frequency_duration_report(analytical, events) LOLE / LOLF / LOLD of the two side by side (text)
 `rts24_generators()` / `rts24_load()` give the IEEE RTS-79 fleet and the 8736-hour reference load
 curve (Montecarlo_seq/anloducurve.m) whose exact answers are the published LOLE 9.3941 h/yr and
 EUE 1176.29 MWh/yr.
@@ -159,6 +163,21 @@ def run_non_sequential_mc(gens, load: LoadModel, iterations: int, *, seed: int =
 _SEQ_START = {"all_up": _abi.HL1_START_ALL_UP, "stationary": _abi.HL1_START_STATIONARY}
 
 
+def _seq_model_load(eng, gens, load: LoadModel) -> None:
+    """relmc_hl1_seq_load, unless this fleet and load curve are already on the device (they stay there between calls on the same model)."""
+    L = eng.L
+    cap = np.ascontiguousarray([g.capacity for g in gens], dtype=np.float64)
+    mttf = np.ascontiguousarray([g.mttf for g in gens], dtype=np.float64)
+    mttr = np.ascontiguousarray([g.mttr for g in gens], dtype=np.float64)
+    hl = np.ascontiguousarray(load.hourly_load, dtype=np.float64)
+    key = (cap.tobytes(), mttf.tobytes(), mttr.tobytes(), hl.tobytes())
+    if getattr(eng, "_hl1_seq_loaded", None) != key:
+        eng._check(L.relmc_hl1_seq_load(eng._h, cap.size, cap.ctypes.data_as(_abi.c_double_p), mttf.ctypes.data_as(_abi.c_double_p),
+                                        mttr.ctypes.data_as(_abi.c_double_p), hl.size, hl.ctypes.data_as(_abi.c_double_p)),
+                   "relmc_hl1_seq_load")
+        eng._hl1_seq_loaded = key
+
+
 def run_sequential_mc(gens, load: LoadModel, years: int, *, seed: int = 1, chains: int = 1, start: str = "all_up",
                       engine=None) -> SequentialReliabilityResult:
     """PowerSystemAdequacy.jl:214-268 on the GPU: `chains` independent chronological chains of years // chains consecutive years each
@@ -174,16 +193,7 @@ def run_sequential_mc(gens, load: LoadModel, years: int, *, seed: int = 1, chain
     eng = engine or api.default_engine()
     L = eng.L
     t0 = time.time()
-    cap = np.ascontiguousarray([g.capacity for g in gens], dtype=np.float64)
-    mttf = np.ascontiguousarray([g.mttf for g in gens], dtype=np.float64)
-    mttr = np.ascontiguousarray([g.mttr for g in gens], dtype=np.float64)
-    hl = np.ascontiguousarray(load.hourly_load, dtype=np.float64)
-    key = (cap.tobytes(), mttf.tobytes(), mttr.tobytes(), hl.tobytes())
-    if getattr(eng, "_hl1_seq_loaded", None) != key:       # fleet and load curve stay on the device between calls on the same model
-        eng._check(L.relmc_hl1_seq_load(eng._h, cap.size, cap.ctypes.data_as(_abi.c_double_p), mttf.ctypes.data_as(_abi.c_double_p),
-                                        mttr.ctypes.data_as(_abi.c_double_p), hl.size, hl.ctypes.data_as(_abi.c_double_p)),
-                   "relmc_hl1_seq_load")
-        eng._hl1_seq_loaded = key
+    _seq_model_load(eng, gens, load)
     acc = _abi.Hl1SeqAcc()
     yr = np.zeros((years, 3))
     eng._check(L.relmc_hl1_seq(eng._h, int(seed), 0, chains, years // chains, _SEQ_START[start], C.byref(acc),
@@ -203,6 +213,128 @@ def compare_results(results) -> str:
              "%-20s | %-10s | %-10s | %-10s" % ("Method", "LOLE(h/yr)", "EUE(MWh)", "Time(s)"), "-" * 60]
     lines += ["%-20s | %-10.4f | %-10.2f | %-10.4f" % (r.method, r.lole_hours_yr, r.eue_mwh_yr, r.computation_time) for r in results]
     lines.append("-" * 60)
+    return "\n".join(lines) + "\n"
+
+
+EVENT_DTYPE = np.dtype(_abi.Hl1Event)     # the structured view of relmc_hl1_event: chain, start_step, duration, energy_mwh, peak_mw
+
+
+@dataclass
+class LossEventResult:
+    """run_sequential_events' result.  A loss event is a maximal run of consecutive loss hours of a chain (it may cross a year boundary;
+    one that is still open at the chain's last hour ends there and counts as censored)."""
+    method: str
+    years: int
+    n_events: int
+    lole_hours_yr: float              # sum of the durations / years (= run_sequential_mc's LOLE)
+    eue_mwh_yr: float                 # sum of the energies / years
+    lolf_occ_yr: float                # events per year (= run_sequential_mc's LOLF)
+    lold_hours: float                 # hours per event, sum of the durations / events (NaN without an event)
+    mean_energy_mwh: float            # MWh per event (NaN without an event)
+    max_duration: int
+    max_energy_mwh: float
+    max_peak_mw: float
+    censored: int
+    computation_time: float
+    duration_hist: np.ndarray = field(default_factory=lambda: np.zeros(0, dtype=np.int64))   # [d - 1] = events of d hours, last bin: that long or longer
+    events: np.ndarray = field(default_factory=lambda: np.zeros(0, dtype=EVENT_DTYPE))       # the first max_events events, (chain, start_step) order
+
+    def duration_quantile(self, p: float) -> float:
+        """Smallest duration d (hours) with P(D <= d) >= p, read off the histogram; NaN if it falls into the overflow bin (or there is no event)."""
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"duration_quantile: p must lie in [0, 1], not {p}")
+        total = int(self.duration_hist.sum())
+        if total == 0:
+            return float("nan")
+        d = int(np.searchsorted(np.cumsum(self.duration_hist), p * total, side="left"))      # 0-based bin
+        return float("nan") if d >= self.duration_hist.size - 1 else float(max(d, 0) + 1)
+
+
+def run_sequential_events(gens, load: LoadModel, years: int, *, seed: int = 1, chains: int = 1, start: str = "all_up",
+                          duration_bins: int = 168, max_events: int = 0, engine=None) -> LossEventResult:
+    """The loss events of run_sequential_mc's chronology (same arguments, same chains under the same seed): how often interruptions
+    occur, how long they last, their energy and peak.  duration_hist has duration_bins bins (the last one counts that many hours or
+    more); `events` holds the first max_events events."""
+    from . import api
+    years, chains, duration_bins, max_events = int(years), int(chains), int(duration_bins), int(max_events)
+    if years < 1 or chains < 1 or years % chains:
+        raise ValueError(f"run_sequential_events: years ({years}) must be a positive multiple of chains ({chains})")
+    if start not in _SEQ_START:
+        raise ValueError(f"run_sequential_events: start must be one of {sorted(_SEQ_START)}, not {start!r}")
+    if not 1 <= duration_bins <= 4096 or max_events < 0:
+        raise ValueError("run_sequential_events: duration_bins must lie in [1, 4096] and max_events must not be negative")
+    eng = engine or api.default_engine()
+    t0 = time.time()
+    _seq_model_load(eng, gens, load)
+    acc = _abi.Hl1EventAcc()
+    hist = np.zeros(duration_bins, dtype=np.int64)
+    ev = np.zeros(max_events, dtype=EVENT_DTYPE)
+    eng._check(eng.L.relmc_hl1_seq_events(eng._h, int(seed), 0, chains, years // chains, _SEQ_START[start], C.byref(acc), duration_bins,
+                                          hist.ctypes.data_as(_abi.c_int64_p), max_events,
+                                          ev.ctypes.data_as(C.POINTER(_abi.Hl1Event)) if max_events else None), "relmc_hl1_seq_events")
+    n = acc.events
+    nan = float("nan")
+    return LossEventResult("Sequential MC events", years, n, acc.sum_dur / years, acc.sum_energy / years, n / years,
+                           acc.sum_dur / n if n else nan, acc.sum_energy / n if n else nan, acc.max_dur, acc.max_energy, acc.max_peak,
+                           acc.censored, time.time() - t0, hist, ev[:min(n, max_events)])
+
+
+@dataclass
+class FrequencyDurationResult:
+    """run_frequency_duration's result: the indices at one load level and the cumulative table (P and F of outage >= level)."""
+    method: str
+    lole_hours_yr: float
+    lolf_occ_yr: float
+    lold_hours: float                 # LOLE / LOLF (NaN when LOLF is 0)
+    computation_time: float
+    levels: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    cum_prob: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    cum_freq: np.ndarray = field(default_factory=lambda: np.zeros(0))
+
+
+def run_frequency_duration(gens, load_mw: float, step_size: float = 1.0) -> FrequencyDurationResult:
+    """The frequency-and-duration recursion of generating_adequacy_frequency.jl (recursion :110-128, boundary rule :76-98, evaluation
+    :155-186) at one load level, without the printing.  Per unit lambda = 8760 / mttf and mu = 8760 / mttr per year, q = lambda / (lambda + mu),
+    p = 1 - q, and over the outage levels X = 0, step, 2 step, ...:
+        P_new(X) = p P(X) + q P(X - C)
+        F_new(X) = p F(X) + q F(X - C) + lambda p (P(X - C) - P(X))
+    with P = 1, F = 0 below level 0 and P = F = 0 above the largest outage.  LOLE = 8760 P, LOLF = F and LOLD = LOLE / LOLF at the first
+    level above the reserve (installed capacity - load).  The reference fixes the step at 1 MW; here a capacity that is not a multiple of
+    step_size raises ValueError.
+    This is the continuous-time answer.  The chronology of run_sequential_mc / run_sequential_events samples the fleet at integer hours:
+    an outage that contains no integer hour is never seen and two events less than an hour apart merge, so its LOLF lies somewhat below
+    this one (tests/tools/hl1_seq_model.small_fleet_stationary gives the exact sampled-chain frequency of a small fleet)."""
+    t0 = time.time()
+    if not step_size > 0:
+        raise ValueError("run_frequency_duration: step_size must be positive")
+    P, F = np.array([1.0]), np.array([0.0])
+    installed = 0.0
+    for g in gens:
+        c = int(round(g.capacity / step_size))
+        if c < 0 or abs(g.capacity - c * step_size) > 1e-9 * max(1.0, abs(g.capacity)):
+            raise ValueError(f"run_frequency_duration: capacity {g.capacity} MW of unit {g.id} is not a multiple of the step {step_size} MW")
+        lam, mu = 8760.0 / g.mttf, 8760.0 / g.mttr
+        q = lam / (lam + mu)
+        p = 1.0 - q
+        P0, F0 = np.concatenate([P, np.zeros(c)]), np.concatenate([F, np.zeros(c)])       # old P(X), F(X): 0 above the old maximum
+        Pc, Fc = np.concatenate([np.ones(c), P]), np.concatenate([np.zeros(c), F])        # old P(X - C), F(X - C): 1 and 0 below level 0
+        P, F = p * P0 + q * Pc, p * F0 + q * Fc + lam * p * (Pc - P0)
+        installed += g.capacity
+    levels = np.arange(P.size) * step_size
+    reserve = installed - float(load_mw)
+    idx = int(np.searchsorted(levels, reserve, side="right"))      # first level > reserve
+    lole, lolf = (8760.0 * float(P[idx]), float(F[idx])) if idx < P.size else (0.0, 0.0)
+    return FrequencyDurationResult("Frequency & Duration", lole, lolf, lole / lolf if lolf > 0 else float("nan"), time.time() - t0,
+                                   levels, P, F)
+
+
+def frequency_duration_report(analytical: FrequencyDurationResult, events: LossEventResult) -> str:
+    """LOLE / LOLF / LOLD of the analytic recursion and of the chronology's events side by side, in compare_results' style."""
+    rule = "=" * 42
+    lines = [rule, "     FREQUENCY & DURATION SUMMARY", rule,
+             "%-20s | %-10s | %-12s | %-10s" % ("Method", "LOLE(h/yr)", "LOLF(occ/yr)", "LOLD(h)"), "-" * 62]
+    lines += ["%-20s | %-10.4f | %-12.4f | %-10.4f" % (r.method, r.lole_hours_yr, r.lolf_occ_yr, r.lold_hours) for r in (analytical, events)]
+    lines.append("-" * 62)
     return "\n".join(lines) + "\n"
 
 

@@ -154,6 +154,13 @@ DEVFI void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uin
 // outage mask of the scenario (bit k = component k failed), kept in LDS behind the workspace
 DEVFI bool outbit(const uint32_t* ob, int k) { return (ob[k >> 5] >> (k & 31)) & 1u; }
 
+// a - b c with the product rounded on its own, whatever the contraction mode of the caller: the form the injection bounds are compared in
+DEVFI double sub_prod(double a, double b, double c)
+{
+#pragma clang fp contract(off)
+    return a - b * c;
+}
+
 struct __attribute__((aligned(16))) d2 { double x, y; };
 DEVFI d2 ld2(const double* p) { return *reinterpret_cast<const d2*>(p); }
 DEVFI void st2(double* p, double x, double y) { d2 v; v.x = x; v.y = y; *reinterpret_cast<d2*>(p) = v; }

@@ -300,8 +300,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
         bool infeas = false, singular = false, iterating = false;
         uint32_t lozero = 0;                 // bit s: lower bound of injection slot s relaxed to 0 (island rules 3, 4)
 #define ISC(s) ((RW * (s) + rlane >= ng) ? lscale : 1.0)      /* virtual generators (loads) scale with the hourly factor */
-#define ILO(s) (((lozero >> (s)) & 1u) ? 0.0 : C.i_tab[RW * (s) + rlane][1] * ISC(s))
-#define ILOV(s, lo_) (((lozero >> (s)) & 1u) ? 0.0 : (lo_) * ISC(s))      /* the same from a bound already loaded */
+#define ILOV(s, lo_) (((lozero >> (s)) & 1u) ? 0.0 : (lo_) * ISC(s))      /* lower bound of injection slot s from its table value lo_ */
 #pragma unroll
         for (int s = 0; s < LS; ++s) { LFv[s] = 0; LGv[s] = 0; lzp[s] = 1; lzm[s] = 1; lmup[s] = 1; lmum[s] = 1; cBv[s] = 0; }
 #pragma unroll
@@ -365,12 +364,28 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
             RELOAD_FENCE();
 
             PT_IMARK(1)
+            // ===== the table words of status -> model and of the island rules, requested as ONE batch behind one wait: the outage-mask word
+            // of every line and injection slot of this lane and every injection slot's {upper bound, lower bound, island lower-bound term}.
+            // The code up to the start point runs on them from registers (the interior-point state is not live yet); the fence at the top of
+            // the main loop ends their lives, the loop re-reads what it needs.
+            uint32_t ow_l[LS], ow_i[IS];
+            double t_hi[IS], t_lo[IS], t_isl[IS];
+#pragma unroll
+            for (int s = 0; s < LS; ++s) ow_l[s] = OB[((linfo[s] >> 24) & LF_EXISTS) ? (ng + RW * s + rlane) >> 5 : 0];
+#pragma unroll
+            for (int s = 0; s < IS; ++s) ow_i[s] = OB[((iinfo[s] >> 8) & 0xff) == IK_REAL ? (RW * s + rlane) >> 5 : 0];
+#pragma unroll
+            for (int s = 0; s < IS; ++s) {
+                const double* const e = C.i_tab[RW * s + rlane];
+                const d2 hl = ld2(e);        // (not the wide tile's register copies: conditions on those are loop invariant and would be kept as lane masks)
+                t_hi[s] = hl.x; t_lo[s] = hl.y; t_isl[s] = e[3];
+            }
             // ===== mc_simulation.m:32-37: component status -> model ==========================
 #pragma unroll
             for (int s = 0; s < LS; ++s) {
                 const int l = RW * s + rlane;
                 const uint32_t fl = linfo[s] >> 24;
-                const bool on = (fl & LF_EXISTS) && !outbit(OB, ng + l);
+                const bool on = (fl & LF_EXISTS) && !((ow_l[s] >> ((ng + l) & 31)) & 1u);
                 if (on) sf |= 1u << s;
                 if (on && (fl & LF_LIMITED)) sf |= 1u << (3 + s);
             }
@@ -378,7 +393,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
             for (int s = 0; s < IS; ++s) {
                 const int j = RW * s + rlane;
                 const uint32_t kind = (iinfo[s] >> 8) & 0xff;
-                if (kind == IK_VIRTUAL || (kind == IK_REAL && !outbit(OB, j))) sf |= 1u << (6 + s);
+                if (kind == IK_VIRTUAL || (kind == IK_REAL && !((ow_i[s] >> (j & 31)) & 1u))) sf |= 1u << (6 + s);
             }
             // lines out in this scenario?  If not (95 % of the RTS-24 scenarios) the network is one island and the
             // reachability sweeps are skipped; the island rules still run on it.
@@ -389,85 +404,112 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
 
             PT_IMARK(2)
             // ===== topology: isolated buses, islands, island rules (DESIGN.md "island policy") ==========
+            // island rules 2-5 on the in-service injections of one island (inI[s]: slot s of this lane is in it); true = the island's balance
+            // rows are dependent (rule 5).  The row's counts travel in ONE integer all-reduce beside the sum of the lower bounds: injections,
+            // loads, units, and the free injections counted with no bound relaxed -- which is the count unless rule 3 or 4 relaxes bounds
+            // (the bits of `lozero` set by earlier islands belong to other injections), and only then is it taken again.
+            auto island_rules = [&](bool (&inI)[IS]) -> bool {
+                uint32_t cnt = 0; double losum = 0.0;
+#pragma unroll
+                for (int s = 0; s < IS; ++s) {
+                    if (inI[s]) {
+                        cnt += 1u;
+                        if (((iinfo[s] >> 8) & 0xff) == IK_VIRTUAL) cnt += 1u << 8; else if (t_hi[s] > 0.0) cnt += 1u << 16;
+                        if (sub_prod(t_hi[s], t_lo[s], ISC(s)) > 0.0) cnt += 1u << 24;
+                        losum += t_isl[s] * ISC(s);
+                    }
+                }
+                cnt = row_add<RW>(cnt); losum = row_sum<RW>(losum);
+                const uint32_t n_inj = cnt & 0xff, n_load = (cnt >> 8) & 0xff, n_gen = (cnt >> 16) & 0xff;
+                uint32_t nfree = cnt >> 24;
+                bool relaxed = false;
+                if (n_inj && !n_load) {                  // rule 2: no load -> decommit the island's units
+#pragma unroll
+                    for (int s = 0; s < IS; ++s) if (inI[s]) { sf &= ~(1u << (6 + s)); inI[s] = false; }
+                    infeas = true;
+                    nfree = 0;
+                } else if (n_load && !n_gen) {           // rule 3: no generation -> all load shed (p fixed 0)
+#pragma unroll
+                    for (int s = 0; s < IS; ++s) if (inI[s] && ((iinfo[s] >> 8) & 0xff) == IK_VIRTUAL) lozero |= 1u << s;
+                    relaxed = true;
+                } else if (losum > 1e-9) {               // rule 4: over-generation -> relax Pmin
+#pragma unroll
+                    for (int s = 0; s < IS; ++s) if (inI[s] && ((iinfo[s] >> 8) & 0xff) == IK_REAL) lozero |= 1u << s;
+                    infeas = true;
+                    relaxed = true;
+                }
+                if (relaxed) {
+                    nfree = 0;
+#pragma unroll
+                    for (int s = 0; s < IS; ++s) if (inI[s] && t_hi[s] - ILOV(s, t_lo[s]) > 0.0) nfree += 1u;
+                    nfree = row_add<RW>(nfree);
+                }
+                return nfree == 0;
+            };
             if constexpr (RW == 16) {
                 // 16-lane tile: bus sets are 32-bit masks in registers
                 uint32_t pinned = 0, dropped = 0;
-                uint32_t adjm[BS];
-                bool iso = false;
+                if (!__any(any_lout)) {
+                    // no row of the wavefront has a line out (95 % of the RTS-24 scenarios have none): every row's network is the one island
+                    // of the base case, no bus is isolated, and rule 1 pins its highest bus.  A row computes here what the general code
+                    // below computes for a row without a line outage.
+                    const uint32_t R = C.exist_mask;
+                    const int pin = 31 - __clz((int)R);
+                    bool inI[IS];
 #pragma unroll
-                for (int t = 0; t < BS; ++t) {
-                    const int i = vb[t];
-                    uint32_t adj = 0;
-                    if (i < nb && any_lout) {           // without a line outage no bus is isolated and the sweeps below are skipped
-                        const int nlb = C.b_nline[i];
-                        for (int e = 0; e < nlb; ++e) {
-                            const uint32_t ent = C.b_line[i][e];
-                            const int l = ent & 0x7f;
-                            if (!outbit(OB, ng + l)) {
-                                const uint32_t inf = C.l_info[l];
-                                adj |= 1u << ((ent & 0x80) ? (inf & 0xff) : ((inf >> 8) & 0xff));
-                            }
-                        }
-                        iso = iso || adj == 0;
-                    }
-                    adjm[t] = adj;
-                }
-                // a bus without any in-service branch makes MATPOWER's KKT matrix exactly singular; the
-                // reference consumes the start point (mc_simulation.m:41,54)
-                singular = (a.policy == 0) && row_any<RW>(iso, lane);
-                if (!singular) {
-                    uint32_t remaining = C.exist_mask;
-                    for (int guard = 0; guard < NBT; ++guard) {
-                        const bool more = remaining != 0;
-                        if (!__any(more)) break;
-                        if (more) {
-                            uint32_t R = any_lout ? 1u << (__ffs((int)remaining) - 1) : remaining;
-                            for (int sweep = 0; sweep < NBT; ++sweep) {
-                                if (!__any(any_lout)) break;
-                                uint32_t c = 0;
+                    for (int s = 0; s < IS; ++s) inI[s] = I_ON(s) && ((R >> (iinfo[s] & 0xff)) & 1u);
+                    if (island_rules(inI)) dropped = 1u << pin;      // rule 5: dependent balance rows
+                    pinned = 1u << pin;
+                } else {
+                    uint32_t adjm[BS];
+                    bool iso = false;
 #pragma unroll
-                                for (int t = 0; t < BS; ++t) if (vb[t] < nb && ((R >> vb[t]) & 1u)) c |= adjm[t];
-                                const uint32_t Rn = R | row_or<RW>(c);
-                                const bool ch = Rn != R;
-                                R = Rn;
-                                if (!__any(ch)) break;
-                            }
-                            // rule 1: the island's angle reference is its bus that is eliminated last =
-                            // highest internal number (the host puts the reference bus at nb-1)
-                            const int pin = 31 - __clz((int)R);
-                            uint32_t cnt = 0; double losum = 0.0; bool inI[IS];
-#pragma unroll
-                            for (int s = 0; s < IS; ++s) {
-                                const int j = RW * s + rlane;
-                                const uint32_t kind = (iinfo[s] >> 8) & 0xff;
-                                inI[s] = I_ON(s) && ((R >> (iinfo[s] & 0xff)) & 1u);
-                                if (inI[s]) {
-                                    cnt += 1u;
-                                    if (kind == IK_VIRTUAL) cnt += 1u << 8; else if (C.i_tab[j][0] > 0.0) cnt += 1u << 16;
-                                    losum += C.i_tab[j][3] * ISC(s);
+                    for (int t = 0; t < BS; ++t) {
+                        const int i = vb[t];
+                        uint32_t adj = 0;
+                        if (i < nb && any_lout) {           // without a line outage no bus is isolated and the sweeps below leave the row's set as it is
+                            const int nlb = C.b_nline[i];
+                            for (int e = 0; e < nlb; ++e) {
+                                const uint32_t ent = C.b_line[i][e];
+                                const int l = ent & 0x7f;
+                                if (!outbit(OB, ng + l)) {
+                                    const uint32_t inf = C.l_info[l];
+                                    adj |= 1u << ((ent & 0x80) ? (inf & 0xff) : ((inf >> 8) & 0xff));
                                 }
                             }
-                            cnt = row_add<RW>(cnt); losum = row_sum<RW>(losum);
-                            const uint32_t n_inj = cnt & 0xff, n_load = (cnt >> 8) & 0xff, n_gen = cnt >> 16;
-                            if (n_inj && !n_load) {                  // rule 2: no load -> decommit the island's units
+                            iso = iso || adj == 0;
+                        }
+                        adjm[t] = adj;
+                    }
+                    // a bus without any in-service branch makes MATPOWER's KKT matrix exactly singular; the
+                    // reference consumes the start point (mc_simulation.m:41,54)
+                    singular = (a.policy == 0) && row_any<RW>(iso, lane);
+                    if (!singular) {
+                        uint32_t remaining = C.exist_mask;
+                        for (int guard = 0; guard < NBT; ++guard) {
+                            const bool more = remaining != 0;
+                            if (!__any(more)) break;
+                            if (more) {
+                                uint32_t R = any_lout ? 1u << (__ffs((int)remaining) - 1) : remaining;
+                                for (int sweep = 0; sweep < NBT; ++sweep) {
+                                    uint32_t c = 0;
 #pragma unroll
-                                for (int s = 0; s < IS; ++s) if (inI[s]) { sf &= ~(1u << (6 + s)); inI[s] = false; }
-                                infeas = true;
-                            } else if (n_load && !n_gen) {           // rule 3: no generation -> all load shed (p fixed 0)
+                                    for (int t = 0; t < BS; ++t) if (vb[t] < nb && ((R >> vb[t]) & 1u)) c |= adjm[t];
+                                    const uint32_t Rn = R | row_or<RW>(c);
+                                    const bool ch = Rn != R;
+                                    R = Rn;
+                                    if (!__any(ch)) break;
+                                }
+                                // rule 1: the island's angle reference is its bus that is eliminated last =
+                                // highest internal number (the host puts the reference bus at nb-1)
+                                const int pin = 31 - __clz((int)R);
+                                bool inI[IS];
 #pragma unroll
-                                for (int s = 0; s < IS; ++s) if (inI[s] && ((iinfo[s] >> 8) & 0xff) == IK_VIRTUAL) lozero |= 1u << s;
-                            } else if (losum > 1e-9) {               // rule 4: over-generation -> relax Pmin
-#pragma unroll
-                                for (int s = 0; s < IS; ++s) if (inI[s] && ((iinfo[s] >> 8) & 0xff) == IK_REAL) lozero |= 1u << s;
-                                infeas = true;
+                                for (int s = 0; s < IS; ++s) inI[s] = I_ON(s) && ((R >> (iinfo[s] & 0xff)) & 1u);
+                                if (island_rules(inI)) dropped |= 1u << pin;        // rule 5: dependent balance rows
+                                pinned |= 1u << pin;
+                                remaining &= ~R;
                             }
-                            uint32_t nfree = 0;
-#pragma unroll
-                            for (int s = 0; s < IS; ++s) if (inI[s] && C.i_tab[RW * s + rlane][0] - ILO(s) > 0.0) nfree += 1u;
-                            nfree = row_add<RW>(nfree);
-                            if (!nfree) dropped |= 1u << pin;        // rule 5: dependent balance rows
-                            pinned |= 1u << pin;
-                            remaining &= ~R;
                         }
                     }
                 }
@@ -487,22 +529,23 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 }
             } else {
                 // one scenario per wavefront: bus sets live in LDS (the solver workspace is idle during this prologue):
-                // LB[i] = label of bus i = highest internal bus number of its island, BF[i] = 1 pinned | 2 dropped
+                // LB[i] = label of bus i = highest internal bus number of its island, BF[i] = 1 pinned | 2 dropped.  Without a line outage
+                // the one island's label is nb - 1 on every bus and only that bus carries flags (bf_top): neither array is touched.
                 static_assert(RW == 16 || RW == 64, "row width");
                 int* const LB = reinterpret_cast<int*>(W);
                 int* const BF = LB + NBT;
                 bool iso = false;
+                int bf_top = 0, top = nb - 1;
+                __asm__ volatile("" : "+v"(top));        // comparisons of the lane's static bus numbers with it are not hoisted as lane masks
 #pragma unroll
                 for (int t = 0; t < BS; ++t) {
                     const int i = vb[t];
-                    if (i < nb) {
-                        if (any_lout) {
-                            bool anyon = false;
-                            const int nlb = C.b_nline[i];
-                            for (int e = 0; e < nlb; ++e) if (!outbit(OB, ng + (C.b_line[i][e] & 0x7f))) anyon = true;
-                            iso = iso || !anyon;
-                        }
-                        LB[i] = any_lout ? i : nb - 1;
+                    if (i < nb && any_lout) {
+                        bool anyon = false;
+                        const int nlb = C.b_nline[i];
+                        for (int e = 0; e < nlb; ++e) if (!outbit(OB, ng + (C.b_line[i][e] & 0x7f))) anyon = true;
+                        iso = iso || !anyon;
+                        LB[i] = i;
                         BF[i] = 0;
                     }
                 }
@@ -526,58 +569,33 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                     }
                     int ilab[IS];
 #pragma unroll
-                    for (int s = 0; s < IS; ++s) ilab[s] = LB[iinfo[s] & 0xff];
+                    for (int s = 0; s < IS; ++s) ilab[s] = any_lout ? LB[iinfo[s] & 0xff] : top;
 #pragma unroll
                     for (int t = 0; t < BS; ++t) {
                         const int i = vb[t];
-                        uint64_t roots = __ballot(i < nb && LB[i] == i);
+                        uint64_t roots = __ballot(i < nb && (any_lout ? LB[i] == i : i == top));
                         while (roots) {
                             const int pin = C.b_lane[RW * t + (int)__builtin_ctzll(roots)];      // rule 1: the island's highest bus (the bus that lane holds)
                             roots &= roots - 1;
-                            uint32_t cnt = 0; double losum = 0.0; bool inI[IS];
+                            bool inI[IS];
 #pragma unroll
-                            for (int s = 0; s < IS; ++s) {
-                                const int j = RW * s + rlane;
-                                const uint32_t kind = (iinfo[s] >> 8) & 0xff;
-                                inI[s] = I_ON(s) && ilab[s] == pin;
-                                if (inI[s]) {
-                                    cnt += 1u;
-                                    if (kind == IK_VIRTUAL) cnt += 1u << 8; else if (C.i_tab[j][0] > 0.0) cnt += 1u << 16;
-                                    losum += C.i_tab[j][3] * ISC(s);
-                                }
-                            }
-                            cnt = row_add<RW>(cnt); losum = row_sum<RW>(losum);
-                            const uint32_t n_inj = cnt & 0xff, n_load = (cnt >> 8) & 0xff, n_gen = cnt >> 16;
-                            if (n_inj && !n_load) {                  // rule 2
-#pragma unroll
-                                for (int s = 0; s < IS; ++s) if (inI[s]) { sf &= ~(1u << (6 + s)); inI[s] = false; }
-                                infeas = true;
-                            } else if (n_load && !n_gen) {           // rule 3
-#pragma unroll
-                                for (int s = 0; s < IS; ++s) if (inI[s] && ((iinfo[s] >> 8) & 0xff) == IK_VIRTUAL) lozero |= 1u << s;
-                            } else if (losum > 1e-9) {               // rule 4
-#pragma unroll
-                                for (int s = 0; s < IS; ++s) if (inI[s] && ((iinfo[s] >> 8) & 0xff) == IK_REAL) lozero |= 1u << s;
-                                infeas = true;
-                            }
-                            uint32_t nfree = 0;
-#pragma unroll
-                            for (int s = 0; s < IS; ++s) if (inI[s] && C.i_tab[RW * s + rlane][0] - ILO(s) > 0.0) nfree += 1u;
-                            nfree = row_add<RW>(nfree);
+                            for (int s = 0; s < IS; ++s) inI[s] = I_ON(s) && ilab[s] == pin;
+                            const bool dep = island_rules(inI);
 #pragma unroll
                             for (int u = 0; u < BS; ++u)
-                                if (vb[u] == pin) { sf |= 1u << (14 + u); if (!nfree) sf |= 1u << (16 + u); }   // rules 1, 5
+                                if (vb[u] == pin) { sf |= 1u << (14 + u); if (dep) sf |= 1u << (16 + u); }   // rules 1, 5
+                            bf_top = dep ? 3 : 1;
                         }
                     }
 #pragma unroll
-                    for (int t = 0; t < BS; ++t) if (vb[t] < nb) BF[vb[t]] = (B_PIN(t) ? 1 : 0) | (B_DROP(t) ? 2 : 0);
+                    for (int t = 0; t < BS; ++t) if (vb[t] < nb && any_lout) BF[vb[t]] = (B_PIN(t) ? 1 : 0) | (B_DROP(t) ? 2 : 0);
                     RELOAD_FENCE();
 #pragma unroll
                     for (int s = 0; s < LS; ++s) {
                         if ((linfo[s] >> 24) & LF_EXISTS) {
                             const int f = linfo[s] & 0xff, t = (linfo[s] >> 8) & 0xff;
                             const int lo_b = f < t ? f : t, hi_b = f < t ? t : f;
-                            const int flo = BF[lo_b], fhi = BF[hi_b];
+                            const int flo = any_lout ? BF[lo_b] : (lo_b == top ? bf_top : 0), fhi = any_lout ? BF[hi_b] : (hi_b == top ? bf_top : 0);
                             if ((flo | fhi) & 1) sf |= 1u << (18 + s);
                             if ((fhi & 1) | (flo & 2)) sf |= 1u << (21 + s);
                             if ((flo & 1) | (fhi & 2)) sf |= 1u << (24 + s);
@@ -588,6 +606,16 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
             }
 
             PT_IMARK(3)
+            // second batch: what the block entries and the start point read once -- the partner lines' mask words and susceptances, z0.  (The bus
+            // sums and the injection costs stay where they are used: in this batch they cost scratch on the wide tile.)
+            uint32_t ow_p[LS];
+            double t_lbp[LS];
+#pragma unroll
+            for (int s = 0; s < LS; ++s) {
+                const int pr = (((linfo[s] >> 24) & LF_OWNER) && lpart[s] >= 0) ? lpart[s] : 0;
+                ow_p[s] = OB[(ng + pr) >> 5]; t_lbp[s] = C.l_b[pr];
+            }
+            const double z0v = A_(6, z0);
             // ===== constant (per scenario) susceptance entries of the KKT blocks, pins/drops masked ==
 #pragma unroll
             for (int s = 0; s < LS; ++s) {
@@ -595,7 +623,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 if ((inf >> 24) & LF_OWNER) {
                     double v = L_ON(s) ? lb(s) : 0.0;
                     const int pr = lpart[s];
-                    if (pr >= 0 && !outbit(OB, ng + pr)) v += C.l_b[pr];
+                    if (pr >= 0 && !((ow_p[s] >> ((ng + pr) & 31)) & 1u)) v += t_lbp[s];
                     cBv[s] = -v;                 // -(b_l + b_partner) of the in-service lines of this bus pair
                 }
             }
@@ -618,34 +646,36 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
 
             PT_IMARK(4)
             // ===== dcopf_solver start point + mips initialisation (SURVEY.md Appendix B 2,4) =====
+            // mu = max(z0, 1/z) with z = max(z0, -h) >= z0: 1/z can exceed z0 only when z0 < 1 (z >= z0 >= 1 gives fl(1/z) <= 1 <= z0), so the
+            // IEEE divisions are taken under that wave-uniform test only (the default z0 is 1)
+            const bool z0_small = __builtin_amdgcn_readfirstlane((int)(z0v < 1.0)) != 0;
             double fl = 0.0;
             uint32_t nq = 0;
 #pragma unroll
             for (int s = 0; s < LS; ++s) {
                 if (L_ACT(s)) {
                     const double h = -lr(s);                       // x0: all angles 0 -> flow 0
-                    double z = A_(6, z0); if (h < -A_(6, z0)) z = -h;
-                    double mu = A_(6, z0); if (1.0 / z > A_(6, z0)) mu = 1.0 / z;
+                    double z = z0v; if (h < -z0v) z = -h;
+                    double mu = z0v; if (z0_small) { if (1.0 / z > z0v) mu = 1.0 / z; }
                     lzp[s] = z; lzm[s] = z; lmup[s] = mu; lmum[s] = mu;
                     nq += 2;
                 }
             }
 #pragma unroll
             for (int s = 0; s < IS; ++s) {
-                const int j = RW * s + rlane;
                 if (I_ON(s)) {
-                    const double hi = C.i_tab[j][0], lo = ILO(s);
+                    const double hi = t_hi[s], lo = ILOV(s, t_lo[s]);
                     const bool box = hi - lo > eps;
                     if (box) sf |= 1u << (10 + s);
                     ip[s] = box ? 0.5 * (lo + hi) : hi;
                     if (box) {
                         const double h = -0.5 * (hi - lo);
-                        double z = A_(6, z0); if (h < -A_(6, z0)) z = -h;
-                        double mu = A_(6, z0); if (1.0 / z > A_(6, z0)) mu = 1.0 / z;
+                        double z = z0v; if (h < -z0v) z = -h;
+                        double mu = z0v; if (z0_small) { if (1.0 / z > z0v) mu = 1.0 / z; }
                         izp[s] = z; izm[s] = z; imup[s] = mu; imum[s] = mu;
                         nq += 2;
                     }
-                    fl += C.i_tab[j][2] * ip[s];
+                    fl += C.i_tab[RW * s + rlane][2] * ip[s];
                 }
             }
 #pragma unroll

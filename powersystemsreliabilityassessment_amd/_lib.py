@@ -209,6 +209,11 @@ def load():
     if hasattr(L, "relmc_debug_set"):
         L.relmc_debug_set.argtypes = [vp, C.c_char_p, C.c_int32]
         L.relmc_debug_set.restype = C.c_int32
+    if hasattr(L, "relmc_debug_tail_plan"):
+        L.relmc_debug_tail_plan.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.relmc_debug_tail_plan.restype = C.c_int32
+        L.relmc_debug_tail_groups.argtypes = [vp, _abi.c_int64_p, i32p]
+        L.relmc_debug_tail_groups.restype = C.c_int32
     if hasattr(L, "relmc_dpp_probe"):
         L.relmc_dpp_probe.argtypes = [vp, dp, dp]
         L.relmc_dpp_probe.restype = C.c_int32

@@ -410,7 +410,8 @@ class Engine:
         return buf.value.decode()
 
     def debug_set(self, key: str, value: bool = True):
-        """Diagnosis switch of the context (tests): no_retry, retry_dense_first, nsq_no_stretch, db_no_probe, dynamic_shape (relmc_debug_set)."""
+        """Diagnosis switch of the context (tests): no_retry, retry_dense_first, nsq_no_stretch, db_no_probe, dynamic_shape, static_tail
+        (relmc_debug_set)."""
         self._check(self.L.relmc_debug_set(self._h, key.encode(), int(bool(value))), "relmc_debug_set")
 
     def shape_path(self) -> str:
@@ -422,6 +423,16 @@ class Engine:
         if rc < 0:
             raise RelmcError(f"relmc_debug_shape_path failed ({rc})")
         return "static" if rc == 1 else "dynamic"
+
+    def tail_groups(self):
+        """(T of the last fused launch on the 16-lane tile -- the tail groups per wavefront that were handed out dynamically, 0 = none --,
+        fused launches of this context that ran with T > 0 so far, wavefronts of a full grid of that tile on this device)
+        (relmc_debug_tail_groups)."""
+        k, w = C.c_int64(), C.c_int32()
+        t = self.L.relmc_debug_tail_groups(self._h, C.byref(k), C.byref(w))
+        if t < 0:
+            raise RelmcError(f"relmc_debug_tail_groups failed ({t})")
+        return int(t), int(k.value), int(w.value)
 
     def last_kernel_ms(self) -> float:
         ms = C.c_double()

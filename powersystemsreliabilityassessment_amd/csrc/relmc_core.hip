@@ -76,6 +76,20 @@ int launch_eval_t(relmc_ctx* ctx, EvalArgs& a, int* rows_out, hipEvent_t ev_star
 #else
     a.timing = nullptr;
 #endif
+    // dynamic tail of the fused path on the 16-lane tile (TailPlan, relmc_ctx.h); the order calibration's MODE 5 and every other mode: T = 0
+    a.tail_groups = 0;
+    if constexpr (MODE == 0 && std::is_same<TL, Tile24>::value) {
+        a.tail_rec = nullptr; a.tail_count = nullptr;          // (they share their words with MODE 6's scratch fields: set by this mode only)
+        const TailPlan plan(a.n, (int64_t)blocks * TL::WPB);
+        if (plan.T > 0 && !ctx->sw.static_tail) {
+            { const int rc = fail_count_ensure(ctx); if (rc) return rc; }
+            HIP_TRY(ctx, ctx->dtail.grow(sizeof(TailRecT<TL>) * (size_t)plan.items()));
+            a.tail_groups = plan.T; a.tail_rec = ctx->dtail.get(); a.tail_count = ctx->retry.fail_count.get() + 1;
+        }
+        ctx->last_tail_groups = a.tail_groups; ctx->tail_launches += a.tail_groups > 0;
+        if (verbose()) fprintf(stderr, "relmc: fused launch of %lld scenarios on %d wavefronts: tail groups T = %d%s\n", (long long)a.n, blocks * TL::WPB, a.tail_groups,
+                               a.tail_groups ? "" : (ctx->sw.static_tail ? " (static_tail)" : " (fewer than 2 T groups per wavefront)"));
+    }
     HIP_TRY(ctx, hipEventRecord(ev_start ? ev_start : ctx->ev0, ctx->stream));
     // the fused path of a case whose whole shape is the compiled-in one (shape_select) runs the shape-specialised instantiation: same program,
     // same results; the further orders' images (alt) have other pass counts and stay with the interpreter
@@ -91,6 +105,13 @@ int launch_eval_t(relmc_ctx* ctx, EvalArgs& a, int* rows_out, hipEvent_t ev_star
         hipLaunchKernelGGL((relmc_eval_kernel<MODE, TL>), dim3(blocks), dim3(64 * TL::WPB), alt ? ctx->alt_lds_bytes[alt - 1] : ctx->lds_bytes, ctx->stream,
                            reinterpret_cast<const DevCaseT<TL>*>(alt ? ctx->dcase_alt[alt - 1].get() : ctx->dcase.get()), a);
     HIP_TRY(ctx, hipGetLastError());
+    if constexpr (MODE == 0 && std::is_same<TL, Tile24>::value) {
+        if (a.tail_groups > 0) {          // the parked fp64 contributions into their owners' records, inside the timed region
+            hipLaunchKernelGGL(relmc_tail_replay_kernel<TL>, dim3(blocks), dim3(64 * TL::WPB), 0, ctx->stream, reinterpret_cast<PartialT<TL>*>(ctx->dpartial.get()),
+                               reinterpret_cast<const TailRecT<TL>*>(ctx->dtail.get()), a.tail_groups, a.tail_count);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+    }
     HIP_TRY(ctx, hipEventRecord(ev_stop ? ev_stop : ctx->ev1, ctx->stream));
     *rows_out = blocks * TL::WPB * TL::SPW;
     return RELMC_OK;
@@ -231,7 +252,7 @@ int order_probe(relmc_ctx* ctx, int alt, int32_t* failures)
         if (rc0) return rc0;
     }
     auto& R = ctx->retry;
-    HIP_TRY(ctx, hipMemsetAsync(R.fail_count.get(), 0, sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(R.fail_count.get(), 0, R.kCountBytes, ctx->stream));
     a.fail_list = R.fail.get(); a.fail_count = R.fail_count.get(); a.fail_cap = (uint32_t)R.fail.size(); a.unit_base = 0;
     int rows = 0;
     int rc = launch_eval(ctx, 5, a, &rows, nullptr, nullptr, alt);      // MODE 5 = MODE 0 under its own kernel name
@@ -239,7 +260,7 @@ int order_probe(relmc_ctx* ctx, int alt, int32_t* failures)
     uint32_t cnt = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&cnt, R.fail_count.get(), sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemset(R.fail_count.get(), 0, sizeof(uint32_t)));
+    HIP_TRY(ctx, hipMemset(R.fail_count.get(), 0, R.kCountBytes));
     R.fail_dirty = false;
     *failures = (int32_t)cnt;
     return RELMC_OK;

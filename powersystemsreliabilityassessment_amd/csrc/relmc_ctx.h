@@ -37,6 +37,7 @@ struct relmc_switches {
     bool nsq_no_stretch = false;     // relmc_nsq_run: one launch per batch
     bool db_no_probe = false;        // state database: every batch through the dedupe, no per-sample probe
     bool dynamic_shape = false;      // fused path: the run-time-shape evaluation kernel even when the case has the compiled-in shape
+    bool static_tail = false;        // fused path on the 16-lane tile: no dynamic tail (T = 0), every group run by the wavefront that owns it
 };
 
 namespace relmc_host {
@@ -100,6 +101,8 @@ struct relmc_ctx {
     DevBuf<uint8_t> dcase;               // device image of the active tile's case (kCaseBytes)
     int nb = 0, ng = 0, nl = 0, ncomp = 0;
     DevBuf<uint8_t> dpartial;
+    DevBuf<uint8_t> dtail;               // TailRecT<Tile24>[wavefronts * T] of the fused path's dynamic tail, allocated at the first launch that has one
+    int last_tail_groups = 0; int64_t tail_launches = 0;   // T of the last fused launch on the 16-lane tile, launches with T > 0 so far (relmc_debug_tail_groups)
     DevBuf<relmc::DevAcc> dacc;
     struct HostStage { relmc_acc acc; uint32_t fail_cnt, pad; };
     PinBuf<HostStage> hstage;            // accumulators + listed-unit count of a fused launch come back in one synchronisation
@@ -134,7 +137,10 @@ struct relmc_ctx {
     int alt_state[kAlt] = {0, 0};            // 0 not built yet, 1 ready, -1 unavailable (that order does not fit the tile)
     DevBuf<uint8_t> dcase_alt[kAlt]; uint32_t alt_scen_doubles[kAlt] = {0, 0}, alt_lds_bytes[kAlt] = {0, 0}, alt_stash_off[kAlt] = {0, 0};
     struct Retry {
-        DevBuf<relmc::FailRec> fail; DevBuf<uint32_t> fail_count; bool fail_dirty = false;   // the kernel's list (grows with the size of the call, fail_arm)
+        // the kernel's list (grows with the size of the call, fail_arm).  fail_count holds kCountWords words: [0] the listed units, [1] the claim
+        // counter of the dynamic tail, zero between launches (relmc_tail_replay_kernel puts it back); every clearing of the buffer clears both
+        DevBuf<relmc::FailRec> fail; DevBuf<uint32_t> fail_count; bool fail_dirty = false;
+        static constexpr size_t kCountWords = 2, kCountBytes = kCountWords * sizeof(uint32_t);
         DevBuf<double> dense;                // global scratch of the dense pivoted last resort (MODE 6)
         // scratch rows of the re-evaluation: twice `rows` listed units (the third order's compact rows start at `rows`)
         DevBuf<uint32_t> keys; DevBuf<double> dns; DevBuf<int32_t> meta; DevBuf<double> nodal, scale; int64_t rows = 0;
@@ -264,10 +270,30 @@ int finish_timing(relmc_ctx* ctx);                 // stream synchronised, ctx->
 int case_load_image(relmc_ctx* ctx, const relmc_case_desc* d, int order_variant);   // device image of the case under a further order (retry levels)
 inline int mask_words(const relmc_ctx* ctx) { return ctx->tile == 0 ? Tile24::OW : Tile96::OW; }
 
+// Dynamic tail of the fused path on the 16-lane tile (relmc_eval_kernel phase B, relmc_tail_replay_kernel): the plan of a launch of n
+// scenarios on `waves` wavefronts.  Wavefront w owns the groups [begin(w), end(w)) of four scenarios; T = kTailGroups if every wavefront
+// owns at least 2 T groups, else 0 (the launch is the static one).  Phase A of w runs [begin(w), end(w) - T); item p of the claim counter,
+// 0 <= p < waves * T, is group end(p % waves) - T + p / waves.
+#ifndef RELMC_TAIL_GROUPS
+#define RELMC_TAIL_GROUPS 8
+#endif
+constexpr int kTailGroups = RELMC_TAIL_GROUPS;
+struct TailPlan {
+    int64_t ngroups, waves; int T;
+    TailPlan(int64_t n, int64_t waves_) : ngroups((n + Tile24::SPW - 1) / Tile24::SPW), waves(waves_), T(waves_ > 0 && ngroups / waves_ >= 2 * kTailGroups ? kTailGroups : 0) {}
+    int64_t begin(int64_t w) const { return ngroups * w / waves; }
+    int64_t end(int64_t w) const { return ngroups * (w + 1) / waves; }
+    int64_t cut(int64_t w) const { return end(w) - T; }
+    int64_t items() const { return waves * T; }
+    int64_t owner(int64_t p) const { return p % waves; }
+    int64_t group(int64_t p) const { return end(p % waves) - T + p / waves; }
+};
+
 // ---- relmc_retry.hip ----------------------------------------------------------------------------------------------------------
 constexpr uint32_t kFailCapMin = 4096, kFailCapSteady = 1u << 20, kFailCapMax = 1u << 26;
 uint32_t fail_cap_for(int64_t call_units);
 int fail_list_ensure(relmc_ctx* ctx, uint32_t cap);
+int fail_count_ensure(relmc_ctx* ctx);           // the two count words exist (zeroed when they are created)
 struct RetryOut { std::vector<FailRec> rec; std::vector<double> dns, nodal; std::vector<int32_t> meta; };   // meta = status | relaxed << 2 | iterations << 8
 int alt_ensure(relmc_ctx* ctx, int v);
 int fail_arm(relmc_ctx* ctx, EvalArgs& a, int64_t unit_base, bool reset, int64_t call_units);

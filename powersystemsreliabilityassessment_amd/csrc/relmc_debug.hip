@@ -1,6 +1,7 @@
 // relmc_debug.hip — introspection and test hooks that are not part of include/relmc.h (bound by the Python test suite and the profiling
 // scripts through ctypes): the active schedule's shape, every Newton step through the dense pivoted solve, per-phase cycle counters and
-// per-iteration traces of the profiling builds, the stretch-length rule of relmc_nsq_run, the diagnosis switches of a context.
+// per-iteration traces of the profiling builds, the stretch-length rule of relmc_nsq_run, the dynamic tail's plan, the diagnosis switches of a
+// context.
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -129,7 +130,31 @@ int32_t relmc_debug_shape_path(const relmc_ctx* ctx)
     return ctx->shape_static && !ctx->sw.dynamic_shape ? 1 : 0;
 }
 
-// diagnosis switches of the context (tests): "no_retry", "retry_dense_first", "nsq_no_stretch", "db_no_probe", "dynamic_shape"; value 0 / 1.
+// The dynamic tail's plan for a fused launch of n scenarios on `waves` wavefronts of the 16-lane tile (TailPlan, relmc_ctx.h; host only: no
+// device, no context).  Returns T.  Optional outputs: a_begin / a_end [waves] = every wavefront's phase-A range of groups, owner / group
+// [waves * T] = the wavefront that owns item p of the claim counter and the group the item stands for; negative = bad arguments.
+int32_t relmc_debug_tail_plan(int64_t n, int32_t waves, int64_t* a_begin, int64_t* a_end, int32_t* owner, int64_t* group)
+{
+    if (n < 0 || waves <= 0) return RELMC_ERR_INVALID;
+    const TailPlan plan(n, waves);
+    for (int64_t w = 0; w < waves; ++w) { if (a_begin) a_begin[w] = plan.begin(w); if (a_end) a_end[w] = plan.cut(w); }
+    for (int64_t p = 0; p < plan.items(); ++p) { if (owner) owner[p] = (int32_t)plan.owner(p); if (group) group[p] = plan.group(p); }
+    return plan.T;
+}
+
+// T of the context's last fused launch on the 16-lane tile (what RELMC_VERBOSE prints per launch): 0 = it ran without the dynamic tail;
+// *launches_out (optional) = the fused launches of the context that ran with one so far; *waves_out (optional) = the wavefronts of a full
+// grid of the 16-lane tile on this device (CUs x workgroups per CU x 4), 0 before a case is loaded
+int32_t relmc_debug_tail_groups(const relmc_ctx* ctx, int64_t* launches_out, int32_t* waves_out)
+{
+    if (!ctx) return RELMC_ERR_INVALID;
+    if (launches_out) *launches_out = ctx->tail_launches;
+    if (waves_out) *waves_out = ctx->has_case && ctx->tile == 0 ? ctx->num_cu * ctx->blocks_per_cu * Tile24::WPB : 0;
+    return ctx->last_tail_groups;
+}
+
+// diagnosis switches of the context (tests): "no_retry", "retry_dense_first", "nsq_no_stretch", "db_no_probe", "dynamic_shape", "static_tail";
+// value 0 / 1.  static_tail may change between launches: the fused path then runs without the dynamic tail (tests/test_tail_paths.py).
 // no_retry must be set before relmc_case_load (the order calibration and the list arming must agree).  dynamic_shape may change between
 // launches: the fused path then runs the run-time-shape kernel on a case that has the compiled-in shape (tests/test_shape_paths.py).
 int32_t relmc_debug_set(relmc_ctx* ctx, const char* key, int32_t value)
@@ -141,6 +166,7 @@ int32_t relmc_debug_set(relmc_ctx* ctx, const char* key, int32_t value)
     else if (!std::strcmp(key, "nsq_no_stretch")) ctx->sw.nsq_no_stretch = v;
     else if (!std::strcmp(key, "db_no_probe")) ctx->sw.db_no_probe = v;
     else if (!std::strcmp(key, "dynamic_shape")) ctx->sw.dynamic_shape = v;
+    else if (!std::strcmp(key, "static_tail")) ctx->sw.static_tail = v;
     else return fail(ctx, RELMC_ERR_INVALID, std::string("relmc_debug_set: unknown switch ") + key);
     return RELMC_OK;
 }

@@ -108,6 +108,16 @@ struct PartialT {
     uint32_t pad;
 };
 
+// Dynamic tail of the fused path on the 16-lane tile (relmc_eval_kernel, phase B): the fp64 contributions of one claimed scenario group,
+// parked until relmc_tail_replay_kernel adds them to the record of the wavefront that owns the group.  Item p = k * W + owner is tail group
+// k of wavefront `owner` (W wavefronts in the grid).  flag[row] is written by every claim; dns[row] and the row's lanes' shed[] only with flag 1.
+template <class TL>
+struct TailRecT {
+    double shed[64][TL::IS];        // per lane of the wavefront
+    double dns[TL::SPW];            // per scenario row
+    uint32_t flag[TL::SPW];         // per scenario row: 1 = the static assignment adds this row's dns (and its non-zero shed[])
+};
+
 // one unit the primary schedule did not converge on
 struct FailRec {
     unsigned long long unit;        // launch-local index + unit_base: sample offset (MODE 0), state (1), year * hours + hour (2), distinct state (3), row offset (4)
@@ -157,10 +167,14 @@ struct EvalArgs {
     uint32_t* fail_count;
     FailRec* fail_list;
     uint32_t fail_cap;
+    int32_t tail_groups;            // dynamic tail (below), 0 = static assignment
     int64_t unit_base;              // added to the launch-local unit index (chunked host-buffer pipeline)
     // MODE 6 (dense pivoted last resort): [scenario rows of the grid][dense_stride] doubles of global scratch, dense_stride >= 2 nb (2 nb + 1)
-    double* dense;
-    uint64_t dense_stride;
+    // Dynamic tail (MODE 0 on the 16-lane tile; TailPlan in relmc_ctx.h): the last tail_groups groups of every wavefront's range are handed out
+    // through *tail_count (zero at launch), their fp64 contributions parked in tail_rec = TailRecT<tile>[wavefronts * tail_groups].  The two
+    // pointers share their words with MODE 6's, which no MODE 0 launch uses: the argument block keeps its size and every field its offset.
+    union { double* dense; void* tail_rec; };
+    union { uint64_t dense_stride; uint32_t* tail_count; };
 };
 
 // Zero-curtailment certificate (relmc_screen.hip; SURVEY 8f rank 4, mc_simulation.m:57-59, 65): tables built by relmc_case_load on the host, resident in

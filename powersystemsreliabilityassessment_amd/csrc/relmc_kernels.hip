@@ -220,10 +220,45 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
     if (WINDOWED) {
         wb_begin = ngroups * gwave / gstride; wb_end = ngroups * (gwave + 1) / gstride; wb_step = 16;
     }
-    for (int64_t wb = wb_begin; wb < wb_end; wb += wb_step) {
-    int win_groups = 1;
+    // Dynamic tail (a.tail_groups = T > 0, WINDOWED only).  Phase A: the wavefront walks its own range up to the cut wb_end - T.  Phase B: the
+    // last T groups of EVERY wavefront's range are items p = k * W + owner of one device counter; whoever claims p samples and sorts the
+    // window of the owner's range that holds group wb_end(owner) - T + k, with the owner's bounds (so every group is composed as under the
+    // static assignment), and runs that one group.  Its integer counts go to the claimant's own record (integer sums do not depend on who
+    // adds what), its fp64 contributions are parked in TailRec[p] and added to the owner's record by relmc_tail_replay_kernel, in group
+    // order: the sums are those of the static assignment bit for bit, whoever ran which group.  The owner claims through the same counter.
+    // The claimed item (phase B; -1: the wavefront's own range, phase A) lives in a spare word of the options block, one per wavefront, and is
+    // read where it is used: carried in a register it would be live across the interior-point loop.
+    static_assert(!WINDOWED || 80 + 4 * WPB <= OPT_BYTES, "one word per wavefront behind the ten option doubles");
+    int* const TP = reinterpret_cast<int*>(smem + 80) + (tid >> 6);
+    if (WINDOWED) { *TP = -1; RELOAD_FENCE(); }
+    for (int64_t wb = wb_begin; WINDOWED || wb < wb_end; wb += wb_step) {
+    int win_groups = 1, wg0 = 0;
     uint32_t win_valid = 0;
     if (WINDOWED) {
+        const int T = a.tail_groups;
+        int run = 16;                              // groups of this window that are run in this pass: [wg0, run)
+        // (every lane of the wavefront holds the same wb and wb_end; the compiler is told so, and branches without saving lane masks)
+        if (__builtin_amdgcn_readfirstlane((int)(*TP < 0 && wb < wb_end - T)) != 0) {
+            if (wb_end - T - wb < 16) run = (int)(wb_end - T - wb);      // the window straddles the cut: sampled whole, run up to the cut
+        } else {
+            if (T == 0) break;
+            uint32_t p = 0;
+            if (lane == 0) p = atomicAdd(a.tail_count, 1u);
+            p = __builtin_amdgcn_readfirstlane(p);
+            // the group and wavefront counts are taken again from the arguments, behind a fence: kept from the top of the kernel they would be
+            // live across the interior-point loop
+            int64_t n_ = a.n; uint32_t nw = gridDim.x;
+            __asm__ volatile("" : "+s"(n_), "+s"(nw));
+            nw *= WPB;
+            if (p >= nw * (uint32_t)T) break;
+            const int64_t ng_ = (n_ + SPW - 1) / SPW, owner = p % nw, ob = ng_ * owner / nw;
+            wb_end = ng_ * (owner + 1) / nw;
+            const int64_t g = wb_end - T + p / nw;
+            wb = ob + ((g - ob) & ~(int64_t)15);
+            wg0 = (int)(g - wb); run = wg0 + 1;
+            *TP = (int)p;
+            RELOAD_FENCE();
+        }
         const int64_t si = wb * 4 + lane;                          // this lane's scenario of the window
         const bool valid = (wb + (lane >> 2)) < wb_end && si < a.n;
         uint32_t m0 = 0, m1 = 0, m2 = 0, m3 = 0;
@@ -264,9 +299,10 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
         RELOAD_FENCE();
         win_valid = n_valid;
         win_groups = (int)((n_valid + 3u) >> 2);
+        if (run < win_groups) win_groups = run;
     }
     PT_IMARK(0)
-    for (int wg = 0; wg < win_groups; ++wg) {
+    for (int wg = wg0; wg < win_groups; ++wg) {
         const int64_t grp = WINDOWED ? wb + wg : wb;
         const int64_t sidx = grp * SPW + lane / RW;
         const bool live = WINDOWED ? (uint32_t)(wg * 4 + lane / RW) < win_valid : sidx < a.n;
@@ -1264,6 +1300,11 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
 
         PT_MARK(6)
         // ===== mc_simulation.m:54-99 (dns, noise filters, nodal shed) + nsqMain.m:270 =============
+        using TailRec = TailRecT<TL>;
+        RELOAD_FENCE();
+        const int tp = WINDOWED ? *TP : -1;
+        const bool park = WINDOWED && tp >= 0;     // a claimed tail group: its fp64 contributions go to TailRec[tp], not to PA
+        uint32_t tflag = 0;                        // the row's flag of that record: 1 = dns and shed[] written
         if (live) {
             double dns = fval + C.total_load * lscale;            // mc_simulation.m:54 / seq_mcsimulation.m:67
             if (dns < 0.1) dns = 0.0;
@@ -1297,7 +1338,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                     const double v = ip[s] * base - C.i_tab[j][3] * lscale;     // Pg - Pmin, mc_simulation.m:86
                     if (v > 1e-3) shed[s] = v;                           // mc_simulation.m:90
                 }
-                if (MODE != 4 && !defer && shed[s] != 0.0) PA.shed[s] += MODE == 3 ? shed[s] * (double)wgt : shed[s];
+                if (MODE != 4 && !defer && !park && shed[s] != 0.0) PA.shed[s] += MODE == 3 ? shed[s] * (double)wgt : shed[s];
                 if (MODE != 4 && !defer && fail && ((iinfo[s] >> 8) & 0xff) == IK_REAL && outbit(OB, j)) PA.cf_inj[s] += wgt;
             }
 #pragma unroll
@@ -1307,6 +1348,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 acc_n += wgt;
                 if (dns != 0.0) {
                     if (MODE == 3) { PA.dns = __builtin_fma((double)wgt, dns, PA.dns); PA.dns2 = __builtin_fma((double)wgt * dns, dns, PA.dns2); }
+                    else if (park) { reinterpret_cast<TailRec*>(a.tail_rec)[tp].dns[lane / RW] = dns; tflag = 1; }
                     else { PA.dns += dns; PA.dns2 = __builtin_fma(dns, dns, PA.dns2); }
                 }
                 if (fail) PA.nfail += wgt;
@@ -1314,6 +1356,11 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 if (status == 1 || status == 2) PA.nnc += wgt;
                 if (infeas) PA.ninf += wgt;
                 acc_it += (uint32_t)it * wgt;
+            }
+            if (WINDOWED && park && !defer && dns != 0.0) {      // where the static assignment adds dns, every lane's shed[] (zeros too: the replay's test skips them)
+                double* const ts = reinterpret_cast<TailRec*>(a.tail_rec)[tp].shed[lane];
+#pragma unroll
+                for (int s = 0; s < IS; ++s) ts[s] = shed[s];
             }
             if (MODE == 2 && rlane == 0) a.curt[(size_t)seq_year * a.seq_hpy + seq_hour] = dns;
             if (MODE == 0 && a.dns && rlane == 0)      // optional: dns of every sample in sampling order (checkpoint histories of small batches)
@@ -1344,11 +1391,37 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 }
             }
         }
+        if (WINDOWED && park && rlane == 0) reinterpret_cast<TailRec*>(a.tail_rec)[tp].flag[lane / RW] = tflag;     // always: dead rows and deferred units say 0
         PT_MARK(7)
     }
     }
     if (rlane == 0) { PA.n = acc_n; PA.iters = acc_it; }
     PT_FLUSH
+}
+
+// Replay of the dynamic tail: one thread per (owner wavefront, lane), the thread that owns the same Partial record in relmc_eval_kernel.  For
+// the owner's tail groups k = 0 .. T - 1 in order it applies the additions of that kernel's output phase under the same conditions, from the
+// values the claimants parked in TailRec[k * W + owner].  The tail groups are the last of the owner's range, so every fp64 field sees the
+// static assignment's additions in the static assignment's order.  The last thread zeroes the claim counter for the next launch.
+template <class TL>
+__global__ void __launch_bounds__(64 * TL::WPB) relmc_tail_replay_kernel(PartialT<TL>* __restrict__ part, const TailRecT<TL>* __restrict__ rec, int tail_groups,
+                                                                           uint32_t* __restrict__ tail_count)
+{
+    constexpr int RW = TL::RW, IS = TL::IS, WPB = TL::WPB;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const size_t nw = (size_t)gridDim.x * WPB, owner = (size_t)blockIdx.x * WPB + (tid >> 6);
+    PartialT<TL>& PA = part[(size_t)blockIdx.x * (64 * WPB) + tid];
+    for (int k = 0; k < tail_groups; ++k) {
+        const TailRecT<TL>& R = rec[(size_t)k * nw + owner];
+        if (R.flag[lane / RW] == 0) continue;
+#pragma unroll
+        for (int s = 0; s < IS; ++s) { const double v = R.shed[lane][s]; if (v != 0.0) PA.shed[s] += v; }
+        if ((lane & (RW - 1)) == 0) {
+            const double dns = R.dns[lane / RW];
+            if (dns != 0.0) { PA.dns += dns; PA.dns2 = __builtin_fma(dns, dns, PA.dns2); }
+        }
+    }
+    if (blockIdx.x == 0 && tid == 0) *tail_count = 0u;
 }
 
 // One workgroup of four wavefronts per output element.  Thread t sums the scenario rows t, t + 256, ... of its element's field (eight

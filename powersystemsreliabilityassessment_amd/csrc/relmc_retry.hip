@@ -25,13 +25,19 @@ uint32_t fail_cap_for(int64_t call_units)
     const int64_t c = (int64_t)kFailCapMin + call_units / 256;
     return c > (int64_t)kFailCapSteady ? kFailCapSteady : (uint32_t)c;
 }
-int fail_list_ensure(relmc_ctx* ctx, uint32_t cap)
+int fail_count_ensure(relmc_ctx* ctx)
 {
     auto& R = ctx->retry;
     if (!R.fail_count.get()) {
-        HIP_TRY(ctx, R.fail_count.grow(1));
-        HIP_TRY(ctx, hipMemsetAsync(R.fail_count.get(), 0, sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, R.fail_count.grow(R.kCountWords));
+        HIP_TRY(ctx, hipMemsetAsync(R.fail_count.get(), 0, R.kCountBytes, ctx->stream));
     }
+    return RELMC_OK;
+}
+int fail_list_ensure(relmc_ctx* ctx, uint32_t cap)
+{
+    auto& R = ctx->retry;
+    { const int rc = fail_count_ensure(ctx); if (rc) return rc; }
     if (cap <= R.fail.size()) return RELMC_OK;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // the list is dropped below: no launch may still write to it
     HIP_TRY(ctx, R.fail.grow(cap));
@@ -63,7 +69,7 @@ int fail_arm(relmc_ctx* ctx, EvalArgs& a, int64_t unit_base, bool reset, int64_t
     }
     // the count is zero whenever a call has collected its list (fail_retry zeroes it after a non-empty one), so the common case costs no
     // memset launch; only a call that was abandoned between arming and collecting leaves it to be cleared here
-    if (reset && ctx->retry.fail_dirty) { HIP_TRY(ctx, hipMemsetAsync(ctx->retry.fail_count.get(), 0, sizeof(uint32_t), ctx->stream)); }
+    if (reset && ctx->retry.fail_dirty) { HIP_TRY(ctx, hipMemsetAsync(ctx->retry.fail_count.get(), 0, ctx->retry.kCountBytes, ctx->stream)); }
     if (reset) ctx->retry.fail_dirty = true;
     a.fail_list = ctx->retry.fail.get(); a.fail_count = ctx->retry.fail_count.get(); a.fail_cap = (uint32_t)ctx->retry.fail.size();
     return RELMC_OK;
@@ -91,7 +97,7 @@ int fail_retry(relmc_ctx* ctx, const relmc_solver_opts& o, double fail_threshold
     else HIP_TRY(ctx, hipMemcpy(&cnt, ctx->retry.fail_count.get(), sizeof(cnt), hipMemcpyDeviceToHost));
     ctx->retry.fail_dirty = false;
     if (cnt == 0) return RELMC_OK;
-    HIP_TRY(ctx, hipMemset(ctx->retry.fail_count.get(), 0, sizeof(uint32_t)));
+    HIP_TRY(ctx, hipMemset(ctx->retry.fail_count.get(), 0, ctx->retry.kCountBytes));
     const uint32_t cap = (uint32_t)ctx->retry.fail.size();
     if (cnt > cap) {                                         // the units beyond the list were accumulated by the kernel as they were
         ctx->retry_overflow += (int64_t)(cnt - cap);

@@ -170,7 +170,7 @@ int nsq_accumulate_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int
             // the launch is a function of (seed, range) alone, so the second one lists them all
             listed = a.fail_count ? ctx->hstage.get()->fail_cnt : 0u;
             if (a.fail_list == nullptr || listed <= ctx->retry.fail.size() || ctx->retry.fail.size() >= kFailCapMax || attempt >= 2) break;
-            HIP_TRY(ctx, hipMemset(ctx->retry.fail_count.get(), 0, sizeof(uint32_t)));
+            HIP_TRY(ctx, hipMemset(ctx->retry.fail_count.get(), 0, ctx->retry.kCountBytes));
             rc = fail_list_ensure(ctx, listed + listed / 8 > kFailCapMax ? kFailCapMax : listed + listed / 8);
             if (rc) return rc;
         }

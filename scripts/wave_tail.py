@@ -1,6 +1,7 @@
 import os, sys, ctypes as C
 sys.path.insert(0,''+os.path.dirname(os.path.dirname(os.path.abspath(__file__)))+'')
-os.environ['RELMC_LIB_PATH']=''+os.path.dirname(os.path.dirname(os.path.abspath(__file__)))+'/powersystemsreliabilityassessment_amd/csrc/ablate/librelmc_pt.so'
+# the phase-timing build to load, relative to csrc (default: ablate/librelmc_pt.so; a parent's build copied beside it for a before / after)
+os.environ['RELMC_LIB_PATH']=''+os.path.dirname(os.path.dirname(os.path.abspath(__file__)))+'/powersystemsreliabilityassessment_amd/csrc/'+(sys.argv[1] if len(sys.argv)>1 else 'ablate/librelmc_pt.so')
 import numpy as np
 from powersystemsreliabilityassessment_amd import api
 e=api.Engine(); e.nsq_accumulate(1,0,65536)

@@ -394,6 +394,39 @@ int32_t relmc_hl1_seq_events(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain
                              int32_t start, relmc_hl1_event_acc* acc, int32_t n_dur_bins, int64_t* dur_hist_host,
                              int64_t events_cap, relmc_hl1_event* events_host);
 
+/* ---- load sweep on the HL1 sequential chronology: one fleet history against up to 16 load levels (an extension beyond the reference) ---- */
+/* The reference evaluates one fleet against one load curve.  A planner also asks how much load a fleet carries at a risk target (PLCC)
+ * and what a unit is worth in load (ELCC); both are root searches on risk as a function of load, and this call gives up to 16 points of
+ * that function from ONE walk of every chain.
+ * The chronology is relmc_hl1_seq's, word for word (model of relmc_hl1_seq_load, draws (seed, chain, k | 0x40000000, event), start rules,
+ * no FMA, DOWN on steps [ceil(T_odd), ceil(T_even))): under one seed, chain c of every level sees exactly the fleet history of chain c of
+ * relmc_hl1_seq.
+ *   load of level j at hour h   L_j(h) = scale_j * load[h] + shift_j, the product and the sum each rounded (numpy's scale * load + shift)
+ *   fleet of level j            0: every unit; 1: every unit except those whose bit is set in `withheld` (bit k & 31 of word k >> 5).
+ *                               cap_avail of fleet 1 is the same ascending loop over the UP units in which a withheld unit adds 0.0
+ *                               (exact), i.e. bitwise the fleet whose withheld capacities were loaded as 0.0
+ *   loss iff cap_fleet < L_j(h) (strict), deficit L_j(h) - cap_fleet; per level and year: loss hours, EUE, loss events by relmc_hl1_seq's
+ *   rules (step 1 counts, an event across a year boundary counts once, in the year it starts; every level has its own previous-step flag)
+ * A level's EUE of a year is summed in relmc_hl1_seq's order, so level (1.0, 0.0, fleet 0) reproduces relmc_hl1_seq's year records bit
+ * for bit, and any level those of relmc_hl1_seq on the model loaded with its curve and with the withheld capacities as 0.0.
+ * A level's year records depend on (seed, chain, start, years_per_chain, data, that level, withheld) only: not on the other levels, their
+ * order, or how a chain range is split into calls.  acc[j] is summed in a fixed order, so a repeated call is bitwise identical. */
+#define RELMC_HL1_SWEEP_MAX_LEVELS 16
+typedef struct { double scale, shift; int32_t fleet; int32_t reserved; } relmc_hl1_sweep_level;   /* 24 bytes, reserved = 0 */
+/* chains [first_chain, first_chain + n_chains), each years_per_chain consecutive years, of the model loaded by relmc_hl1_seq_load
+ * (RELMC_ERR_NO_CASE before that call).  RELMC_ERR_INVALID, with relmc_last_error naming the level or the bit, for: a null ctx, levels or
+ * acc; n_levels outside 1 .. RELMC_HL1_SWEEP_MAX_LEVELS; a non-finite scale or shift; fleet not 0 or 1; reserved != 0; fleet 1 with
+ * withheld == NULL; a withheld bit at or above ngen; anything relmc_hl1_seq refuses.  A refused call changes nothing; n_chains == 0
+ * zeroes the outputs.
+ *   withheld    optional [4] mask words (128 units)
+ *   acc         [n_levels]
+ *   years_host  optional [n_levels][n_chains * years_per_chain], level-major, then chain-major
+ * Long chain ranges go in launches of at most ~4M year records counted over all levels; relmc_last_kernel_ms covers every launch. */
+int32_t relmc_hl1_seq_sweep(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain,
+                            int32_t start, int32_t n_levels, const relmc_hl1_sweep_level* levels,
+                            const uint32_t* withheld, relmc_hl1_seq_acc* acc,
+                            relmc_hl1_seq_year* years_host);
+
 /* ---- HL1 multi-area chronology with tie-line transfers (AdequacyAssessmentII.jl:73-250 solve_curtailment_fast / run_fast_sequential_simulation) ---- */
 /* The chronology is relmc_hl1_seq's, word for word: draws (seed, chain, k | 0x40000000, event) with k the GLOBAL unit index (units stored
  * area-major: area 0's units, then area 1's, ...), the same start rules, steps n = 1 .. Y*H with the state carried across years, no FMA.

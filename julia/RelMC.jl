@@ -513,6 +513,52 @@ function run_sequential_events(eng::Engine, capacity::Vector{Float64}, mttf::Vec
             n_events=n, duration_hist=hist, events=evs[1:min(n, max_events)])
 end
 
+"relmc_hl1_sweep_level (include/relmc.h): one load level of relmc_hl1_seq_sweep; fleet 0 = every unit, 1 = without the withheld units"
+struct Hl1SweepLevel
+    scale::Cdouble; shift::Cdouble; fleet::Int32; reserved::Int32
+end
+const HL1_SWEEP_MAX_LEVELS = 16                                            # RELMC_HL1_SWEEP_MAX_LEVELS
+
+"""
+run_load_sweep (an extension beyond the reference): run_sequential_mc's chronology, same arguments and same chains under one seed,
+against up to 16 load levels in one walk of the chains.  `levels` holds (scale, shift, withheld) triples: the level sees the load
+scale * hourly_load + shift and, if withheld, the fleet without the units `withheld_units` (1-based indices).  Returns per level LOLE,
+EUE, LOLF and the per-year indices (n_levels x years).
+"""
+function run_load_sweep(eng::Engine, capacity::Vector{Float64}, mttf::Vector{Float64}, mttr::Vector{Float64},
+                        hourly_load::Vector{Float64}, years::Integer, levels::Vector{<:Tuple{Real,Real,Bool}};
+                        withheld_units::Vector{<:Integer}=Int[], seed::Integer=1, chains::Integer=1, start::Symbol=:all_up)
+    (years >= 1 && chains >= 1 && years % chains == 0) || throw(ArgumentError("years must be a positive multiple of chains"))
+    n = length(levels)
+    1 <= n <= HL1_SWEEP_MAX_LEVELS || throw(ArgumentError("between 1 and $HL1_SWEEP_MAX_LEVELS levels"))
+    all(1 <= k <= length(capacity) for k in withheld_units) || throw(ArgumentError("withheld_units must be unit indices"))
+    (isempty(withheld_units) && any(l[3] for l in levels)) && throw(ArgumentError("a withheld level needs withheld_units"))
+    check(ccall((:relmc_hl1_seq_load, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}),
+                eng.h, length(capacity), capacity, mttf, mttr, length(hourly_load), hourly_load), eng.h, "relmc_hl1_seq_load")
+    lv = [Hl1SweepLevel(Float64(l[1]), Float64(l[2]), l[3] ? Int32(1) : Int32(0), Int32(0)) for l in levels]
+    mask = zeros(UInt32, 4)
+    for k in withheld_units
+        mask[((k - 1) >> 5) + 1] |= UInt32(1) << ((k - 1) & 31)
+    end
+    yrs = Vector{Hl1SeqYear}(undef, n * years)
+    raw = zeros(UInt8, 56 * n)                                              # relmc_hl1_seq_acc[n], contiguous (Hl1SeqAcc is mutable: a Vector of it holds references)
+    check(ccall((:relmc_hl1_seq_sweep, LIB), Int32,
+                (Ptr{Cvoid}, UInt64, UInt64, Int64, Int32, Int32, Int32, Ptr{Hl1SweepLevel}, Ptr{UInt32}, Ptr{UInt8}, Ptr{Hl1SeqYear}),
+                eng.h, seed, 0, chains, years ÷ chains, HL1_START[start], n, lv, isempty(withheld_units) ? C_NULL : mask, raw, yrs),
+          eng.h, "relmc_hl1_seq_sweep")
+    sums = reshape(reinterpret(Float64, raw), 7, n)                         # rows 2 .. 4: sum_lole, sum_eue, sum_lolf (row 1 is the Int64 years)
+    Y = reshape(yrs, years, n)
+    return (lole_hours_yr=[sums[2, j] / years for j in 1:n], eue_mwh_yr=[sums[3, j] / years for j in 1:n],
+            lolf_occ_yr=[sums[4, j] / years for j in 1:n],
+            year_lole=[Y[y, j].lole for j in 1:n, y in 1:years], year_eue=[Y[y, j].eue for j in 1:n, y in 1:years],
+            year_lolf=[Y[y, j].lolf for j in 1:n, y in 1:years])
+end
+
+# Layout of the sweep level, kept apart from LAYOUT (tests/test_hl1_sweep_host.py compares it with the C compiler's and with ctypes)
+const LAYOUT_HL1_SWEEP = [
+    ("relmc_hl1_sweep_level", 24, [("scale", 0), ("shift", 8), ("fleet", 16), ("reserved", 20)]),
+]
+
 # Layout of the HL1 sequential structs, kept apart from LAYOUT (tests/test_hl1_seq_host.py compares it with the C compiler's)
 const LAYOUT_HL1_SEQ = [
     ("relmc_hl1_seq_year", 24, [("lole", 0), ("eue", 8), ("lolf", 16)]),

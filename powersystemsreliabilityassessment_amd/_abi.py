@@ -132,6 +132,13 @@ class Hl1Event(C.Structure):              # relmc_hl1_event
     _fields_ = [("chain", C.c_int64), ("start_step", C.c_int64), ("duration", C.c_int64), ("energy_mwh", C.c_double), ("peak_mw", C.c_double)]
 
 
+class Hl1SweepLevel(C.Structure):         # relmc_hl1_sweep_level (24 bytes)
+    _fields_ = [("scale", C.c_double), ("shift", C.c_double), ("fleet", C.c_int32), ("reserved", C.c_int32)]
+
+
+HL1_SWEEP_MAX_LEVELS = 16                 # RELMC_HL1_SWEEP_MAX_LEVELS
+
+
 class Hl1EventAcc(C.Structure):           # relmc_hl1_event_acc
     _fields_ = [("years", C.c_int64), ("events", C.c_int64), ("censored", C.c_int64), ("sum_dur", C.c_int64), ("sum_dur2", C.c_int64),
                 ("max_dur", C.c_int64), ("sum_energy", C.c_double), ("sum_energy2", C.c_double), ("max_energy", C.c_double),

@@ -11,7 +11,8 @@
 //   relmc_database.hip   the reference's dedupe and persistent unique-state database on the device
 //   relmc_comm.hip       the path's single collective: RCCL (bound at run time) or a host-supplied all-reduce, with a wall-clock guard
 //   relmc_seq.hip        sequential track (chronology, scaled-load hours, annual indices, the seqMain loop), the HL1 copper sheet, the HL1
-//                        sequential chronology (relmc_hl1_seq), its loss events (relmc_hl1_seq_events, kernels in relmc_event_kernels.h) and
+//                        sequential chronology (relmc_hl1_seq), its loss events (relmc_hl1_seq_events, kernels in relmc_event_kernels.h), its
+//                        load sweep (relmc_hl1_seq_sweep, kernel in relmc_sweep_kernels.h) and
 //                        the record reduction and unit check of every HL1 chronology track
 //   relmc_plan.hip       the HL1 planning model's Monte Carlo (relmc_hl1_plan)
 //   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area); its rows are summed by relmc_seq.hip's record reduction
@@ -181,6 +182,8 @@ struct relmc_ctx {
     struct Hl1Events {
         DevBuf<relmc::Hl1EventRec> rec, part; DevBuf<long long> count, offset; DevBuf<unsigned long long> hist; DevBuf<relmc_hl1_event> list;
     } hl1_events;
+    // load sweep on that model (relmc_hl1_seq_sweep): grow-only per-level year records and reduction partials
+    struct Hl1Sweep { DevBuf<double> years, part; } hl1_sweep;
     // HL1 planning model (relmc_hl1_plan): its own fleet / maintenance / ELUs / load curve, grow-only per-year records, ELU energies,
     // hour loss counts and reduction partials
     bool has_hl1_plan = false;

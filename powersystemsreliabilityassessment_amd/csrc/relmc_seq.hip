@@ -10,6 +10,7 @@
 #include "relmc_ctx.h"
 #include "relmc_seq_kernels.h"
 #include "relmc_event_kernels.h"
+#include "relmc_sweep_kernels.h"
 
 namespace relmc_host {
 
@@ -534,6 +535,72 @@ int32_t relmc_hl1_seq_events(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain
     acc->years = n_chains * years_per_chain;
     acc->events = sum.events; acc->censored = sum.censored; acc->sum_dur = sum.sum_dur; acc->sum_dur2 = sum.sum_dur2; acc->max_dur = sum.max_dur;
     acc->sum_energy = sum.sum_energy; acc->sum_energy2 = sum.sum_energy2; acc->max_energy = sum.max_energy; acc->max_peak = sum.max_peak;
+    return RELMC_OK;
+}
+
+// Load sweep on the chronology above: per chunk of chains one launch that walks every chain once and writes the year records of all
+// levels ([level][chain][year][3]), then relmc_hl1_reduce_kernel over each level's slice.  A chunk holds at most ~4M year records over all
+// levels; a chain's records never depend on the chunk it is in.
+int32_t relmc_hl1_seq_sweep(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain, int32_t start,
+                            int32_t n_levels, const relmc_hl1_sweep_level* levels, const uint32_t* withheld, relmc_hl1_seq_acc* acc,
+                            relmc_hl1_seq_year* years_host)
+{
+    if (!ctx) return RELMC_ERR_INVALID;
+    if (!ctx->has_hl1_seq) return fail(ctx, RELMC_ERR_NO_CASE, "relmc_hl1_seq_sweep: relmc_hl1_seq_load has not been called");
+    if (!acc || !levels || n_chains < 0 || years_per_chain < 1 || (start != RELMC_HL1_START_ALL_UP && start != RELMC_HL1_START_STATIONARY))
+        return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_sweep: bad arguments");
+    if (n_levels < 1 || n_levels > RELMC_HL1_SWEEP_MAX_LEVELS)
+        return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_sweep: n_levels " + std::to_string(n_levels) + " not in 1.." + std::to_string(RELMC_HL1_SWEEP_MAX_LEVELS));
+    auto& S = ctx->hl1_seq;
+    Hl1SweepArgs A; std::memset(&A, 0, sizeof(A));
+    A.n_levels = n_levels;
+    for (int j = 0; j < n_levels; ++j) {
+        const relmc_hl1_sweep_level& v = levels[j];
+        const std::string lvl = "relmc_hl1_seq_sweep: level " + std::to_string(j);
+        if (!std::isfinite(v.scale) || !std::isfinite(v.shift)) return fail(ctx, RELMC_ERR_INVALID, lvl + ": scale / shift not finite");
+        if (v.fleet != 0 && v.fleet != 1) return fail(ctx, RELMC_ERR_INVALID, lvl + ": fleet " + std::to_string(v.fleet) + " is not 0 or 1");
+        if (v.reserved != 0) return fail(ctx, RELMC_ERR_INVALID, lvl + ": reserved must be 0");
+        if (v.fleet == 1 && !withheld) return fail(ctx, RELMC_ERR_INVALID, lvl + ": fleet 1 without a withheld mask");
+        A.lv[j] = v;
+        if (v.fleet == 1) A.fleet1 |= 1u << j;
+    }
+    for (int j = n_levels; j < RELMC_HL1_SWEEP_MAX_LEVELS; ++j) { A.lv[j].scale = 0.0; A.lv[j].shift = -INFINITY; }      // never loses
+    if (withheld)
+        for (int k = S.ngen; k < 128; ++k)
+            if ((withheld[k >> 5] >> (k & 31)) & 1u)
+                return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_sweep: withheld bit " + std::to_string(k) + " at or above ngen = " + std::to_string(S.ngen));
+    if (withheld) std::memcpy(A.withheld, withheld, sizeof(A.withheld));
+    const int64_t total = n_chains * years_per_chain;
+    std::memset(acc, 0, sizeof(*acc) * n_levels);
+    if (n_chains == 0) return RELMC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto& X = ctx->hl1_sweep;
+    const int64_t max_rec = (int64_t)1 << 22;
+    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_chains, max_rec / ((int64_t)years_per_chain * n_levels)));
+    const int64_t rec_max = per * years_per_chain;                                       // records of one level in a launch
+    const int64_t pblocks = hl1_reduce_blocks(rec_max);
+    HIP_TRY(ctx, X.years.grow((size_t)rec_max * 3 * n_levels));
+    HIP_TRY(ctx, X.part.grow((size_t)pblocks * 6 * n_levels));
+    const auto kernel = n_levels <= 1 ? relmc_hl1_sweep_kernel<1> : n_levels <= 4 ? relmc_hl1_sweep_kernel<4>
+                      : n_levels <= 8 ? relmc_hl1_sweep_kernel<8> : relmc_hl1_sweep_kernel<16>;
+    std::vector<double> part, sum((size_t)6 * n_levels, 0.0);
+    double kernel_ms = 0.0;
+    for (int64_t c0 = 0; c0 < n_chains; c0 += per) {
+        const int64_t nc = std::min(per, n_chains - c0), nrec = nc * years_per_chain;
+        (void)hipEventRecord(ctx->ev0, ctx->stream);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
+                           first_chain + (uint64_t)c0, nc, years_per_chain, start, A, X.years.get());
+        if (const int rc = hl1_reduce_queue(ctx, "relmc_hl1_seq_sweep", X.years.get(), nrec, n_levels, X.part.get(), part)) return rc;
+        if (years_host)
+            for (int j = 0; j < n_levels; ++j)
+                HIP_TRY(ctx, hipMemcpyAsync(years_host + (size_t)j * total + c0 * years_per_chain, X.years.get() + (size_t)j * nrec * 3,
+                                            sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
+        if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_seq_sweep: synchronisation failed");
+        kernel_ms += ctx->last_kernel_ms;
+        hl1_reduce_add(part, n_levels, sum.data());
+    }
+    ctx->last_kernel_ms = kernel_ms;
+    for (int j = 0; j < n_levels; ++j) hl1_acc_fill(acc + j, total, sum.data() + (size_t)6 * j);
     return RELMC_OK;
 }
 

@@ -12,6 +12,10 @@ Mirror of the reference's Julia module GeneratingAdequacy/PowerSystemAdequacy.jl
                                                             (relmc_hl1_seq_events)
   run_frequency_duration(gens, load_mw)        generating_adequacy_frequency.jl:53-186: the frequency-and-duration recursion (host)
   frequency_duration_report(analytical, events) LOLE / LOLF / LOLD of the two side by side (text)
+  run_load_sweep(gens, load, years, levels)    an extension beyond the reference: one chronology against up to 16 load levels
+                                                            (relmc_hl1_seq_sweep), and on it the planner's two questions,
+  peak_load_carrying_capability / effective_load_carrying_capability, with analytical_load_sweep / analytical_plcc /
+  analytical_elcc as their exact counterparts through run_analytical, and load_sweep_report for the table
 `rts24_generators()` / `rts24_load()` give the IEEE RTS-79 fleet and the 8736-hour reference load
 curve (Montecarlo_seq/anloducurve.m) whose exact answers are the published LOLE 9.3941 h/yr and
 EUE 1176.29 MWh/yr.
@@ -213,6 +217,294 @@ def compare_results(results) -> str:
              "%-20s | %-10s | %-10s | %-10s" % ("Method", "LOLE(h/yr)", "EUE(MWh)", "Time(s)"), "-" * 60]
     lines += ["%-20s | %-10.4f | %-10.2f | %-10.4f" % (r.method, r.lole_hours_yr, r.eue_mwh_yr, r.computation_time) for r in results]
     lines.append("-" * 60)
+    return "\n".join(lines) + "\n"
+
+
+# ---- load sweep on one chronology: risk curves, PLCC and unit ELCC (an extension beyond the reference) --------------------------------
+@dataclass(frozen=True)
+class SweepLevel:
+    """One level of a load sweep: the load curve scale * load + shift (MW), against the whole fleet or, with withheld=True, against the
+    fleet without the sweep's withheld units."""
+    scale: float = 1.0
+    shift: float = 0.0
+    withheld: bool = False
+
+
+@dataclass
+class LoadSweepResult:
+    """run_load_sweep's result: index j is level j.  The standard errors are over the simulated years (NaN with a single year)."""
+    levels: list
+    withheld_units: tuple
+    years: int
+    lole_hours_yr: np.ndarray
+    eue_mwh_yr: np.ndarray
+    lolf_occ_yr: np.ndarray
+    lole_se: np.ndarray
+    eue_se: np.ndarray
+    lolf_se: np.ndarray
+    year_lole: np.ndarray             # [n_levels, years], chain-major as run_sequential_mc's
+    year_eue: np.ndarray
+    year_lolf: np.ndarray
+    computation_time: float
+
+    def result(self, j: int) -> SequentialReliabilityResult:
+        """Level j as run_sequential_mc would report it (compare_results takes it)."""
+        lv = self.levels[j]
+        lole, eue, lolf = float(self.lole_hours_yr[j]), float(self.eue_mwh_yr[j]), float(self.lolf_occ_yr[j])
+        k = np.arange(10, self.years + 1, 10)
+        history = np.cumsum(self.year_lole[j])[k - 1] / k if k.size else np.zeros(0)
+        name = "Sweep %gx%+g%s" % (lv.scale, lv.shift, " w/o" if lv.withheld else "")
+        return SequentialReliabilityResult(name, lole, eue, self.computation_time, history, lolf_occ_yr=lolf,
+                                           lold_hours=lole / lolf if lolf > 0 else float("nan"), year_lole=self.year_lole[j].copy(),
+                                           year_eue=self.year_eue[j].copy(), year_lolf=self.year_lolf[j].copy())
+
+
+@dataclass
+class AnalyticalLoadSweep:
+    """analytical_load_sweep's result: run_analytical's LOLE and EUE per level."""
+    levels: list
+    withheld_units: tuple
+    lole_hours_yr: np.ndarray
+    eue_mwh_yr: np.ndarray
+    computation_time: float
+
+
+def _sweep_levels(who: str, levels, n_units: int, withheld_units) -> tuple:
+    """The checks of a sweep's levels and withheld units that need no device; returns (list of SweepLevel, sorted tuple of unit indices)."""
+    lv = [x if isinstance(x, SweepLevel) else SweepLevel(*x) for x in levels]
+    if not 1 <= len(lv) <= _abi.HL1_SWEEP_MAX_LEVELS:
+        raise ValueError(f"{who}: between 1 and {_abi.HL1_SWEEP_MAX_LEVELS} levels, not {len(lv)}")
+    for j, x in enumerate(lv):
+        if not (np.isfinite(x.scale) and np.isfinite(x.shift)):
+            raise ValueError(f"{who}: scale / shift of level {j} not finite")
+    wh = [int(k) for k in withheld_units]
+    if len(set(wh)) != len(wh) or any(not 0 <= k < n_units for k in wh):
+        raise ValueError(f"{who}: withheld_units must be distinct unit indices in [0, {n_units}), not {list(withheld_units)}")
+    if not wh and any(x.withheld for x in lv):
+        raise ValueError(f"{who}: a level with withheld=True needs withheld_units")
+    return lv, tuple(sorted(wh))
+
+
+def _seq_shape(who: str, years, chains, start) -> tuple:
+    years, chains = int(years), int(chains)
+    if years < 1 or chains < 1 or years % chains:
+        raise ValueError(f"{who}: years ({years}) must be a positive multiple of chains ({chains})")
+    if start not in _SEQ_START:
+        raise ValueError(f"{who}: start must be one of {sorted(_SEQ_START)}, not {start!r}")
+    return years, chains
+
+
+def _se(x: np.ndarray) -> np.ndarray:
+    """Standard error of the mean along the last axis (NaN with one value)."""
+    n = x.shape[-1]
+    return x.std(axis=-1, ddof=1) / np.sqrt(n) if n > 1 else np.full(x.shape[:-1], np.nan)
+
+
+def run_load_sweep(gens, load: LoadModel, years: int, levels, *, withheld_units=(), seed: int = 1, chains: int = 1, start: str = "all_up",
+                   engine=None) -> LoadSweepResult:
+    """run_sequential_mc's chronology (same arguments, same chains under the same seed) against up to 16 load levels in one walk of the
+    chains.  Level j sees the load scale_j * load + shift_j and, with withheld=True, the fleet without the units `withheld_units`
+    (0-based indices into gens).  Every level sees the same fleet history, so the sampled LOLE and EUE are exactly monotone in a load
+    shift and two levels may be differenced year by year.  Level SweepLevel() is run_sequential_mc bit for bit."""
+    from . import api
+    years, chains = _seq_shape("run_load_sweep", years, chains, start)
+    lv, wh = _sweep_levels("run_load_sweep", levels, len(gens), withheld_units)
+    eng = engine or api.default_engine()
+    t0 = time.time()
+    _seq_model_load(eng, gens, load)
+    n = len(lv)
+    arr = (_abi.Hl1SweepLevel * n)(*[_abi.Hl1SweepLevel(float(x.scale), float(x.shift), 1 if x.withheld else 0, 0) for x in lv])
+    mask = None
+    if wh:
+        mask = (C.c_uint32 * 4)()
+        for k in wh:
+            mask[k >> 5] |= 1 << (k & 31)
+    acc = (_abi.Hl1SeqAcc * n)()
+    yr = np.zeros((n, years, 3))
+    eng._check(eng.L.relmc_hl1_seq_sweep(eng._h, int(seed), 0, chains, years // chains, _SEQ_START[start], n, arr, mask, acc,
+                                         yr.ctypes.data_as(C.POINTER(_abi.Hl1SeqYear))), "relmc_hl1_seq_sweep")
+    mean = lambda f: np.array([getattr(a, f) for a in acc]) / years
+    yl, ye, yf = (np.ascontiguousarray(yr[:, :, q]) for q in range(3))
+    return LoadSweepResult(lv, wh, years, mean("sum_lole"), mean("sum_eue"), mean("sum_lolf"), _se(yl), _se(ye), _se(yf), yl, ye, yf,
+                           time.time() - t0)
+
+
+def _level_model(gens, load: LoadModel, lv: SweepLevel, wh) -> tuple:
+    """The fleet and the load curve of one level, for run_analytical (the kernel rounds scale * load + shift the same way)."""
+    fleet = [g for k, g in enumerate(gens) if not (lv.withheld and k in wh)]
+    return fleet, LoadModel(lv.scale * np.asarray(load.hourly_load, dtype=float) + lv.shift)
+
+
+def analytical_load_sweep(gens, load: LoadModel, levels, withheld_units=(), step_size: float = 1.0) -> AnalyticalLoadSweep:
+    """The exact LOLE / EUE of every level of a sweep, through run_analytical on the level's curve and fleet."""
+    t0 = time.time()
+    lv, wh = _sweep_levels("analytical_load_sweep", levels, len(gens), withheld_units)
+    res = [run_analytical(*_level_model(gens, load, x, wh), step_size=step_size) for x in lv]
+    return AnalyticalLoadSweep(lv, wh, np.array([r.lole_hours_yr for r in res]), np.array([r.eue_mwh_yr for r in res]), time.time() - t0)
+
+
+_SWEEP_METRIC = {"lole": "lole_hours_yr", "eue": "eue_mwh_yr"}
+_SWEEP_MODE = {"shift": lambda x: SweepLevel(1.0, float(x)), "scale": lambda x: SweepLevel(float(x), 0.0)}
+
+
+def _search_args(who: str, metric, mode, bracket, rounds) -> tuple:
+    if metric not in _SWEEP_METRIC:
+        raise ValueError(f"{who}: metric must be one of {sorted(_SWEEP_METRIC)}, not {metric!r}")
+    if mode not in _SWEEP_MODE:
+        raise ValueError(f"{who}: mode must be one of {sorted(_SWEEP_MODE)}, not {mode!r}")
+    lo, hi = (float(b) for b in bracket)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError(f"{who}: bracket must be finite and ascending, not {tuple(bracket)}")
+    if int(rounds) < 1:
+        raise ValueError(f"{who}: rounds must be at least 1")
+    return lo, hi, int(rounds)
+
+
+def _bisect(f, target: float, lo: float, hi: float, tol: float, hi_is_bound: bool, who: str) -> float:
+    """The largest x in [lo, hi] with f(x) <= target, for a non-decreasing f (run_analytical's LOLE is a staircase in the load)."""
+    if f(lo) > target:
+        raise ValueError(f"{who}: the target lies below the bracket")
+    if f(hi) <= target:
+        if hi_is_bound:
+            return hi
+        raise ValueError(f"{who}: the target lies above the bracket")
+    while hi - lo > tol:
+        mid = 0.5 * (lo + hi)
+        if f(mid) <= target:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
+def analytical_plcc(gens, load: LoadModel, target: float, *, metric: str = "lole", mode: str = "shift", bracket, step_size: float = 1.0,
+                    tol: float = 1e-6) -> float:
+    """Peak load carrying capability by bisection on run_analytical: the largest load shift (MW; mode="scale": the largest scale factor)
+    inside `bracket` at which the metric does not exceed `target`.  ValueError if the target lies outside the bracket."""
+    lo, hi, _ = _search_args("analytical_plcc", metric, mode, bracket, 1)
+    f = lambda x: getattr(run_analytical(*_level_model(gens, load, _SWEEP_MODE[mode](x), ()), step_size=step_size), _SWEEP_METRIC[metric])
+    return _bisect(f, float(target), lo, hi, tol, False, "analytical_plcc")
+
+
+def analytical_elcc(gens, load: LoadModel, units, *, metric: str = "lole", bracket=None, step_size: float = 1.0, tol: float = 1e-6) -> float:
+    """Effective load carrying capability of the units `units` (0-based indices into gens) by bisection on run_analytical: the largest
+    load shift (MW) at which the whole fleet is no riskier than the fleet without the units at the unshifted load.  The default bracket
+    is (0, the units' capacity): units that never fail are worth exactly their capacity, which is then returned."""
+    _, wh = _sweep_levels("analytical_elcc", [SweepLevel(withheld=True)], len(gens), units)
+    if not wh:
+        raise ValueError("analytical_elcc: no unit given")
+    default = bracket is None
+    lo, hi, _ = _search_args("analytical_elcc", metric, "shift", (0.0, sum(gens[k].capacity for k in wh)) if default else bracket, 1)
+    attr = _SWEEP_METRIC[metric]
+    target = getattr(run_analytical(*_level_model(gens, load, SweepLevel(withheld=True), wh), step_size=step_size), attr)
+    f = lambda x: getattr(run_analytical(gens, LoadModel(np.asarray(load.hourly_load, dtype=float) + x), step_size=step_size), attr)
+    return _bisect(f, target, lo, hi, tol, default, "analytical_elcc")
+
+
+@dataclass
+class CarryingCapabilityResult:
+    """The result of peak_load_carrying_capability / effective_load_carrying_capability.  `value` is the load shift in MW (the scale factor
+    with mode="scale") at which the sampled metric meets the target, interpolated linearly inside the final pair of levels."""
+    method: str
+    metric: str
+    mode: str
+    value: float
+    std_error: float                  # delta method: the standard error of the metric (difference) over the local slope
+    pair: tuple                       # the final pair of levels (lower, upper) ...
+    pair_metric: tuple                # ... and the sampled metric at them
+    target: float                     # the metric to meet (ELCC: the fleet without the units, at the unshifted load)
+    years: int
+    rounds: int
+    computation_time: float
+    target_year: list = field(default_factory=list)    # ELCC: the per-year metric of the target level, one array per round
+
+
+def _pick_pair(who: str, m: np.ndarray, target: float) -> int:
+    """Index i of the adjacent pair (i, i + 1) of the non-decreasing m that brackets the target."""
+    if not m[0] <= target <= m[-1]:
+        raise ValueError(f"{who}: the target {target:g} lies outside the bracket (the metric runs from {m[0]:g} to {m[-1]:g} over it)")
+    return min(int(np.searchsorted(m, target, side="right")) - 1, m.size - 2)
+
+
+def _interpolate(x: np.ndarray, m: np.ndarray, i: int, target: float) -> tuple:
+    """(value, weight of the upper level, slope) of the linear interpolation inside the pair (i, i + 1)."""
+    dm, dx = m[i + 1] - m[i], x[i + 1] - x[i]
+    t = (target - m[i]) / dm if dm > 0 else 0.0
+    return float(x[i] + t * dx), float(t), float(dm / dx)
+
+
+def peak_load_carrying_capability(gens, load: LoadModel, target: float, years: int, *, metric: str = "lole", mode: str = "shift", bracket,
+                                  rounds: int = 3, seed: int = 1, chains: int = 1, start: str = "all_up", engine=None) -> CarryingCapabilityResult:
+    """How much load the fleet carries at the risk `target` (LOLE in h/yr or EUE in MWh/yr): the load shift in MW (mode="scale": the factor
+    on the load curve) at which the sampled metric meets the target.  Each round sweeps 16 equally spaced levels over the bracket under
+    the same seed -- the sampled metric is then exactly monotone along them -- and keeps the adjacent pair that brackets the target; the
+    last pair is interpolated linearly.  ValueError if the target lies outside the bracket."""
+    who = "peak_load_carrying_capability"
+    years, chains = _seq_shape(who, years, chains, start)
+    lo, hi, rounds = _search_args(who, metric, mode, bracket, rounds)
+    t0 = time.time()
+    target = float(target)
+    for _ in range(rounds):
+        x = np.linspace(lo, hi, _abi.HL1_SWEEP_MAX_LEVELS)
+        sw = run_load_sweep(gens, load, years, [_SWEEP_MODE[mode](v) for v in x], seed=seed, chains=chains, start=start, engine=engine)
+        m = getattr(sw, _SWEEP_METRIC[metric])
+        i = _pick_pair(who, m, target)
+        lo, hi = float(x[i]), float(x[i + 1])
+    value, t, slope = _interpolate(x, m, i, target)
+    se_m = getattr(sw, metric + "_se")[i + 1 if t > 0.5 else i]
+    return CarryingCapabilityResult("Sequential MC sweep", metric, mode, value, float(se_m / slope) if slope > 0 else float("inf"), (lo, hi),
+                                    (float(m[i]), float(m[i + 1])), target, years, rounds, time.time() - t0)
+
+
+def effective_load_carrying_capability(gens, load: LoadModel, units, years: int, *, metric: str = "lole", bracket=None, rounds: int = 3,
+                                       seed: int = 1, chains: int = 1, start: str = "all_up", engine=None) -> CarryingCapabilityResult:
+    """What the units `units` (0-based indices into gens) are worth in load: the load shift in MW after which the whole fleet is as risky
+    as the fleet without them at the unshifted load.  The search of peak_load_carrying_capability with 15 shifted levels of the whole
+    fleet and one level of the fleet without the units per round; that level is the target and is bitwise the same in every round.  Both
+    fleets see the same draws, so the standard error comes from the per-year paired differences between the interpolated pair and the
+    target level, over the slope.  The default bracket is (0, the units' capacity)."""
+    who = "effective_load_carrying_capability"
+    years, chains = _seq_shape(who, years, chains, start)
+    _, wh = _sweep_levels(who, [SweepLevel(withheld=True)], len(gens), units)
+    if not wh:
+        raise ValueError(f"{who}: no unit given")
+    lo, hi, rounds = _search_args(who, metric, "shift", (0.0, sum(gens[k].capacity for k in wh)) if bracket is None else bracket, rounds)
+    t0 = time.time()
+    n = _abi.HL1_SWEEP_MAX_LEVELS - 1
+    per_year = "year_" + metric
+    target_year = []
+    for _ in range(rounds):
+        x = np.linspace(lo, hi, n)
+        sw = run_load_sweep(gens, load, years, [SweepLevel(1.0, float(v)) for v in x] + [SweepLevel(withheld=True)], withheld_units=wh,
+                            seed=seed, chains=chains, start=start, engine=engine)
+        m, target = getattr(sw, _SWEEP_METRIC[metric])[:n], float(getattr(sw, _SWEEP_METRIC[metric])[n])
+        target_year.append(getattr(sw, per_year)[n].copy())
+        i = _pick_pair(who, m, target)
+        lo, hi = float(x[i]), float(x[i + 1])
+    value, t, slope = _interpolate(x, m, i, target)
+    yr = getattr(sw, per_year)
+    se_d = float(_se((1.0 - t) * yr[i] + t * yr[i + 1] - yr[n]))
+    return CarryingCapabilityResult("Sequential MC sweep", metric, "shift", value, se_d / slope if slope > 0 else float("inf"), (lo, hi),
+                                    (float(m[i]), float(m[i + 1])), target, years, rounds, time.time() - t0, target_year)
+
+
+def load_sweep_report(sweep: LoadSweepResult, analytical: AnalyticalLoadSweep = None) -> str:
+    """The levels of a sweep as a text table in compare_results' style, beside the analytic values if given."""
+    rule = "=" * 42
+    head = "%-5s | %-8s | %-10s | %-5s | %-20s | %-22s | %-12s" % ("Level", "Scale", "Shift(MW)", "Fleet", "LOLE(h/yr) +- SE", "EUE(MWh/yr) +- SE", "LOLF(occ/yr)")
+    if analytical is not None:
+        head += " | %-10s | %-10s" % ("LOLE exact", "EUE exact")
+    lines = [rule, "          LOAD SWEEP SUMMARY", rule, head, "-" * len(head)]
+    for j, lv in enumerate(sweep.levels):
+        ln = "%-5d | %-8.4f | %-10.2f | %-5s | %-9.4f +- %-7.4f | %-11.2f +- %-7.2f | %-12.4f" % (
+            j, lv.scale, lv.shift, "w/o" if lv.withheld else "all", sweep.lole_hours_yr[j], sweep.lole_se[j], sweep.eue_mwh_yr[j],
+            sweep.eue_se[j], sweep.lolf_occ_yr[j])
+        if analytical is not None:
+            ln += " | %-10.4f | %-10.2f" % (analytical.lole_hours_yr[j], analytical.eue_mwh_yr[j])
+        lines.append(ln)
+    lines.append("-" * len(head))
+    if sweep.withheld_units:
+        lines.append("w/o: the fleet without units %s" % list(sweep.withheld_units))
     return "\n".join(lines) + "\n"
 
 

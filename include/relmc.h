@@ -625,6 +625,133 @@ int32_t relmc_case_order_hint(relmc_ctx* ctx, const int32_t* order, int32_t n);
  * leaves no trace in relmc_retry_stats or kernel_seconds.  */
 int32_t relmc_nsq_run(relmc_ctx* ctx, const relmc_nsq_opts* opts, relmc_nsq_result* result);
 
+/* ---- importance sampling for the non-sequential HL2 Monte Carlo: cross-entropy tilt of the component unavailabilities (an extension beyond the reference) ---- */
+/* nsqMain counts every sample with weight 1; away from the annual peak almost every sample is a zero.  Here the states are drawn under tilted
+ * unavailabilities and every sample carries its likelihood ratio W, so that the weighted estimators stay unbiased for the case's own law.
+ * Tilt.  unavail_is[ng+nl] = the sampling probabilities; NULL = the case's own.  thr_is[k] is derived from unavail_is[k] by exactly the rule
+ *   relmc_case_load uses for thr[k] (relmc_case_thresholds): floor(u * 2^32), at most 2^32 - 1, and 0 where always_up.  A call is refused with
+ *   RELMC_ERR_INVALID (relmc_last_error naming the component where the call takes a context) if an entry is not finite or outside [0, 1], or if
+ *   thr_is[k] == 0 while thr[k] > 0: the tilted law must cover the nominal one.  A refused call changes nothing.
+ * Draws.  relmc_mc_sampling's, word for word: Philox4x32-10, ctr = (index lo, index hi, k >> 2, 0), key = seed; component k is down iff word
+ *   k & 3 < thr_is[k] (the spare words of the last block are ignored).  So with thr_is == thr the states are bitwise relmc_mc_sampling's, and
+ *   with thr_is >= thr everywhere the down set of sample i contains the down set of the nominal sample i.
+ * Weight.  From the realised probabilities thr / 2^32, not from the doubles that were passed in:
+ *   r_dn[k] = (double)thr[k] / (double)thr_is[k]   (never read when thr_is[k] == 0: stored as 1.0)
+ *   r_up[k] = (double)(2^32 - thr[k]) / (double)(2^32 - thr_is[k])
+ *   each one fp64 division of exactly representable integers, done on the host.  W_i = the product over k ascending of r_dn[k] where component
+ *   k of sample i is down and r_up[k] where it is up, starting from 1.0, one rounded multiply per component (no FMA): thr_is == thr gives
+ *   W == 1.0 exactly, and a NumPy model reproduces every W bit for bit.  W is a plain fp64 product: an absurd tilt (hundreds of components at
+ *   ratios far from 1) may underflow it to 0; relmc_nsq_is_tune's clamp [thr / 2^32, q_max] keeps it far from that.
+ * Accumulators (relmc_is_acc), x_k = 1 iff component k is down, fail = dns > 1e-4 (nsqMain.m:270).  Every floating sum is taken in a fixed
+ *   order: a repeated call is bitwise identical; splitting a range into calls changes the doubles only by rounding and the integers not at all. */
+typedef struct {
+    int64_t n;                /* samples evaluated                                   */
+    int64_t n_fail;           /* raw count of dns > 1e-4                             */
+    int64_t n_singular, n_infeasible, n_nonconverged, sum_iters;   /* as relmc_acc's */
+    double sum_w, sum_w2;     /* sum W, sum W^2                                      */
+    double sum_wfail, sum_w2fail;   /* sum W fail, sum W^2 fail                      */
+    double sum_wdns, sum_w2dns2;    /* sum W dns, sum (W dns)^2                      */
+    double comp_wfail[RELMC_MAX_COMP];   /* sum W fail x_k                           */
+    double comp_wdns[RELMC_MAX_COMP];    /* sum W dns x_k                            */
+    double sum_wnodal[RELMC_MAX_BUS];    /* sum W nodal_dns                          */
+} relmc_is_acc;
+/* relmc_nsq_indices' formulas with W dns in place of dns and W fail in place of fail; with every W = 1 each field the two structs share equals
+ * relmc_nsq_indices' output. */
+typedef struct {
+    int64_t n;
+    double edns;              /* sum_wdns / n                                        */
+    double lole;              /* plc * hours_per_year                                */
+    double plc;               /* sum_wfail / n                                       */
+    double beta;              /* relmc_nsq_indices' expression fed sum_wdns, sum_w2dns2 */
+    double eens;              /* edns * hours_per_year                               */
+    double mean_iters;
+    double beta_plc;          /* the same expression fed sum_wfail, sum_w2fail       */
+    double mean_w;            /* sum_w / n: 1 in expectation                         */
+    double ess;               /* effective sample size sum_w^2 / sum_w2              */
+    double nodal_eens[RELMC_MAX_BUS];        /* sum_wnodal / n                       */
+    double comp_importance[RELMC_MAX_COMP];  /* comp_wfail / sum_wfail, 0 without a failure */
+} relmc_is_indices;
+/* Host only (no context, no GPU): the validation above and the three tables [ncomp].  thr = relmc_case_thresholds' output; always_up and
+ * unavail_is may be NULL (nothing forced / the nominal law: thr_is = thr).  Returns RELMC_ERR_INVALID for a refused tilt;
+ * bad_component_out (optional) = the offending component, -1 if none. */
+int32_t relmc_is_ratios(int32_t ncomp, const uint32_t* thr, const uint8_t* always_up, const double* unavail_is,
+                        uint32_t* thr_is_out, double* r_dn_out, double* r_up_out, int32_t* bad_component_out);
+/* States eqstatus[n x (ng+nl)] (row-major, 1 = failed) and weights W[n] of samples [first_index, first_index + n); either output may be NULL. */
+int32_t relmc_is_sampling(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t n, const double* unavail_is,
+                          uint8_t* eqstatus_host, double* weight_host);
+int32_t relmc_is_sampling_dev(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t n, const double* unavail_is,
+                              uint8_t* eqstatus_dev, double* weight_dev);
+/* Samples the range under the tilt, evaluates the states through relmc_mc_simulation_dev (retry ladder included) and reduces, in launches of
+ * at most 2^20 samples so that the per-sample buffers stay bounded.  relmc_last_kernel_ms covers sampling, every evaluation launch and the
+ * reductions.  opts->screen is ignored: relmc_mc_simulation solves every state it is handed (certifying tilted samples is a follow-up).
+ * n == 0 zeroes *out; RELMC_ERR_NO_CASE before relmc_case_load. */
+int32_t relmc_nsq_is_accumulate(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t n, const relmc_solver_opts* opts,
+                                const double* unavail_is, relmc_is_acc* out);
+void relmc_is_acc_zero(relmc_is_acc* acc);
+void relmc_is_acc_merge(relmc_is_acc* dst, const relmc_is_acc* src);
+void relmc_nsq_is_indices(const relmc_is_acc* acc, int32_t nb, int32_t ncomp, double hours_per_year, relmc_is_indices* out);
+/* The cross-entropy tuner.  Pass t = 0, 1, ... samples the indices [t * n_pilot, (t + 1) * n_pilot) of `seed` under the current tilt q (pass 0:
+ * the nominal p_k = thr[k] / 2^32) and evaluates them.  F = its samples with dns > 1e-4.
+ *   |F| >= min_elite (a FINAL pass): elites = F with weight e_i = W_i (objective 0, PLC) or W_i dns_i (objective 1, EDNS).
+ *   otherwise (a LEVEL pass): elites = F plus the ceil(rho * n_pilot) - |F| non-failed samples of largest generation shortfall
+ *     m_i = total_load - sum over the in-service real generators, ascending, of max(inj_pmax, 0)   (ties: the lower index), e_i = W_i.
+ *   update: v_k = sum_i e_i x_ik / sum_i e_i (sum_i e_i on the host in sample order, the column sums on the device, by the kernel that produces
+ *     comp_wfail / comp_wdns);  q_k <- min(alpha v_k + (1 - alpha) q_k, q_max), then max(., p_k), and 0 where always_up: never below nominal.
+ *     A pass without an elite of positive weight leaves q as it is.
+ * Stops after final_iters final passes or max_iters passes; never reaching a final pass is reported (report->final_passes == 0), not an error.
+ * Deterministic in (seed, options, case): a repeated call is bitwise identical.  unavail_is_out[ng+nl] = the tilt, report optional. */
+#define RELMC_IS_TUNE_MAX_PASSES 32
+typedef struct {
+    uint64_t seed;
+    int64_t n_pilot;          /* 20000 */
+    int32_t max_iters;        /* 5, at most RELMC_IS_TUNE_MAX_PASSES */
+    int32_t final_iters;      /* 2 */
+    int64_t min_elite;        /* 100 */
+    double rho;               /* 0.1, in (0, 1] */
+    int32_t objective;        /* 0 = PLC, 1 = EDNS */
+    int32_t reserved;         /* 0 */
+    double alpha;             /* smoothing, 1.0, in (0, 1] */
+    double q_max;             /* 0.5, in (0, 1] */
+    relmc_solver_opts solver;
+} relmc_is_tune_opts;
+typedef struct {
+    int32_t passes;           /* passes run */
+    int32_t final_passes;     /* how many of them were final */
+    int64_t n_fail[RELMC_IS_TUNE_MAX_PASSES];      /* |F| per pass */
+    int64_t n_elite[RELMC_IS_TUNE_MAX_PASSES];     /* elites per pass */
+    double sum_e[RELMC_IS_TUNE_MAX_PASSES];        /* sum of e_i per pass */
+    double level[RELMC_IS_TUNE_MAX_PASSES];        /* level pass: the smallest shortfall among the added elites (MW); NaN for a final pass or none added */
+    double kernel_seconds, wall_seconds;
+} relmc_is_tune_report;
+void relmc_is_tune_opts_default(relmc_is_tune_opts* opts);
+int32_t relmc_nsq_is_tune(relmc_ctx* ctx, const relmc_is_tune_opts* opts, double* unavail_is_out, relmc_is_tune_report* report);
+/* Batches of `batch` samples of `seed` from index 0 under unavail_is until beta <= beta_limit or max_samples; histories optional, one entry
+ * per batch, as in relmc_nsq_run.  Single-rank: RELMC_ERR_UNSUPPORTED with a communicator of more than one rank in the context. */
+typedef struct {
+    double beta_limit;        /* 0.0017 */
+    int64_t max_samples;      /* 1e5    */
+    int64_t batch;            /* 1000   */
+    uint64_t seed;
+    double hours_per_year;    /* 8760   */
+    relmc_solver_opts solver;
+    const double* unavail_is; /* [ng+nl] or NULL = nominal */
+    int64_t history_cap;
+    double* beta_history;
+    double* edns_history;
+    double* plc_history;
+} relmc_is_run_opts;
+typedef struct {
+    relmc_is_acc acc;
+    relmc_is_indices idx;
+    int64_t checkpoints;      /* history entries written = min(batches, history_cap) */
+    int64_t batches;
+    int32_t converged;        /* beta <= beta_limit */
+    int32_t reserved;
+    double wall_seconds, kernel_seconds;
+} relmc_is_run_result;
+void relmc_is_run_opts_default(relmc_is_run_opts* opts);
+int32_t relmc_nsq_is_run(relmc_ctx* ctx, const relmc_is_run_opts* opts, relmc_is_run_result* result);
+
 #ifdef __cplusplus
 }
 #endif

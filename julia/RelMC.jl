@@ -645,6 +645,130 @@ const LAYOUT_HL1_PLAN = [
     ("relmc_hl1_seq_acc", 56, [("years", 0), ("sum_lole", 8), ("sum_eue", 16), ("sum_lolf", 24), ("sum_lole2", 32), ("sum_eue2", 40), ("sum_lolf2", 48)]),
 ]
 
+# ---- importance sampling for the non-sequential track (include/relmc.h: cross-entropy tilt of the unavailabilities) ----------------
+
+const IS_TUNE_MAX_PASSES = 32                                                 # RELMC_IS_TUNE_MAX_PASSES
+
+"relmc_is_acc (include/relmc.h): the weighted accumulators of a tilted sample range"
+mutable struct IsAcc
+    n::Int64; n_fail::Int64; n_singular::Int64; n_infeasible::Int64; n_nonconverged::Int64; sum_iters::Int64
+    sum_w::Cdouble; sum_w2::Cdouble; sum_wfail::Cdouble; sum_w2fail::Cdouble; sum_wdns::Cdouble; sum_w2dns2::Cdouble
+    comp_wfail::NTuple{MAX_COMP,Cdouble}
+    comp_wdns::NTuple{MAX_COMP,Cdouble}
+    sum_wnodal::NTuple{MAX_BUS,Cdouble}
+    IsAcc() = new()
+end
+
+"relmc_is_indices (include/relmc.h)"
+mutable struct IsIndices
+    n::Int64
+    edns::Cdouble; lole::Cdouble; plc::Cdouble; beta::Cdouble; eens::Cdouble; mean_iters::Cdouble
+    beta_plc::Cdouble; mean_w::Cdouble; ess::Cdouble
+    nodal_eens::NTuple{MAX_BUS,Cdouble}
+    comp_importance::NTuple{MAX_COMP,Cdouble}
+    IsIndices() = new()
+end
+
+"relmc_is_tune_opts (include/relmc.h): the options of the cross-entropy tuner"
+struct IsTuneOpts
+    seed::UInt64; n_pilot::Int64; max_iters::Int32; final_iters::Int32; min_elite::Int64; rho::Cdouble
+    objective::Int32; reserved::Int32; alpha::Cdouble; q_max::Cdouble
+    solver::SolverOptsC
+end
+
+"relmc_is_tune_report (include/relmc.h)"
+mutable struct IsTuneReport
+    passes::Int32; final_passes::Int32
+    n_fail::NTuple{IS_TUNE_MAX_PASSES,Int64}; n_elite::NTuple{IS_TUNE_MAX_PASSES,Int64}
+    sum_e::NTuple{IS_TUNE_MAX_PASSES,Cdouble}; level::NTuple{IS_TUNE_MAX_PASSES,Cdouble}
+    kernel_seconds::Cdouble; wall_seconds::Cdouble
+    IsTuneReport() = new()
+end
+
+"relmc_is_run_opts (include/relmc.h)"
+struct IsRunOpts
+    beta_limit::Cdouble; max_samples::Int64; batch::Int64; seed::UInt64; hours_per_year::Cdouble
+    solver::SolverOptsC
+    unavail_is::Ptr{Cdouble}
+    history_cap::Int64
+    beta_history::Ptr{Cdouble}; edns_history::Ptr{Cdouble}; plc_history::Ptr{Cdouble}
+end
+
+# relmc_is_run_result is read out of a byte buffer at these offsets (IsAcc and IsIndices are mutable mirrors and cannot be embedded)
+const IS_ACC_BYTES = 8 * (12 + 2 * MAX_COMP + MAX_BUS)
+const IS_INDICES_BYTES = 8 * (10 + MAX_BUS + MAX_COMP)
+const IS_RUN_TAIL = IS_ACC_BYTES + IS_INDICES_BYTES                           # checkpoints, batches, converged, reserved, wall_seconds, kernel_seconds
+const IS_RUN_BYTES = IS_RUN_TAIL + 40
+
+tilt_ptr(eng::Engine, unavail_is) = unavail_is === nothing ? Ptr{Cdouble}(C_NULL) :
+    (length(unavail_is) == eng.sys.ng + eng.sys.nl ? pointer(unavail_is) : throw(ArgumentError("unavail_is must have Ng+Nl entries")))
+
+"(eqstatus n x (Ng+Nl), W): relmc_mc_sampling's draws against the tilted unavailabilities (`nothing` = the case's own) and their likelihood ratios."
+function is_sampling(eng::Engine, seed::Integer, first_index::Integer, n::Integer; unavail_is::Union{Nothing,Vector{Float64}}=nothing)
+    ncomp = eng.sys.ng + eng.sys.nl
+    out = Matrix{UInt8}(undef, ncomp, n); w = Vector{Float64}(undef, n)
+    GC.@preserve unavail_is check(ccall((:relmc_is_sampling, LIB), Int32, (Ptr{Cvoid}, UInt64, UInt64, Int64, Ptr{Cdouble}, Ptr{UInt8}, Ptr{Cdouble}),
+                                        eng.h, seed, first_index, n, tilt_ptr(eng, unavail_is), out, w), eng.h, "relmc_is_sampling")
+    return permutedims(out), w
+end
+
+"Tilted samples [first_index, first_index+n), evaluated and reduced with their weights (relmc_nsq_is_accumulate)."
+function nsq_is_accumulate(eng::Engine, seed::Integer, first_index::Integer, n::Integer; unavail_is::Union{Nothing,Vector{Float64}}=nothing,
+                           mpopt::SolverOpts=mpoption())
+    acc = IsAcc()
+    GC.@preserve unavail_is check(ccall((:relmc_nsq_is_accumulate, LIB), Int32,
+                                        (Ptr{Cvoid}, UInt64, UInt64, Int64, Ref{SolverOpts}, Ptr{Cdouble}, Ref{IsAcc}),
+                                        eng.h, seed, first_index, n, mpopt, tilt_ptr(eng, unavail_is), acc), eng.h, "relmc_nsq_is_accumulate")
+    return acc
+end
+
+function is_indices(eng::Engine, acc::IsAcc; hours_per_year=8760.0)
+    out = IsIndices()
+    ccall((:relmc_nsq_is_indices, LIB), Cvoid, (Ref{IsAcc}, Int32, Int32, Cdouble, Ref{IsIndices}),
+          acc, eng.sys.nb, eng.sys.ng + eng.sys.nl, hours_per_year, out)
+    return out
+end
+
+"The cross-entropy tuner (relmc_nsq_is_tune): (unavail_is, IsTuneReport).  objective :plc or :edns."
+function is_tune(eng::Engine; objective::Symbol=:edns, seed::Integer=1, n_pilot::Integer=20000, max_iters::Integer=5, final_iters::Integer=2,
+                 min_elite::Integer=100, rho::Real=0.1, alpha::Real=1.0, q_max::Real=0.5, mpopt::SolverOpts=mpoption())
+    o = IsTuneOpts(seed, n_pilot, max_iters, final_iters, min_elite, rho, objective == :plc ? Int32(0) : Int32(1), Int32(0), alpha, q_max,
+                   SolverOptsC(mpopt))
+    q = zeros(Float64, eng.sys.ng + eng.sys.nl); rep = IsTuneReport()
+    check(ccall((:relmc_nsq_is_tune, LIB), Int32, (Ptr{Cvoid}, Ref{IsTuneOpts}, Ptr{Cdouble}, Ref{IsTuneReport}), eng.h, Ref(o), q, rep),
+          eng.h, "relmc_nsq_is_tune")
+    return q, rep
+end
+
+"Batches under the tilt until beta <= beta_limit or max_samples (relmc_nsq_is_run); tunes first when no tilt is given."
+function nsq_is_run(eng::Engine; unavail_is::Union{Nothing,Vector{Float64}}=nothing, beta_limit::Real=0.0017, max_samples::Integer=100000,
+                    batch::Integer=1000, seed::Integer=1, mpopt::SolverOpts=mpoption(), hours_per_year::Real=8760.0)
+    q = unavail_is === nothing ? is_tune(eng; seed=seed + 1, mpopt=mpopt)[1] : unavail_is
+    ncp = cld(max_samples, batch)
+    hb = zeros(ncp); he = zeros(ncp); hp = zeros(ncp)
+    raw = zeros(UInt8, IS_RUN_BYTES)
+    GC.@preserve q hb he hp begin
+        o = IsRunOpts(beta_limit, max_samples, batch, seed, hours_per_year, SolverOptsC(mpopt), tilt_ptr(eng, q), ncp, pointer(hb), pointer(he), pointer(hp))
+        check(ccall((:relmc_nsq_is_run, LIB), Int32, (Ptr{Cvoid}, Ref{IsRunOpts}, Ptr{UInt8}), eng.h, Ref(o), raw), eng.h, "relmc_nsq_is_run")
+    end
+    f64(off) = reinterpret(Float64, raw[off + 1:off + 8])[1]; i64(off) = reinterpret(Int64, raw[off + 1:off + 8])[1]
+    k = i64(IS_RUN_TAIL)
+    return (n=i64(IS_ACC_BYTES), edns=f64(IS_ACC_BYTES + 8), lole=f64(IS_ACC_BYTES + 16), plc=f64(IS_ACC_BYTES + 24), beta=f64(IS_ACC_BYTES + 32),
+            beta_plc=f64(IS_ACC_BYTES + 56), mean_w=f64(IS_ACC_BYTES + 64), ess=f64(IS_ACC_BYTES + 72),
+            converged=reinterpret(Int32, raw[IS_RUN_TAIL + 17:IS_RUN_TAIL + 20])[1] != 0, wall_seconds=f64(IS_RUN_TAIL + 24),
+            kernel_seconds=f64(IS_RUN_TAIL + 32), beta_history=hb[1:k], edns_history=he[1:k], plc_history=hp[1:k], unavail_is=q)
+end
+
+# Layout of the importance-sampling structs, kept apart from LAYOUT (tests/test_importance_host.py compares it with the C compiler's and with ctypes)
+const LAYOUT_IS = [
+    ("relmc_is_acc", IS_ACC_BYTES, [("n", 0), ("sum_iters", 40), ("sum_w", 48), ("sum_w2dns2", 88), ("comp_wfail", 96), ("comp_wdns", 96 + 8 * MAX_COMP), ("sum_wnodal", 96 + 16 * MAX_COMP)]),
+    ("relmc_is_indices", IS_INDICES_BYTES, [("n", 0), ("edns", 8), ("mean_iters", 48), ("beta_plc", 56), ("mean_w", 64), ("ess", 72), ("nodal_eens", 80), ("comp_importance", 80 + 8 * MAX_BUS)]),
+    ("relmc_is_tune_opts", 152, [("seed", 0), ("n_pilot", 8), ("max_iters", 16), ("final_iters", 20), ("min_elite", 24), ("rho", 32), ("objective", 40), ("reserved", 44), ("alpha", 48), ("q_max", 56), ("solver", 64)]),
+    ("relmc_is_tune_report", 16 + 32 * IS_TUNE_MAX_PASSES + 8, [("passes", 0), ("final_passes", 4), ("n_fail", 8), ("n_elite", 8 + 8 * IS_TUNE_MAX_PASSES), ("sum_e", 8 + 16 * IS_TUNE_MAX_PASSES), ("level", 8 + 24 * IS_TUNE_MAX_PASSES), ("kernel_seconds", 8 + 32 * IS_TUNE_MAX_PASSES), ("wall_seconds", 16 + 32 * IS_TUNE_MAX_PASSES)]),
+    ("relmc_is_run_opts", 168, [("beta_limit", 0), ("max_samples", 8), ("batch", 16), ("seed", 24), ("hours_per_year", 32), ("solver", 40), ("unavail_is", 128), ("history_cap", 136), ("beta_history", 144), ("edns_history", 152), ("plc_history", 160)]),
+    ("relmc_is_run_result", IS_RUN_BYTES, [("acc", 0), ("idx", IS_ACC_BYTES), ("checkpoints", IS_RUN_TAIL), ("batches", IS_RUN_TAIL + 8), ("converged", IS_RUN_TAIL + 16), ("reserved", IS_RUN_TAIL + 20), ("wall_seconds", IS_RUN_TAIL + 24), ("kernel_seconds", IS_RUN_TAIL + 32)]),
+]
+
 # Layout table of the plain-C structs this file mirrors: tests/test_c_abi.py compiles a C program printing sizeof / offsetof of
 # include/relmc.h's structs and compares with these numbers and with the ctypes mirror, so drift in either mirror is caught
 # without a Julia installation.  (name, sizeof, [(field, offset) ...])

@@ -174,6 +174,67 @@ class DbStats(C.Structure):
     _fields_ = [("rows", C.c_int64), ("samples", C.c_int64), ("new_rows", C.c_int64), ("batch_distinct", C.c_int64)]
 
 
+IS_TUNE_MAX_PASSES = 32                   # RELMC_IS_TUNE_MAX_PASSES
+
+
+class IsAcc(C.Structure):                 # relmc_is_acc
+    _fields_ = [
+        ("n", C.c_int64), ("n_fail", C.c_int64), ("n_singular", C.c_int64),
+        ("n_infeasible", C.c_int64), ("n_nonconverged", C.c_int64), ("sum_iters", C.c_int64),
+        ("sum_w", C.c_double), ("sum_w2", C.c_double), ("sum_wfail", C.c_double), ("sum_w2fail", C.c_double),
+        ("sum_wdns", C.c_double), ("sum_w2dns2", C.c_double),
+        ("comp_wfail", C.c_double * RELMC_MAX_COMP), ("comp_wdns", C.c_double * RELMC_MAX_COMP),
+        ("sum_wnodal", C.c_double * RELMC_MAX_BUS),
+    ]
+
+
+class IsIndices(C.Structure):             # relmc_is_indices
+    _fields_ = [
+        ("n", C.c_int64),
+        ("edns", C.c_double), ("lole", C.c_double), ("plc", C.c_double), ("beta", C.c_double),
+        ("eens", C.c_double), ("mean_iters", C.c_double),
+        ("beta_plc", C.c_double), ("mean_w", C.c_double), ("ess", C.c_double),
+        ("nodal_eens", C.c_double * RELMC_MAX_BUS),
+        ("comp_importance", C.c_double * RELMC_MAX_COMP),
+    ]
+
+
+class IsTuneOpts(C.Structure):            # relmc_is_tune_opts
+    _fields_ = [
+        ("seed", C.c_uint64), ("n_pilot", C.c_int64), ("max_iters", C.c_int32), ("final_iters", C.c_int32),
+        ("min_elite", C.c_int64), ("rho", C.c_double), ("objective", C.c_int32), ("reserved", C.c_int32),
+        ("alpha", C.c_double), ("q_max", C.c_double), ("solver", SolverOpts),
+    ]
+
+
+class IsTuneReport(C.Structure):          # relmc_is_tune_report
+    _fields_ = [
+        ("passes", C.c_int32), ("final_passes", C.c_int32),
+        ("n_fail", C.c_int64 * IS_TUNE_MAX_PASSES), ("n_elite", C.c_int64 * IS_TUNE_MAX_PASSES),
+        ("sum_e", C.c_double * IS_TUNE_MAX_PASSES), ("level", C.c_double * IS_TUNE_MAX_PASSES),
+        ("kernel_seconds", C.c_double), ("wall_seconds", C.c_double),
+    ]
+
+
+class IsRunOpts(C.Structure):             # relmc_is_run_opts
+    _fields_ = [
+        ("beta_limit", C.c_double), ("max_samples", C.c_int64), ("batch", C.c_int64),
+        ("seed", C.c_uint64), ("hours_per_year", C.c_double),
+        ("solver", SolverOpts),
+        ("unavail_is", c_double_p),
+        ("history_cap", C.c_int64),
+        ("beta_history", c_double_p), ("edns_history", c_double_p), ("plc_history", c_double_p),
+    ]
+
+
+class IsRunResult(C.Structure):           # relmc_is_run_result
+    _fields_ = [
+        ("acc", IsAcc), ("idx", IsIndices),
+        ("checkpoints", C.c_int64), ("batches", C.c_int64), ("converged", C.c_int32), ("reserved", C.c_int32),
+        ("wall_seconds", C.c_double), ("kernel_seconds", C.c_double),
+    ]
+
+
 assert C.sizeof(Acc) == (Acc.N_INT + Acc.N_DBL) * 8
 
 

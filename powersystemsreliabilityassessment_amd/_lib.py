@@ -29,6 +29,8 @@ EXPORTS = [
     "relmc_seq_load", "relmc_seq_mcsampling", "relmc_seq_mcsimulation", "relmc_seq_years", "relmc_retry_stats", "relmc_retry_overflow", "relmc_retry_dense_stats", "relmc_case_order",
     "relmc_case_order_hint", "relmc_tune_order",
     "relmc_comm_set_timeout", "relmc_comm_allreduce_f64", "relmc_comm_set_host_allreduce_f64", "relmc_device_pci_bus_id", "relmc_seq_opts_default", "relmc_seq_run",
+    "relmc_is_ratios", "relmc_is_sampling", "relmc_is_sampling_dev", "relmc_nsq_is_accumulate", "relmc_is_acc_zero", "relmc_is_acc_merge", "relmc_nsq_is_indices",
+    "relmc_is_tune_opts_default", "relmc_nsq_is_tune", "relmc_is_run_opts_default", "relmc_nsq_is_run",
 ]
 
 
@@ -190,6 +192,28 @@ def load():
     L.relmc_retry_overflow.restype = C.c_int32
     L.relmc_retry_dense_stats.argtypes = [vp, _abi.c_int64_p, _abi.c_int64_p]
     L.relmc_retry_dense_stats.restype = C.c_int32
+    L.relmc_is_ratios.argtypes = [C.c_int32, _abi.c_uint32_p, u8p, dp, _abi.c_uint32_p, dp, dp, i32p]
+    L.relmc_is_ratios.restype = C.c_int32
+    L.relmc_is_sampling.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int64, dp, u8p, dp]
+    L.relmc_is_sampling.restype = C.c_int32
+    L.relmc_is_sampling_dev.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int64, dp, vp, vp]
+    L.relmc_is_sampling_dev.restype = C.c_int32
+    L.relmc_nsq_is_accumulate.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int64, C.POINTER(_abi.SolverOpts), dp, C.POINTER(_abi.IsAcc)]
+    L.relmc_nsq_is_accumulate.restype = C.c_int32
+    L.relmc_is_acc_zero.argtypes = [C.POINTER(_abi.IsAcc)]
+    L.relmc_is_acc_zero.restype = None
+    L.relmc_is_acc_merge.argtypes = [C.POINTER(_abi.IsAcc), C.POINTER(_abi.IsAcc)]
+    L.relmc_is_acc_merge.restype = None
+    L.relmc_nsq_is_indices.argtypes = [C.POINTER(_abi.IsAcc), C.c_int32, C.c_int32, C.c_double, C.POINTER(_abi.IsIndices)]
+    L.relmc_nsq_is_indices.restype = None
+    L.relmc_is_tune_opts_default.argtypes = [C.POINTER(_abi.IsTuneOpts)]
+    L.relmc_is_tune_opts_default.restype = None
+    L.relmc_nsq_is_tune.argtypes = [vp, C.POINTER(_abi.IsTuneOpts), dp, C.POINTER(_abi.IsTuneReport)]
+    L.relmc_nsq_is_tune.restype = C.c_int32
+    L.relmc_is_run_opts_default.argtypes = [C.POINTER(_abi.IsRunOpts)]
+    L.relmc_is_run_opts_default.restype = None
+    L.relmc_nsq_is_run.argtypes = [vp, C.POINTER(_abi.IsRunOpts), C.POINTER(_abi.IsRunResult)]
+    L.relmc_nsq_is_run.restype = C.c_int32
     if hasattr(L, "relmc_debug_mc_simulation_dense"):
         L.relmc_debug_mc_simulation_dense.argtypes = [vp, u8p, C.c_int64, C.c_void_p, dp, dp, i32p, i32p]
         L.relmc_debug_mc_simulation_dense.restype = C.c_int32

@@ -444,6 +444,76 @@ class Engine:
         self.L.relmc_nsq_indices(C.byref(acc), self.case.nb, self.case.ncomp, hours_per_year, C.byref(out))
         return out
 
+    # -- importance sampling (include/relmc.h; the loops and reports on top of these are in importance.py) ------------------
+    def _tilt(self, unavail_is):
+        if unavail_is is None:
+            return None, None
+        q = np.ascontiguousarray(unavail_is, dtype=np.float64).ravel()
+        if q.size != self.case.ncomp:
+            raise ValueError("unavail_is must have numGenerators+numLines entries")
+        return q, q.ctypes.data_as(_abi.c_double_p)
+
+    def is_sampling(self, seed: int, first_index: int, n: int, unavail_is=None):
+        """relmc_is_sampling: relmc_mc_sampling's draws against the tilted unavailabilities (None = the case's own).
+        Returns (eqstatus [n, Ng+Nl] uint8, W [n]): the states and their likelihood ratios."""
+        q, qp = self._tilt(unavail_is)
+        st = np.zeros((int(n), self.case.ncomp), dtype=np.uint8)
+        w = np.zeros(int(n))
+        self._check(self.L.relmc_is_sampling(self._h, int(seed), int(first_index), int(n), qp, st.ctypes.data_as(_abi.c_uint8_p),
+                                             w.ctypes.data_as(_abi.c_double_p)), "relmc_is_sampling")
+        return st, w
+
+    def nsq_is_accumulate(self, seed: int, first_index: int, n: int, unavail_is=None, mpopt=None) -> _abi.IsAcc:
+        """relmc_nsq_is_accumulate: tilted samples [first_index, first_index + n), evaluated and reduced with their weights."""
+        q, qp = self._tilt(unavail_is)
+        o = mpopt if mpopt is not None else mpoption()
+        acc = _abi.IsAcc()
+        self._check(self.L.relmc_nsq_is_accumulate(self._h, int(seed), int(first_index), int(n), C.byref(o), qp, C.byref(acc)),
+                    "relmc_nsq_is_accumulate")
+        return acc
+
+    def is_indices(self, acc: _abi.IsAcc, hours_per_year: float = 8760.0) -> _abi.IsIndices:
+        out = _abi.IsIndices()
+        self.L.relmc_nsq_is_indices(C.byref(acc), self.case.nb, self.case.ncomp, hours_per_year, C.byref(out))
+        return out
+
+    def is_tune(self, objective: int | str = "edns", *, seed: int = 1, n_pilot: int = 20000, max_iters: int = 5, final_iters: int = 2,
+                min_elite: int = 100, rho: float = 0.1, alpha: float = 1.0, q_max: float = 0.5, mpopt=None):
+        """relmc_nsq_is_tune: the cross-entropy tuner.  objective "plc" / 0 or "edns" / 1.  Returns (unavail_is [Ng+Nl], IsTuneReport)."""
+        obj = {"plc": 0, "edns": 1}.get(objective, objective)
+        if obj not in (0, 1):
+            raise ValueError('objective must be "plc" or "edns"')
+        o = _abi.IsTuneOpts()
+        self.L.relmc_is_tune_opts_default(C.byref(o))
+        o.seed, o.n_pilot, o.max_iters, o.final_iters, o.min_elite = int(seed), int(n_pilot), int(max_iters), int(final_iters), int(min_elite)
+        o.rho, o.objective, o.alpha, o.q_max = float(rho), int(obj), float(alpha), float(q_max)
+        if mpopt is not None:
+            o.solver = mpopt
+        q = np.zeros(self.case.ncomp)
+        rep = _abi.IsTuneReport()
+        self._check(self.L.relmc_nsq_is_tune(self._h, C.byref(o), q.ctypes.data_as(_abi.c_double_p), C.byref(rep)), "relmc_nsq_is_tune")
+        return q, rep
+
+    def nsq_is_run(self, unavail_is=None, beta_limit: float = 0.0017, max_samples: int = 100000, batch: int = 1000, *, seed: int = 1,
+                   mpopt=None, hours_per_year: float = 8760.0):
+        """relmc_nsq_is_run: batches under the tilt until beta <= beta_limit or max_samples.
+        Returns (IsRunResult, dict(beta=, edns=, plc=) histories, one entry per batch)."""
+        q, qp = self._tilt(unavail_is)
+        o = _abi.IsRunOpts()
+        self.L.relmc_is_run_opts_default(C.byref(o))
+        o.beta_limit, o.max_samples, o.batch, o.seed, o.hours_per_year = float(beta_limit), int(max_samples), int(batch), int(seed), float(hours_per_year)
+        if mpopt is not None:
+            o.solver = mpopt
+        o.unavail_is = qp
+        ncp = (int(max_samples) + int(batch) - 1) // int(batch)
+        hist = [np.zeros(ncp) for _ in range(3)]
+        o.history_cap = ncp
+        o.beta_history, o.edns_history, o.plc_history = (h.ctypes.data_as(_abi.c_double_p) for h in hist)
+        res = _abi.IsRunResult()
+        self._check(self.L.relmc_nsq_is_run(self._h, C.byref(o), C.byref(res)), "relmc_nsq_is_run")
+        k = int(res.checkpoints)
+        return res, dict(beta=hist[0][:k], edns=hist[1][:k], plc=hist[2][:k])
+
     # -- nsqMain.m:208-406 ---------------------------------------------------------------------
     def nsqMain(self, beta_limit: float = 0.0017, max_iterations: int = 100000,
                 samples_per_batch: int = 100, *, seed: int = 1, mpopt=None,

@@ -17,6 +17,8 @@
 //   relmc_plan.hip       the HL1 planning model's Monte Carlo (relmc_hl1_plan)
 //   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area); its rows are summed by relmc_seq.hip's record reduction
 //   relmc_screen.hip     the zero-curtailment pre-screen (relmc_solver_opts.screen): certificate tables, pre-pass kernels, worklists
+//   relmc_importance.hip importance sampling for the non-sequential track: tilted sampler with likelihood ratios, weighted reductions (kernels in
+//                        relmc_is_kernels.h), the cross-entropy tuner and the weighted run loop
 //   relmc_debug.hip      introspection and test hooks that are not part of include/relmc.h
 #pragma once
 #include <hip/hip_runtime.h>
@@ -203,6 +205,13 @@ struct relmc_ctx {
         DevBuf<uint32_t> keys; DevBuf<uint8_t> flags; DevBuf<uint32_t> idx, dcount; DevBuf<uint8_t> tmp;
     } screen;
     hipEvent_t screen_ev0 = nullptr, screen_ev1 = nullptr;      // timing of the pre-pass
+    // importance sampling (relmc_importance.hip): tilt tables of a call, grow-only per-sample buffers of one launch (at most 2^20 samples) and
+    // reduction partials
+    struct Is {
+        DevBuf<uint32_t> thr; DevBuf<double> r_dn, r_up;
+        DevBuf<uint8_t> states; DevBuf<double> w, dns, nodal, f_fail, f_dns, e; DevBuf<int32_t> status, iters;
+        DevBuf<double> part_d, part_col; DevBuf<long long> part_i;
+    } is;
     double last_kernel_ms = 0.0;
     long conflict_before = 0, conflict_after = 0;   // modelled extra LDS cycles per Newton step before / after the placement search
     long alt_conflict_before[kAlt] = {0, 0}, alt_conflict_after[kAlt] = {0, 0};      // the same of the further orders' images
@@ -310,6 +319,10 @@ void acc_add_unit(relmc_acc* acc, const FailRec& rec, double dns, int32_t meta, 
 int pipe_run(relmc_ctx* ctx, const uint8_t* states, const double* load_scale, int64_t n, const relmc_solver_opts& o, double fail_threshold,
              double* dns, double* nodal, int32_t* status, int32_t* iters);
 int nsq_accumulate_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t n, const relmc_solver_opts* opts, relmc_acc* acc_out, double* dns_dev);
+// relmc_mc_simulation_dev itself; n_infeasible_out (optional): how many of the n states needed an island rule (relmc_acc.n_infeasible), which no
+// per-state output carries -- from the launch's partial records and the re-evaluated units' meta words
+int mc_simulation_dev_impl(relmc_ctx* ctx, const uint8_t* states_dev, int64_t n, const relmc_solver_opts* opts, double* dns_dev, double* nodal_dev,
+                           int32_t* status_dev, int32_t* iters_dev, int64_t* n_infeasible_out);
 
 // ---- relmc_nsq_run.hip --------------------------------------------------------------------------------------------------------
 constexpr int64_t kStretch = 1 << 18, kStretchMaxBatch = 32768;      // samples a stretch holds at most; batches above the second are not stretched

@@ -190,15 +190,10 @@ int nsq_accumulate_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int
     return RELMC_OK;
 }
 
-}  // namespace relmc_host
-
-using namespace relmc_host;
-
-extern "C" {
-
-int32_t relmc_mc_simulation_dev(relmc_ctx* ctx, const uint8_t* states_dev, int64_t n, const relmc_solver_opts* opts,
-                                double* dns_dev, double* nodal_dev, int32_t* status_dev, int32_t* iters_dev)
+int mc_simulation_dev_impl(relmc_ctx* ctx, const uint8_t* states_dev, int64_t n, const relmc_solver_opts* opts, double* dns_dev, double* nodal_dev,
+                           int32_t* status_dev, int32_t* iters_dev, int64_t* n_infeasible_out)
 {
+    if (n_infeasible_out) *n_infeasible_out = 0;
     if (!ctx) return RELMC_ERR_INVALID;
     if (!ctx->has_case) return fail(ctx, RELMC_ERR_NO_CASE, "relmc_mc_simulation: no case loaded");
     if (n < 0 || (n > 0 && (!states_dev || !dns_dev))) return fail(ctx, RELMC_ERR_INVALID, "relmc_mc_simulation: bad arguments");
@@ -213,8 +208,14 @@ int32_t relmc_mc_simulation_dev(relmc_ctx* ctx, const uint8_t* states_dev, int64
     if (rc) return rc;
     rc = launch_eval(ctx, 1, a, &blocks);
     if (rc) return rc;
+    if (n_infeasible_out) {                               // the launch's partial records hold the count (of the units it did not list)
+        rc = launch_finalize(ctx, blocks);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(&ctx->hstage.get()->acc, ctx->dacc.get(), sizeof(relmc_acc), hipMemcpyDeviceToHost, ctx->stream));
+    }
     rc = finish_timing(ctx);
     if (rc) return rc;
+    if (n_infeasible_out) *n_infeasible_out = ctx->hstage.get()->acc.n_infeasible;
     RetryOut ro;
     double ms = ctx->last_kernel_ms;
     rc = fail_retry(ctx, o, a.fail_threshold, nullptr, ro, &ms);
@@ -223,12 +224,25 @@ int32_t relmc_mc_simulation_dev(relmc_ctx* ctx, const uint8_t* states_dev, int64
     for (size_t r = 0; r < ro.rec.size(); ++r) {          // the second attempt's results in the place of the first's
         const size_t u = (size_t)ro.rec[r].unit, nb = (size_t)ctx->nb;
         const int32_t st = ro.meta[r] & 3, it = (int32_t)((uint32_t)ro.meta[r] >> 8);
+        if (n_infeasible_out && (ro.meta[r] & 4)) ++*n_infeasible_out;
         HIP_TRY(ctx, hipMemcpy(dns_dev + u, &ro.dns[r], sizeof(double), hipMemcpyHostToDevice));
         if (nodal_dev) HIP_TRY(ctx, hipMemcpy(nodal_dev + u * nb, &ro.nodal[r * nb], sizeof(double) * nb, hipMemcpyHostToDevice));
         if (status_dev) HIP_TRY(ctx, hipMemcpy(status_dev + u, &st, sizeof(int32_t), hipMemcpyHostToDevice));
         if (iters_dev) HIP_TRY(ctx, hipMemcpy(iters_dev + u, &it, sizeof(int32_t), hipMemcpyHostToDevice));
     }
     return RELMC_OK;
+}
+
+}  // namespace relmc_host
+
+using namespace relmc_host;
+
+extern "C" {
+
+int32_t relmc_mc_simulation_dev(relmc_ctx* ctx, const uint8_t* states_dev, int64_t n, const relmc_solver_opts* opts,
+                                double* dns_dev, double* nodal_dev, int32_t* status_dev, int32_t* iters_dev)
+{
+    return mc_simulation_dev_impl(ctx, states_dev, n, opts, dns_dev, nodal_dev, status_dev, iters_dev, nullptr);
 }
 
 int32_t relmc_mc_simulation(relmc_ctx* ctx, const uint8_t* states_host, int64_t n, const relmc_solver_opts* opts,

@@ -233,6 +233,9 @@ def load():
     if hasattr(L, "relmc_debug_stretch_len"):
         L.relmc_debug_stretch_len.argtypes = [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int64, i32p]
         L.relmc_debug_stretch_len.restype = C.c_int64
+    if hasattr(L, "relmc_debug_task_image"):
+        L.relmc_debug_task_image.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_int32]
+        L.relmc_debug_task_image.restype = C.c_int32
     if hasattr(L, "relmc_debug_set"):
         L.relmc_debug_set.argtypes = [vp, C.c_char_p, C.c_int32]
         L.relmc_debug_set.restype = C.c_int32

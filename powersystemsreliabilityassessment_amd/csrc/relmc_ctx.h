@@ -261,7 +261,8 @@ struct SymOpts {
     int scen_pad4 = 0;                   // extra padding of a scenario row's LDS stride in units of 4 doubles (ablation builds)
     int model_leaf_free = -1;            // >= 0: scheduling MODEL with the pivots complete at assembly left out (relmc_debug_symbolic only: not a valid program)
 };
-struct SymGeom { uint32_t stash_off = 0, scen_doubles = 0, lds_bytes = 0; long conflict_before = 0, conflict_after = 0; };
+struct SymGeom { uint32_t stash_off = 0, scen_doubles = 0, lds_bytes = 0; long conflict_before = 0, conflict_after = 0;
+                 long shadow_masked = 0, shadow_tasks = 0, shadow_all = 0; };   // the same model on the finished device image: idle lanes masked / shadowing an active lane
 SymOpts sym_opts_default();              // the shipped schedule; a RELMC_DEV_SWITCHES build reads the ablation variables here
 template <class TL>
 int case_symbolic(const relmc_case_desc* d, DevCaseT<TL>& C, int order_variant, const SymOpts& so, SymGeom& geom, std::string& err);

@@ -53,6 +53,18 @@ constexpr uint32_t IK_NONE = 0u, IK_REAL = 1u, IK_VIRTUAL = 2u;
 //   [4*nb, 4*(nb+noff))       off-diagonal blocks K(a, i), a eliminated after i (lines and fill)
 //   [off_rhs, off_rhs+4*nb)   right-hand side as a pseudo-bus: block i = [[y_theta, y_lambda], [0, 0]]
 //   [off_p, off_p+4*nb)       P_i = inv(D_i) after the factorisation
+//
+// Idle lanes.  A lane without a task in a pass does not hold a null descriptor in the device image: it SHADOWS an active lane of the pass
+// (the same read operands, so its loads are broadcasts of addresses the pass reads anyway) and carries an idle marker the kernel tests with
+// one compare.  A kernel instantiation may then run the loads and the arithmetic of a pass on all lanes and predicate only the stores.
+//   PK_UPD (all forms), PK_BWD (both forms): field 0 == field 3.  No real task has it: an update's target T is an off-diagonal block, the
+//           diagonal block of a bus eliminated LATER than the pivot's, or an rhs pair (bit 15 set in the full form) -- never the pivot block D
+//           itself; a back substitution's y_i and y_a belong to different buses (i < a).  The idle lane reads the pivot block as its target.
+//   PK_INV: fields 2 and 3 non-zero (TASK_IDLE_INV); a real inversion task leaves them zero.
+// case_symbolic asserts both when it builds the image.  Descriptors behind the last pass (the one-pass-ahead prefetch reads one) stay 0xffff.
+constexpr uint16_t TASK_IDLE_INV = 0xffff;
+inline bool task_idle(const uint16_t* t, bool inv) { return inv ? (t[2] | t[3]) != 0 : t[0] == t[3]; }
+
 template <class TL>
 struct DevCaseT {
     static constexpr int NBT = TL::NBT, NLT = TL::NLT, NIT = TL::NIT, NCOMPMAX = TL::NCOMPMAX, MAXPASS = TL::MAXPASS, MAXOFF = TL::MAXOFF, ROWL = TL::RW;
@@ -94,7 +106,7 @@ struct DevCaseT {
     // static schedule of the sparse block LDL' (computed once per case on the host)
     uint16_t zero_off[MAXOFF];      // W offsets of fill-only blocks (cleared every iteration)
     uint8_t pass_ntask[MAXPASS];
-    uint16_t task[MAXPASS][ROWL][4];    // byte offsets into the scenario's workspace (< 32 KiB), 0xffff in field 0 = no task for this lane
+    uint16_t task[MAXPASS][ROWL][4];    // byte offsets into the scenario's workspace (< 32 KiB); a lane without a task shadows an active one and carries the idle marker (above)
 };
 
 // per-lane partial accumulators written once per workgroup-row, reduced by relmc_finalize_kernel

@@ -52,6 +52,16 @@ constexpr int kMinWaves = 2;       // waves per SIMD the register allocator must
 constexpr int kPfMask = 0xc0;        // 16-lane tile: sites 6, 7 (-1 % kernel time; site 3 on top: -0.3 % for +44 B/lane of scratch = +40 % HBM traffic, not taken; single sites -0.3 .. +1.3 %, profiles/r3_pf/)
 constexpr int kPfMaskWide = 0xc6;    // 64-lane tile: sites 1, 2, 6, 7 (-2.9 %)
 #define PFSITE(k) (((PF_MASK >> (k)) & 1) != 0)
+// Solver passes with the idle lanes SHADOWING an active lane (relmc_dev.h, "idle lanes"; bit m = MODE m): the operand loads, the pivot inverse and the
+// arithmetic of a pass run on all 64 lanes and only the stores are predicated on "not idle", so a pass has no branch around its body and the
+// descriptor's compare is off the chain to the first LDS read.  An idle lane computes on an active lane's operands (Inf / NaN included) and stores
+// nothing; an active lane executes what it executed before.  Instantiations outside the masks keep the masked form (the body under the idle
+// test) on the same device image.  Measurements and the choice per tile and mode: profiles/pass_shadow/README.md.
+constexpr int kShadowMask = 0xff;       // 16-lane tile
+constexpr int kShadowMaskWide = 0xff;   // 64-lane tile
+// the one compare a pass spends on its descriptor: field 0 == field 3 (updates, back substitution), fields 2, 3 non-zero (inversion)
+#define PASS_IDLE(d) (((d).x & 0xffffu) == ((d).y >> 16))
+#define PASS_IDLE_INV(d) ((d).y != 0u)
 // optional per-phase cycle accounting (profiling builds only: -DRELMC_PHASE_TIMING)
 #ifdef RELMC_PHASE_TIMING
 #define PT_DECL unsigned long long pt_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long pt0_ = __builtin_readcyclecounter();
@@ -98,6 +108,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
     constexpr int PAIR_MASK = TL::RW == 16 ? kRpairMask : kRpairMaskWide;      // which call sites share a reciprocal (frcp_pair)
 #define PAIRSITE(k) (((PAIR_MASK >> (k)) & 1) != 0)
     constexpr int PF_MASK = TL::RW == 16 ? kPfMask : kPfMaskWide;                 // which LDS round trips are taken off the critical path (PFSITE)
+    constexpr bool SHADOW = (((TL::RW == 16 ? kShadowMask : kShadowMaskWide) >> MODE) & 1) != 0;   // solver passes: all lanes compute, the stores are predicated (above)
     constexpr int RW = TL::RW, BS = TL::BS, LS = TL::LS, IS = TL::IS, NBT = TL::NBT, WPB = TL::WPB, SPW = TL::SPW, OW = TL::OW;
     using DevCase = DevCaseT<TL>;
     using Partial = PartialT<TL>;
@@ -1019,15 +1030,24 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                     RELOAD_FENCE();
                 } else {
                 // ---- Newton step: sparse 2x2-block LDL' on the LDS workspace, static schedule --------
-                // descriptors are prefetched one pass ahead (they do not depend on data); 0xffff = no task for this lane
+                // descriptors are prefetched one pass ahead (they do not depend on data); a lane without a task shadows an active lane's operands and
+                // carries the idle marker (relmc_dev.h): with SHADOW it runs the pass like every lane and skips the stores, else it skips the pass
                 // descriptor fields are byte offsets into the scenario's workspace (bit 15 of the first = rhs task in the full-form passes)
                 unsigned char* const W8 = reinterpret_cast<unsigned char*>(W);
 #define WP(off) reinterpret_cast<double*>(W8 + (off))
+                // Left alone the compiler sinks a pass's loads and arithmetic into the predicated region of its store, and the branch around the body is
+                // back (+1.5 % kernel time: vA in profiles/pass_shadow/ab_summary.txt); with the loads alone kept in place (RELOAD_FENCE) the arithmetic
+                // still sinks (+0.25 %: vB; the three forms' assembly side by side in pass_asm_variants.txt).  So the values to be stored are pinned in front
+                // of the predicate with the file's empty-statement idiom (it emits nothing, like RELOAD_FENCE and the flag-word pins of the evaluation):
+                // what is left under the predicate is the store, and the compiler drops the branch around it.  The memory clobber keeps the second row's
+                // loads behind the first row's store as before; without it the kernel takes the same time (vN).
+#define SHADOW_PIN(...) do { if constexpr (SHADOW) __asm__ volatile("" :: __VA_ARGS__ : "memory"); } while (0)
                 uint2 dsc = *reinterpret_cast<const uint2*>(&TASKSRC.task[0][rlane][0]);
                 PASS_LOOP
                 for (int p = 0; p < npuf; ++p) {             // T -= Wa * inv(D) * Wb'   (T: 2x2 block, or 1x2 rhs row)
                     const uint2 nxt = *reinterpret_cast<const uint2*>(&TASKSRC.task[p + 1][rlane][0]);
-                    if ((dsc.x & 0xffffu) != 0xffffu) {
+                    const bool idle = PASS_IDLE(dsc);
+                    if (SHADOW || !idle) {
                         const bool vec = (dsc.x & 0x8000u) != 0;            // rhs pseudo-bus: Wa = [y_i'; 0], T = y_a'
                         double* T = WP(dsc.x & 0x7fffu);
                         const double* Wa = WP(dsc.x >> 16);
@@ -1043,13 +1063,13 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                         const double P00 = pe * q, P01 = pb * q, P11 = -pm * q;
                         const double g00 = __builtin_fma(a0.x, P00, a0.y * P01), g01 = __builtin_fma(a0.x, P01, a0.y * P11);
                         t0.x -= __builtin_fma(g00, b0.x, g01 * b0.y); t0.y -= __builtin_fma(g00, b1.x, g01 * b1.y);
-                        st2(T, t0.x, t0.y);
-                        if (!vec) {
+                        SHADOW_PIN("v"(t0.x), "v"(t0.y)); if (!idle) st2(T, t0.x, t0.y);
+                        if (SHADOW || !vec) {                               // SHADOW: an rhs task reads the 16 bytes behind its operands (workspace words) and stores nothing
                             const d2 a1 = ld2(Wa + 2);
                             d2 t1 = ld2(T + 2);
                             const double g10 = __builtin_fma(a1.x, P00, a1.y * P01), g11 = __builtin_fma(a1.x, P01, a1.y * P11);
                             t1.x -= __builtin_fma(g10, b0.x, g11 * b0.y); t1.y -= __builtin_fma(g10, b1.x, g11 * b1.y);
-                            st2(T + 2, t1.x, t1.y);
+                            SHADOW_PIN("v"(t1.x), "v"(t1.y)); if (!idle && !vec) st2(T + 2, t1.x, t1.y);
                         }
                     }
                     dsc = nxt;
@@ -1057,7 +1077,8 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 PASS_LOOP
                 for (int p = npuf; p < npuh; ++p) {          // the same update, one row of T per lane (passes filled to at most a half, relmc_dev.h)
                     const uint2 nxt = *reinterpret_cast<const uint2*>(&TASKSRC.task[p + 1][rlane][0]);
-                    if ((dsc.x & 0xffffu) != 0xffffu) {
+                    const bool idle = PASS_IDLE(dsc);
+                    if (SHADOW || !idle) {
                         double* T = WP(dsc.x & 0xffffu);
                         const double* Wa = WP(dsc.x >> 16);
                         const double* Wb = WP(dsc.y & 0xffffu);
@@ -1070,14 +1091,15 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                         const double P00 = pe * q, P01 = pb * q, P11 = -pm * q;
                         const double g00 = __builtin_fma(a0.x, P00, a0.y * P01), g01 = __builtin_fma(a0.x, P01, a0.y * P11);
                         t0.x -= __builtin_fma(g00, b0.x, g01 * b0.y); t0.y -= __builtin_fma(g00, b1.x, g01 * b1.y);
-                        st2(T, t0.x, t0.y);
+                        SHADOW_PIN("v"(t0.x), "v"(t0.y)); if (!idle) st2(T, t0.x, t0.y);
                     }
                     dsc = nxt;
                 }
                 PASS_LOOP
                 for (int p = npuh; p < npu; ++p) {           // the same update, one element of T per lane (sparsely filled passes, relmc_dev.h)
                     const uint2 nxt = *reinterpret_cast<const uint2*>(&TASKSRC.task[p + 1][rlane][0]);
-                    if ((dsc.x & 0xffffu) != 0xffffu) {
+                    const bool idle = PASS_IDLE(dsc);
+                    if (SHADOW || !idle) {
                         double* T = WP(dsc.x & 0xffffu);
                         const double* Wa = WP(dsc.x >> 16);
                         const double* Wb = WP(dsc.y & 0xffffu);
@@ -1090,7 +1112,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                         const double P00 = pe * q, P01 = pb * q, P11 = -pm * q;
                         const double g0 = __builtin_fma(a0.x, P00, a0.y * P01), g1 = __builtin_fma(a0.x, P01, a0.y * P11);
                         t -= __builtin_fma(g0, b0.x, g1 * b0.y);
-                        *T = t;
+                        SHADOW_PIN("v"(t)); if (!idle) *T = t;
                     }
                     dsc = nxt;
                 }
@@ -1098,15 +1120,16 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 PASS_LOOP
                 for (int p = npu; p < npu + npi; ++p) {      // D <- P = inv(D) in place; y <- P*y
                     const uint2 nxt = *reinterpret_cast<const uint2*>(&TASKSRC.task[p + 1][rlane][0]);
-                    if ((dsc.x & 0xffffu) != 0xffffu) {
+                    const bool idle = PASS_IDLE_INV(dsc);
+                    if (SHADOW || !idle) {
                         double* D = WP(dsc.x & 0xffffu);
                         double* Y = WP(dsc.x >> 16);
                         const d2 dA = ld2(D), y = ld2(Y); const double dBy = D[3];
                         const double pm = dA.x, pb = dA.y, pe = -dBy;
                         const double q = frcp(__builtin_fma(pm, pe, pb * pb));
                         const double P00 = pe * q, P01 = pb * q, P11 = -pm * q;
-                        st2(D, P00, P01); st2(D + 2, P01, P11);
-                        st2(Y, __builtin_fma(P00, y.x, P01 * y.y), __builtin_fma(P01, y.x, P11 * y.y));
+                        const double y0 = __builtin_fma(P00, y.x, P01 * y.y), y1 = __builtin_fma(P01, y.x, P11 * y.y);
+                        SHADOW_PIN("v"(P00), "v"(P01), "v"(P11), "v"(y0), "v"(y1)); if (!idle) { st2(D, P00, P01); st2(D + 2, P01, P11); st2(Y, y0, y1); }
                     }
                     dsc = nxt;
                 }
@@ -1115,7 +1138,8 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 PASS_LOOP
                     for (int p = npu + npi; p < npass; ++p) {
                         const uint2 nxt = *reinterpret_cast<const uint2*>(&TASKSRC.task[p + 1][rlane][0]);
-                        if ((dsc.x & 0xffffu) != 0xffffu) {
+                        const bool idle = PASS_IDLE(dsc);
+                        if (SHADOW || !idle) {
                             double* Yi = WP(dsc.x & 0xffffu);
                             const double* Wk = WP(dsc.x >> 16);
                             const double* Pr = WP(dsc.y & 0xffffu);
@@ -1124,7 +1148,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                             double y = *Yi;
                             const double u0 = __builtin_fma(w0.x, x.x, w1.x * x.y), u1 = __builtin_fma(w0.y, x.x, w1.y * x.y);
                             y -= __builtin_fma(pr.x, u0, pr.y * u1);
-                            *Yi = y;
+                            SHADOW_PIN("v"(y)); if (!idle) *Yi = y;
                         }
                         dsc = nxt;
                     }
@@ -1132,7 +1156,8 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 PASS_LOOP
                 for (int p = npu + npi; p < npass; ++p) {    // y_i -= P_i * W' * x_a
                     const uint2 nxt = *reinterpret_cast<const uint2*>(&TASKSRC.task[p + 1][rlane][0]);
-                    if ((dsc.x & 0xffffu) != 0xffffu) {
+                    const bool idle = PASS_IDLE(dsc);
+                    if (SHADOW || !idle) {
                         double* Yi = WP(dsc.x & 0xffffu);
                         const double* Wk = WP(dsc.x >> 16);
                         const double* P = WP(dsc.y & 0xffffu);
@@ -1141,7 +1166,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                         d2 y = ld2(Yi);
                         const double u0 = __builtin_fma(w0.x, x.x, w1.x * x.y), u1 = __builtin_fma(w0.y, x.x, w1.y * x.y);
                         y.x -= __builtin_fma(p0.x, u0, p0.y * u1); y.y -= __builtin_fma(p1.x, u0, p1.y * u1);
-                        st2(Yi, y.x, y.y);
+                        SHADOW_PIN("v"(y.x), "v"(y.y)); if (!idle) st2(Yi, y.x, y.y);
                     }
                     dsc = nxt;
                 }

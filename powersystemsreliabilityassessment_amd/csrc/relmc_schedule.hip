@@ -309,15 +309,16 @@ int case_symbolic(const relmc_case_desc* d, DevCaseT<TL>& C, int order_variant, 
         // a group is conflict-free when its 16 lanes hit 16 different 16-byte bank slots.  Two degrees of freedom cost
         // nothing at run time: where the off-diagonal blocks live in W and which lane of the row carries which task of a
         // pass.  A seeded local search minimises the modelled extra LDS cycles of all operand reads of one Newton step.
+        static const int kGroupOfLane[64] = {0,0,0,0,1,1,1,1,1,1,1,1,0,0,0,0, 1,1,1,1,0,0,0,0,0,0,0,0,1,1,1,1,
+                                             2,2,2,2,3,3,3,3,3,3,3,3,2,2,2,2, 3,3,3,3,2,2,2,2,2,2,2,2,3,3,3,3};
+        uint32_t stride = 0;                                    // doubles between two scenario rows' workspaces (the shadow rewrite below models with it too)
         {
             const uint32_t eval_d = 4u * (nl + 1) + 4u * (ninj + 1);
-            uint32_t stride = C.nws > eval_d ? C.nws : eval_d;
+            stride = C.nws > eval_d ? C.nws : eval_d;
             stride = (stride + 1u) & ~1u;
             stride += 2u * IS * ROWL + 2u + NBT + OW / 2u;
             while ((stride & 3u) != 2u) stride += 1;            // = the per-scenario LDS stride computed below
             stride += 4u * (uint32_t)so.scen_pad4;
-            static const int kGroupOfLane[64] = {0,0,0,0,1,1,1,1,1,1,1,1,0,0,0,0, 1,1,1,1,0,0,0,0,0,0,0,0,1,1,1,1,
-                                                 2,2,2,2,3,3,3,3,3,3,3,3,2,2,2,2, 3,3,3,3,2,2,2,2,2,2,2,2,3,3,3,3};
             auto remap = [&](int o) {                             // offset under the identity placement -> current placement
                 const int f = o & 0x8000; o &= 0x7fff;
                 if (o >= 4 * nb && o < (int)C.off_rhs) o = 4 * pos[o >> 2] + (o & 3);
@@ -496,6 +497,97 @@ int case_symbolic(const relmc_case_desc* d, DevCaseT<TL>& C, int order_variant, 
                         C.task[q][r][k] = (uint16_t)(((v & (f ? 0x7fffu : 0xffffu)) << 3) | f);
                     }
                 }
+        }
+        // Idle lanes shadow an active lane (relmc_dev.h, "idle lanes"): the last rewrite of the finished pass program.  Every lane without a
+        // task gets the read operands of an active lane of its pass plus the form's idle marker, so the kernel may run a pass's loads and
+        // arithmetic on all 64 lanes and predicate only the stores.  Equal addresses are broadcasts to the LDS, so a shadow inside the same
+        // b128 read group adds no bank conflict to the operands it copies; the one field the marker occupies (T / Y_i := the pivot field) is a
+        // new address in that operand's read.  The shadowed lane is therefore chosen per pass and read group by the placement model itself:
+        // the active lane OF THE SAME READ GROUP that leaves the pass's modelled conflicts lowest (ties: the lowest lane; any lane of the pass where the
+        // group holds no task: its lanes then read one address all together).  A pass always holds a task: the scheduler refuses an empty one above.
+        {
+            const int np = (int)pkind.size();
+            int nup_all = 0;
+            for (int q = 0; q < np; ++q) if (pkind[q] == 0) nup_all++;
+            const int nfull_upd = nup_all - (int)C.npass_updq - (int)C.npass_updh, nhalf_end = nup_all - (int)C.npass_updq;
+            int first_bwd = 0;
+            while (first_bwd < np && pkind[first_bwd] != 2) first_bwd++;
+            // operand reads per pass form as (field, byte offset); the full form's last two are the second row (not read by a masked rhs task)
+            static const int kRdFull[8][2] = {{3, 0}, {3, 16}, {1, 0}, {2, 0}, {2, 16}, {0, 0}, {1, 16}, {0, 16}};
+            static const int kRdHalf[6][2] = {{3, 0}, {3, 16}, {1, 0}, {2, 0}, {2, 16}, {0, 0}};
+            static const int kRdQuarter[5][2] = {{3, 0}, {3, 16}, {1, 0}, {2, 0}, {0, 0}};
+            static const int kRdInv[3][2] = {{0, 0}, {0, 16}, {1, 0}};
+            static const int kRdBwd[6][2] = {{1, 0}, {1, 16}, {2, 0}, {2, 16}, {3, 0}, {0, 0}};
+            static const int kRdBwdHalf[5][2] = {{1, 0}, {1, 16}, {2, 0}, {3, 0}, {0, 0}};
+            auto form_of = [&](int p, const int (*&rd)[2]) {
+                if (pkind[p] == 0) { if (p < nfull_upd) { rd = kRdFull; return 8; } if (p < nhalf_end) { rd = kRdHalf; return 6; } rd = kRdQuarter; return 5; }
+                if (pkind[p] == 1) { rd = kRdInv; return 3; }
+                if ((C.bwd_half >> (p - first_bwd)) & 1) { rd = kRdBwdHalf; return 5; }
+                rd = kRdBwd; return 6;
+            };
+            // modelled extra LDS cycles of the pass's operand reads on the byte-offset image: lanes with field 0 = 0xffff take no part;
+            // mode 0 = the masked kernel (idle lanes and an rhs task's second row off), 1 = the tasks alone with both rows read by every one of
+            // them (what the shadowing kernel's active lanes do), 2 = the shadowing kernel (every lane reads everything)
+            auto image_cost = [&](int p, int mode) {
+                const bool all = mode == 2;
+                const int (*rd)[2] = nullptr; const int nins = form_of(p, rd);
+                const bool inv = pkind[p] == 1, full = pkind[p] == 0 && p < nfull_upd;
+                long cost = 0;
+                for (int ins = 0; ins < nins; ++ins) {
+                    int cnt[4][16]; int addr[4][16][16];
+                    for (int g = 0; g < 4; ++g) for (int q = 0; q < 16; ++q) cnt[g][q] = 0;
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const uint16_t* t = C.task[p][lane % ROWL];
+                        if (t[0] == 0xffff && t[3] == 0xffff) continue;                 // not assigned yet
+                        if (!all && (task_idle(t, inv) || (mode == 0 && full && ins >= 6 && (t[0] & 0x8000u)))) continue;
+                        const int f = rd[ins][0], o = (int)((f == 0 && full) ? (t[0] & 0x7fffu) : t[f]) + rd[ins][1];
+                        const int ad = (lane / ROWL) * (int)stride * 8 + o, g = kGroupOfLane[lane], q = (ad >> 4) & 15;
+                        bool seen = false;
+                        for (int k = 0; k < cnt[g][q]; ++k) if (addr[g][q][k] == ad) { seen = true; break; }
+                        if (!seen) addr[g][q][cnt[g][q]++] = ad;
+                    }
+                    for (int g = 0; g < 4; ++g) { int mx = 0; for (int q = 0; q < 16; ++q) if (cnt[g][q] > mx) mx = cnt[g][q]; if (mx > 1) cost += mx - 1; }
+                }
+                return cost;
+            };
+            long masked = 0, tasks_all_rows = 0, shadowed = 0;
+            const bool model = so.place_moves > 0;               // the order tuner evaluates thousands of orders without placing them: first candidate, no model
+            for (int p = 0; p < np; ++p) {
+                const bool inv = pkind[p] == 1;
+                std::vector<int> active;
+                for (int r = 0; r < ROWL; ++r) {
+                    const uint16_t* t = C.task[p][r];
+                    if (t[0] == 0xffff) continue;
+                    // no real task carries the idle marker: an update's target is an off-diagonal block, a LATER bus' diagonal block or an rhs pair,
+                    // never its own pivot; a back substitution's y_i and y_a belong to different buses; an inversion's last two fields are zero
+                    if (task_idle(t, inv)) return failx(RELMC_ERR_INVALID, "relmc_case_load: a solver task carries the idle marker");
+                    active.push_back(r);
+                }
+                if (active.empty()) return failx(RELMC_ERR_INVALID, "relmc_case_load: a solver pass without a task");
+                if (model) { masked += image_cost(p, 0); tasks_all_rows += image_cost(p, 1); }
+                const int ngroup = ROWL == 64 ? 4 : 2;                                       // lanes that share their b128 read groups in every scenario row
+                for (int g = 0; g < ngroup; ++g) {
+                    std::vector<int> idle;
+                    for (int r = 0; r < ROWL; ++r) if (C.task[p][r][0] == 0xffff && kGroupOfLane[r] == g) idle.push_back(r);
+                    if (idle.empty()) continue;
+                    std::vector<int> cand;
+                    for (int r : active) if (kGroupOfLane[r] == g) cand.push_back(r);
+                    if (cand.empty()) cand = active;                  // no task among these lanes: any lane of the pass (they all read one address then)
+                    auto assign = [&](int src) {
+                        for (int r : idle) {
+                            uint16_t* q = C.task[p][r]; const uint16_t* s = C.task[p][src];
+                            if (inv) { q[0] = s[0]; q[1] = s[1]; q[2] = TASK_IDLE_INV; q[3] = TASK_IDLE_INV; }
+                            else { q[0] = s[3]; q[1] = s[1]; q[2] = s[2]; q[3] = s[3]; }
+                        }
+                    };
+                    int best = -1; long bestc = 0;
+                    for (int src : cand) { if (!model) { best = src; break; } assign(src); const long c = image_cost(p, 2); if (best < 0 || c < bestc) { best = src; bestc = c; } }
+                    assign(best);
+                }
+                if (model) shadowed += image_cost(p, 2);
+            }
+            geom.shadow_masked = masked; geom.shadow_tasks = tasks_all_rows; geom.shadow_all = shadowed;
+            if (verbose()) fprintf(stderr, "relmc: order %d: modelled LDS conflict cycles of the device image, idle lanes masked %ld, the tasks with every second row read %ld, idle lanes shadowing %ld\n", order_variant, masked, tasks_all_rows, shadowed);
         }
         C.npass = (uint16_t)pkind.size();
         int nu = 0, ni = 0;
@@ -741,7 +833,9 @@ int32_t relmc_debug_symbolic(const relmc_case_desc* d, int32_t order_variant, co
             // back to offsets in doubles (what tests/schedule_interp.py executes); bit 15 of field 0 of a full-form update pass is the rhs flag
             const uint16_t v = C.task[p][r][k];
             const bool full_upd = p < C.npass_upd - C.npass_updh - C.npass_updq;
-            tasks[((size_t)p * rw + r) * 4 + k] = C.task[p][r][0] == 0xffff ? v : (uint16_t)((k == 0 && full_upd) ? (((v & 0x7fffu) >> 3) | (v & 0x8000u)) : (v >> 3));
+            const bool inv = p >= C.npass_upd && p < C.npass_upd + C.npass_inv;
+            // idle lanes shadow an active lane in the device image (relmc_debug_task_image); here they stay "no task"
+            tasks[((size_t)p * rw + r) * 4 + k] = task_idle(C.task[p][r], inv) ? (uint16_t)0xffff : (uint16_t)((k == 0 && full_upd) ? (((v & 0x7fffu) >> 3) | (v & 0x8000u)) : (v >> 3));
         } }
         for (int i = 0; i < C.nb; ++i) b_int[i] = C.b_int[i];
         for (int l = 0; l < C.nl; ++l) { l_info[l] = C.l_info[l]; l_blk[l] = ((C.l_info[l] >> 24) & LF_OWNER) ? C.l_blk[l] : (uint16_t)0xffff; }
@@ -756,6 +850,42 @@ int32_t relmc_debug_symbolic(const relmc_case_desc* d, int32_t order_variant, co
         auto C = std::make_unique<DevCaseT<Tile96>>();
         rc = case_symbolic<Tile96>(d, *C, order_variant, so, g, errs);
         if (rc == RELMC_OK) rc = dump(*C, 1, Tile96::RW, Tile96::MAXPASS);
+    }
+    if (err && err_cap > 0) { std::strncpy(err, errs.c_str(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+    return rc;
+}
+
+// Host-only introspection: the pass descriptors exactly as the device gets them (byte offsets, idle lanes shadowing an active lane and
+// carrying the idle marker; relmc_dev.h).  Same case / order arguments as relmc_debug_symbolic.
+//   hdr[16]: tile, RW, nb, nws, off_rhs, npass, npass_upd, npass_inv, npass_updh, npass_updq, bwd_half (2), scen_doubles, modelled LDS
+//            conflict cycles of the image with the idle lanes masked / shadowing / masked but every task reading both rows (full form)
+//   tasks[npass][RW][4]
+int32_t relmc_debug_task_image(const relmc_case_desc* d, int32_t order_variant, const int32_t* order_hint, int32_t n_hint, int32_t* hdr, uint16_t* tasks, int64_t tasks_cap,
+                               char* err, int32_t err_cap)
+{
+    if (!d || !hdr || !tasks) return RELMC_ERR_INVALID;
+    SymOpts so = sym_opts_default();
+    if (order_hint && n_hint > 0) { so.order_hint = order_hint; so.n_hint = n_hint; }
+    std::string errs;
+    SymGeom g;
+    int rc;
+    auto dump = [&](const auto& C, int tile, int rw) {
+        for (int k = 0; k < 16; ++k) hdr[k] = 0;
+        hdr[0] = tile; hdr[1] = rw; hdr[2] = C.nb; hdr[3] = (int)C.nws; hdr[4] = C.off_rhs; hdr[5] = C.npass; hdr[6] = C.npass_upd; hdr[7] = C.npass_inv;
+        hdr[8] = C.npass_updh; hdr[9] = C.npass_updq; hdr[10] = (int32_t)(uint32_t)(C.bwd_half & 0xffffffffull); hdr[11] = (int32_t)(uint32_t)(C.bwd_half >> 32);
+        hdr[12] = (int)g.scen_doubles; hdr[13] = (int)g.shadow_masked; hdr[14] = (int)g.shadow_all; hdr[15] = (int)g.shadow_tasks;
+        if ((int64_t)C.npass * rw * 4 > tasks_cap) return (int)RELMC_ERR_INVALID;
+        for (int p = 0; p < C.npass; ++p) for (int r = 0; r < rw; ++r) for (int k = 0; k < 4; ++k) tasks[((size_t)p * rw + r) * 4 + k] = C.task[p][r][k];
+        return (int)RELMC_OK;
+    };
+    if (fits_tile24(d)) {
+        auto C = std::make_unique<DevCaseT<Tile24>>();
+        rc = case_symbolic<Tile24>(d, *C, order_variant, so, g, errs);
+        if (rc == RELMC_OK) rc = dump(*C, 0, Tile24::RW);
+    } else {
+        auto C = std::make_unique<DevCaseT<Tile96>>();
+        rc = case_symbolic<Tile96>(d, *C, order_variant, so, g, errs);
+        if (rc == RELMC_OK) rc = dump(*C, 1, Tile96::RW);
     }
     if (err && err_cap > 0) { std::strncpy(err, errs.c_str(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
     return rc;

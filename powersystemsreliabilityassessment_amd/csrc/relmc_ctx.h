@@ -108,7 +108,7 @@ struct relmc_ctx {
     int last_tail_groups = 0; int64_t tail_launches = 0;   // T of the last fused launch on the 16-lane tile, launches with T > 0 so far (relmc_debug_tail_groups)
     DevBuf<relmc::DevAcc> dacc;
     struct HostStage { relmc_acc acc; uint32_t fail_cnt, pad; };
-    PinBuf<HostStage> hstage;            // accumulators + listed-unit count of a fused launch come back in one synchronisation
+    PinBuf<HostStage> hstage;            // accumulators + listed-unit count of a first-attempt launch come back in one synchronisation (eval_collect)
     int num_cu = 0;
     int blocks_per_cu = 0;
     uint32_t scen_doubles = 0, lds_bytes = 0, stash_off = 0;
@@ -274,6 +274,13 @@ inline bool fits_tile24(const relmc_case_desc* d)
 }
 
 // ---- relmc_core.hip -----------------------------------------------------------------------------------------------------------
+inline relmc_solver_opts solver_opts_or_default(const relmc_solver_opts* opts)
+{
+    relmc_solver_opts o;
+    if (opts) o = *opts; else relmc_solver_opts_default(&o);
+    return o;
+}
+inline bool screen_active(const relmc_ctx* ctx, const relmc_solver_opts& o) { return o.screen != 0 && ctx->screen.tab.valid != 0; }   // relmc_solver_opts.screen, and the case has its certificate tables
 EvalArgs make_args(const relmc_solver_opts& o);
 // launches relmc_eval_kernel<mode, active tile> on the context's stream between two events (default: ev0 / ev1); alt = 0 the primary image of
 // the case, 1.. = the further orders'; *rows_out = scenario rows holding partial accumulators
@@ -307,14 +314,40 @@ constexpr uint32_t kFailCapMin = 4096, kFailCapSteady = 1u << 20, kFailCapMax = 
 uint32_t fail_cap_for(int64_t call_units);
 int fail_list_ensure(relmc_ctx* ctx, uint32_t cap);
 int fail_count_ensure(relmc_ctx* ctx);           // the two count words exist (zeroed when they are created)
-struct RetryOut { std::vector<FailRec> rec; std::vector<double> dns, nodal; std::vector<int32_t> meta; };   // meta = status | relaxed << 2 | iterations << 8
+// one re-evaluated unit, its meta word (status | relaxed << 2 | iterations << 8) decoded once
+struct RetryUnit {
+    unsigned long long unit; long long weight; const uint32_t* mask;
+    double dns; int32_t meta; int32_t status, iters; bool island_rule;      // island_rule: an island needed Pmin relaxation / decommit (relmc_acc.n_infeasible)
+    const double* nodal;
+};
+struct RetryOut {
+    std::vector<FailRec> rec; std::vector<double> dns, nodal; std::vector<int32_t> meta; size_t nb = 0;
+    size_t size() const { return rec.size(); }
+    RetryUnit operator[](size_t r) const
+    {
+        const int32_t m = meta[r];
+        return {rec[r].unit, (long long)rec[r].weight, rec[r].mask, dns[r], m, m & 3, (int32_t)((uint32_t)m >> 8), (m & 4) != 0, &nodal[r * nb]};
+    }
+};
 int alt_ensure(relmc_ctx* ctx, int v);
 int fail_arm(relmc_ctx* ctx, EvalArgs& a, int64_t unit_base, bool reset, int64_t call_units);
-int fail_listed(relmc_ctx* ctx, uint32_t* cnt);
+// One first-attempt launch of relmc_eval_kernel<mode> and its collection, the protocol of every HL2 entry point (`who`, for the message): the list
+// armed for the call_units units of the call (unit_base: the launch's first), the launch, then -- acc != nullptr -- the reduction of its partial
+// records, and the accumulators and the listed count back through the context's pinned words in ONE synchronisation.
+struct Collected {
+    uint32_t listed = 0; bool armed = false;       // units the launch listed (may exceed the list's capacity); armed: there is a list (not sw.no_retry)
+    double ms = 0.0;                               // the launch's kernel time (ctx->last_kernel_ms as well)
+    const uint32_t* known() const { return armed ? &listed : nullptr; }      // fail_retry's known_count
+};
+int eval_collect(relmc_ctx* ctx, const char* who, int mode, EvalArgs& a, int64_t unit_base, int64_t call_units, relmc_acc* acc, Collected& c);
 using ScaleFn = std::function<double(unsigned long long)>;          // unit -> load scale factor of a re-evaluated unit
-// known_count (optional): the number of listed units if the caller has already copied it back with its results
+// known_count (optional): the number of listed units if the caller has already copied it back with its results; ms (optional)
 int fail_retry(relmc_ctx* ctx, const relmc_solver_opts& o, double fail_threshold, const ScaleFn* scale, RetryOut& out, double* ms, const uint32_t* known_count = nullptr);
-void acc_add_unit(relmc_acc* acc, const FailRec& rec, double dns, int32_t meta, const double* nodal, int nb, int ncomp, double fail_threshold);
+void acc_add_unit(relmc_acc* acc, const RetryUnit& u, int nb, int ncomp, double fail_threshold);
+inline void acc_add_retry(relmc_acc* acc, const RetryOut& ro, int ncomp, double fail_threshold)      // every re-evaluated unit, in list order
+{
+    for (size_t r = 0; r < ro.size(); ++r) acc_add_unit(acc, ro[r], (int)ro.nb, ncomp, fail_threshold);
+}
 
 // ---- relmc_simulate.hip -------------------------------------------------------------------------------------------------------
 int pipe_run(relmc_ctx* ctx, const uint8_t* states, const double* load_scale, int64_t n, const relmc_solver_opts& o, double fail_threshold,

@@ -190,8 +190,7 @@ int db_batch_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t n
 
 int db_batch_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t n, const relmc_solver_opts* opts, relmc_acc* acc_out, relmc_db_stats* stats_out)
 {
-    relmc_solver_opts o;
-    if (opts) o = *opts; else relmc_solver_opts_default(&o);
+    const relmc_solver_opts o = solver_opts_or_default(opts);
     if (ctx->db.has_opts && ctx->db.n > 0 && !same_opts(o, ctx->db.opts))
         return fail(ctx, RELMC_ERR_INVALID, "relmc_nsq_db_batch: the database holds results of other solver options (relmc_db_reset first)");
     ctx->db.opts = o; ctx->db.has_opts = true;
@@ -258,7 +257,6 @@ int db_batch_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t n
         uint32_t n_new = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&n_new, dnew, sizeof(n_new), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        double eval_ms = 0.0;
         if (n_new > 0) {
             // new rows in the order of first appearance (unique(...,'stable'), :220): sort the flagged states by first sample index
             size_t tb = ctx->memo.tmp.size(), need = 0;
@@ -275,35 +273,29 @@ int db_batch_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t n
             a.dns = ctx->db.dns.get(); a.status = ctx->db.meta.get(); a.nodal = ctx->db.nodal.get();
             // screen = 1 (relmc_screen.hip): the new rows the zero-curtailment certificate covers get their (0, zeros) right away, the interior
             // point runs over the list of the others
-            if (o.screen != 0 && ctx->screen.tab.valid != 0) {
+            if (screen_active(ctx, o)) {
                 uint32_t n_eval = 0;
                 rc = screen_prepass_rows(ctx, ctx->db.n, (int64_t)n_new, &n_eval);
                 if (rc) return rc;
                 a.n = (int64_t)n_eval; a.memo_perm = ctx->screen.idx.get();
             }
-            int rows = 0;
             RetryOut ro;
             if (a.n > 0) {
-                rc = fail_arm(ctx, a, 0, true, a.n);
-                if (rc) return rc;
-                rc = launch_eval(ctx, 4, a, &rows);
-                if (rc) return rc;
-                rc = finish_timing(ctx);
-                if (rc) return rc;
-                eval_ms = ctx->last_kernel_ms;
-                rc = fail_retry(ctx, o, a.fail_threshold, nullptr, ro, &eval_ms);
+                Collected c;
+                rc = eval_collect(ctx, "relmc_nsq_db_batch", 4, a, 0, a.n, nullptr, c);
+                if (rc == RELMC_OK) rc = fail_retry(ctx, o, a.fail_threshold, nullptr, ro, nullptr, c.known());
                 if (rc) return rc;
             }
-            for (size_t r = 0; r < ro.rec.size(); ++r) {          // into the rows the first attempt filled
-                const size_t row = (size_t)ctx->db.n + (size_t)ro.rec[r].unit, nbz = (size_t)ctx->nb;
-                HIP_TRY(ctx, hipMemcpy(ctx->db.dns.get() + row, &ro.dns[r], sizeof(double), hipMemcpyHostToDevice));
-                HIP_TRY(ctx, hipMemcpy(ctx->db.meta.get() + row, &ro.meta[r], sizeof(int32_t), hipMemcpyHostToDevice));
-                HIP_TRY(ctx, hipMemcpy(ctx->db.nodal.get() + row * nbz, &ro.nodal[r * nbz], sizeof(double) * nbz, hipMemcpyHostToDevice));
+            for (size_t r = 0; r < ro.size(); ++r) {              // into the rows the first attempt filled
+                const RetryUnit u = ro[r];
+                const size_t row = (size_t)ctx->db.n + (size_t)u.unit, nbz = (size_t)ctx->nb;
+                HIP_TRY(ctx, hipMemcpy(ctx->db.dns.get() + row, &u.dns, sizeof(double), hipMemcpyHostToDevice));
+                HIP_TRY(ctx, hipMemcpy(ctx->db.meta.get() + row, &u.meta, sizeof(int32_t), hipMemcpyHostToDevice));
+                HIP_TRY(ctx, hipMemcpy(ctx->db.nodal.get() + row * nbz, u.nodal, sizeof(double) * nbz, hipMemcpyHostToDevice));
             }
             ctx->db.n += (int64_t)n_new;
         }
         ctx->db.samples += m;
-        (void)eval_ms;
         ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         new_total += n_new; distinct_total += nu;
         done += m;
@@ -337,12 +329,11 @@ int32_t relmc_nsq_accumulate_distinct(relmc_ctx* ctx, uint64_t seed, uint64_t fi
     relmc_acc_zero(acc_out);
     if (n_distinct_out) *n_distinct_out = 0;
     if (n == 0) return RELMC_OK;
-    relmc_solver_opts o;
-    if (opts) o = *opts; else relmc_solver_opts_default(&o);
+    const relmc_solver_opts o = solver_opts_or_default(opts);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // screen = 1 (relmc_screen.hip): the zero-curtailment certificate runs first, one thread per sample; only the masks it does not cover are sorted and
     // run-length encoded, and only their distinct states are solved.  Certified samples add 1 to n and to n_screened and nothing else.
-    const bool screen = o.screen != 0 && ctx->screen.tab.valid != 0;
+    const bool screen = screen_active(ctx, o);
     const int64_t kMaxPerLaunch = screen ? kScreenChunk : (int64_t)1 << 27;      // 32-bit weighted counters per scenario row; the pre-pass' buffers
     double ms_total = 0.0;
     int64_t distinct_total = 0;
@@ -367,22 +358,14 @@ int32_t relmc_nsq_accumulate_distinct(relmc_ctx* ctx, uint64_t seed, uint64_t fi
         if (nu > 0) {
             EvalArgs a = make_args(o);
             a.n = (int64_t)nu; a.memo_keys = ctx->memo.k.get(); a.memo_perm = pin; a.memo_start = ctx->memo.start.get();
-            int rows = 0;
-            rc = fail_arm(ctx, a, 0, true, a.n);
+            Collected c;
+            rc = eval_collect(ctx, "relmc_nsq_accumulate_distinct", 3, a, 0, a.n, &part, c);
             if (rc) return rc;
-            rc = launch_eval(ctx, 3, a, &rows);
-            if (rc) return rc;
-            rc = launch_finalize(ctx, rows);
-            if (rc) return rc;
-            HIP_TRY(ctx, hipMemcpyAsync(&part, ctx->dacc.get(), sizeof(part), hipMemcpyDeviceToHost, ctx->stream));
-            rc = finish_timing(ctx);
-            if (rc) return rc;
-            ms_total += ctx->last_kernel_ms;
+            ms_total += c.ms;
             RetryOut ro;
-            rc = fail_retry(ctx, o, a.fail_threshold, nullptr, ro, &ms_total);
+            rc = fail_retry(ctx, o, a.fail_threshold, nullptr, ro, &ms_total, c.known());
             if (rc) return rc;
-            for (size_t r = 0; r < ro.rec.size(); ++r)
-                acc_add_unit(&part, ro.rec[r], ro.dns[r], ro.meta[r], &ro.nodal[r * (size_t)ctx->nb], ctx->nb, ctx->ncomp, a.fail_threshold);
+            acc_add_retry(&part, ro, ctx->ncomp, a.fail_threshold);
         }
         ms_total += prep_ms;                                     // (pre-screen +) sampling + sort + run-length encoding, host-timed; the evaluation kernel above
         part.n += certified; part.n_screened += certified;
@@ -530,7 +513,7 @@ int32_t relmc_db_import(relmc_ctx* ctx, const relmc_solver_opts* opts, int64_t n
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->db.n = n_rows; ctx->db.samples = samples;
-    if (opts) { ctx->db.opts = *opts; ctx->db.has_opts = true; } else { relmc_solver_opts_default(&ctx->db.opts); ctx->db.has_opts = true; }
+    ctx->db.opts = solver_opts_or_default(opts); ctx->db.has_opts = true;
     return RELMC_OK;
 }
 

@@ -37,8 +37,7 @@ int32_t relmc_debug_mc_simulation_dense(relmc_ctx* ctx, const uint8_t* states_ho
 {
     if (!ctx || !ctx->has_case || !states_host || !dns_host || n < 0) return RELMC_ERR_INVALID;
     if (n == 0) return RELMC_OK;
-    relmc_solver_opts o;
-    if (opts) o = *opts; else relmc_solver_opts_default(&o);
+    const relmc_solver_opts o = solver_opts_or_default(opts);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int ow = mask_words(ctx), ncomp = ctx->ncomp, nb = ctx->nb;
     std::vector<uint32_t> keys((size_t)n * ow, 0u);

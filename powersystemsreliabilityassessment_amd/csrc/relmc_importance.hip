@@ -177,8 +177,7 @@ int accumulate_impl(relmc_ctx* ctx, const char* who, uint64_t seed, uint64_t fir
     if (rc) return rc;
     relmc_is_acc_zero(out);
     if (n == 0) return RELMC_OK;
-    relmc_solver_opts o;
-    if (opts) o = *opts; else relmc_solver_opts_default(&o);
+    relmc_solver_opts o = solver_opts_or_default(opts);
     o.screen = 0;                                                   // relmc_mc_simulation solves what it is handed
     double ms = 0.0;
     for (int64_t done = 0; done < n;) {

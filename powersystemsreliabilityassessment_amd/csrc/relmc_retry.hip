@@ -75,12 +75,25 @@ int fail_arm(relmc_ctx* ctx, EvalArgs& a, int64_t unit_base, bool reset, int64_t
     return RELMC_OK;
 }
 
-// units listed by the completed launches of the call (may exceed the capacity: the excess kept its first-attempt results)
-int fail_listed(relmc_ctx* ctx, uint32_t* cnt)
+int eval_collect(relmc_ctx* ctx, const char* who, int mode, EvalArgs& a, int64_t unit_base, int64_t call_units, relmc_acc* acc, Collected& c)
 {
-    *cnt = 0;
-    if (!ctx->retry.fail_count.get()) return RELMC_OK;
-    HIP_TRY(ctx, hipMemcpy(cnt, ctx->retry.fail_count.get(), sizeof(*cnt), hipMemcpyDeviceToHost));
+    int rows = 0;
+    int rc = fail_arm(ctx, a, unit_base, true, call_units);
+    if (rc == RELMC_OK) rc = launch_eval(ctx, mode, a, &rows);
+    if (rc == RELMC_OK && acc) rc = launch_finalize(ctx, rows);
+    if (rc) return rc;
+    // accumulators and the count of listed units come back in ONE synchronisation, through the context's pinned staging words (two more
+    // blocking 4-byte copies per launch used to follow the kernel)
+    auto* const st = ctx->hstage.get();
+    c.armed = a.fail_count != nullptr;
+    if ((acc && hipMemcpyAsync(&st->acc, ctx->dacc.get(), sizeof(relmc_acc), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) ||
+        (c.armed && hipMemcpyAsync(&st->fail_cnt, a.fail_count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
+        return fail(ctx, RELMC_ERR_HIP, std::string(who) + ": queueing the copy of the launch's results failed");
+    rc = finish_timing(ctx);
+    if (rc) return rc;
+    if (acc) *acc = st->acc;
+    c.listed = c.armed ? st->fail_cnt : 0u;
+    c.ms = ctx->last_kernel_ms;
     return RELMC_OK;
 }
 
@@ -117,100 +130,82 @@ int fail_retry(relmc_ctx* ctx, const relmc_solver_opts& o, double fail_threshold
     HIP_TRY(ctx, R.meta.grow(rc2 * 2));
     HIP_TRY(ctx, R.nodal.grow(rc2 * 2 * nb));
     HIP_TRY(ctx, R.scale.grow(rc2 * 2));
-    std::vector<uint32_t> keys((size_t)cnt * ow);
-    for (uint32_t r = 0; r < cnt; ++r) for (int q = 0; q < ow; ++q) keys[(size_t)r * ow + q] = out.rec[r].mask[q];
-    HIP_TRY(ctx, hipMemcpy(ctx->retry.keys.get(), keys.data(), sizeof(uint32_t) * keys.size(), hipMemcpyHostToDevice));
-    if (have_scale) {
-        std::vector<double> sc(cnt);
-        for (uint32_t r = 0; r < cnt; ++r) sc[r] = scale(out.rec[r].unit);
-        HIP_TRY(ctx, hipMemcpy(ctx->retry.scale.get(), sc.data(), sizeof(double) * cnt, hipMemcpyHostToDevice));
-    }
-    out.dns.resize(cnt); out.meta.resize(cnt); out.nodal.resize((size_t)cnt * nb);
+    out.dns.resize(cnt); out.meta.resize(cnt); out.nodal.resize((size_t)cnt * nb); out.nb = nb;
     // first the whole list under the second order, then whatever is still non-converged under the third (the sets of states the three
     // orders fail on were disjoint on the 67 RTS-96 states of the fixture).  A case without further orders (they do not fit the tile)
     // repeats the primary one, so that the callers' bookkeeping is one path.
     const bool dense_first = ctx->sw.retry_dense_first;      // tests: the listed units straight to the dense pivoted solve
+    auto converged = [](int32_t meta) { return (meta & 3) == 0 || (meta & 3) == 3; };
+    // A level evaluates the list rows idx at the scratch row `base`.  The first level that runs: every row, in place (base 0).  A later one: the
+    // rows still at status 1 or 2, compacted behind the list's rows and evaluated in ONE launch (round 2 launched once per unit), the results
+    // copied over the rows they belong to.
+    std::vector<uint32_t> idx(cnt), keys; std::vector<double> sc;
+    for (uint32_t r = 0; r < cnt; ++r) idx[r] = r;
+    size_t base = 0;
     // level 0, 1: the further static orders; level 2: the dense, partially pivoted solve (what MATLAB's `\` does under mips) for whatever
     // no static order converged on
     for (int level = dense_first ? relmc_ctx::kAlt : 0; level <= relmc_ctx::kAlt; ++level) {
         const bool dense = level == relmc_ctx::kAlt;
         const bool have = dense || alt_ensure(ctx, level) == RELMC_OK;
         if (level > 0 && !have) continue;
+        if (base) {
+            idx.clear();
+            for (uint32_t r = 0; r < cnt; ++r) if (!converged(out.meta[r])) idx.push_back(r);
+            if (idx.empty()) break;
+        }
+        const size_t m = idx.size();
+        keys.resize(m * ow); sc.resize(m);
+        for (size_t q = 0; q < m; ++q) { for (int w = 0; w < ow; ++w) keys[q * ow + w] = out.rec[idx[q]].mask[w]; if (have_scale) sc[q] = scale(out.rec[idx[q]].unit); }
+        HIP_TRY(ctx, hipMemcpy(R.keys.get() + base * ow, keys.data(), sizeof(uint32_t) * keys.size(), hipMemcpyHostToDevice));
+        if (have_scale) HIP_TRY(ctx, hipMemcpy(R.scale.get() + base, sc.data(), sizeof(double) * m, hipMemcpyHostToDevice));
         EvalArgs a = make_args(o);
         a.fail_threshold = fail_threshold;
-        a.load_scale = have_scale ? ctx->retry.scale.get() : nullptr;
-        int rows = 0, rc;
-        if (level == 0 || (dense && dense_first)) {
-            a.n = (int64_t)cnt; a.memo_keys = ctx->retry.keys.get(); a.db_first = 0; a.dns = ctx->retry.dns.get(); a.status = ctx->retry.meta.get(); a.nodal = ctx->retry.nodal.get();
-            rc = dense ? launch_eval(ctx, 6, a, &rows) : launch_eval(ctx, 4, a, &rows, nullptr, nullptr, have ? 1 : 0);
-            if (rc) return rc;
-            if (dense) ctx->retry_dense_units += cnt;
-            const double before = ctx->last_kernel_ms;
-            rc = finish_timing(ctx);
-            if (rc) return rc;
-            if (ms) *ms += ctx->last_kernel_ms;
-            ctx->last_kernel_ms = before;
-            HIP_TRY(ctx, hipMemcpy(out.meta.data(), ctx->retry.meta.get(), sizeof(int32_t) * cnt, hipMemcpyDeviceToHost));
-            if (dense) for (uint32_t r = 0; r < cnt; ++r) if ((out.meta[r] & 3) == 0 || (out.meta[r] & 3) == 3) ctx->retry_dense_converged += 1;
-        } else {
-            // what the second order left non-converged, compacted behind the list's rows and evaluated under the third order in ONE launch
-            // (round 2 launched once per unit); the results are copied over the rows they belong to
-            std::vector<uint32_t> idx;
-            for (uint32_t r = 0; r < cnt; ++r) if ((out.meta[r] & 3) == 1 || (out.meta[r] & 3) == 2) idx.push_back(r);
-            if (idx.empty()) break;
-            if (dense) ctx->retry_dense_units += (int64_t)idx.size();
-            const size_t m = idx.size(), base = (size_t)ctx->retry.rows;
-            std::vector<uint32_t> k2(m * ow); std::vector<double> s2(m);
-            for (size_t q = 0; q < m; ++q) { for (int w = 0; w < ow; ++w) k2[q * ow + w] = out.rec[idx[q]].mask[w]; if (have_scale) s2[q] = scale(out.rec[idx[q]].unit); }
-            HIP_TRY(ctx, hipMemcpy(ctx->retry.keys.get() + base * ow, k2.data(), sizeof(uint32_t) * k2.size(), hipMemcpyHostToDevice));
-            if (have_scale) HIP_TRY(ctx, hipMemcpy(ctx->retry.scale.get() + base, s2.data(), sizeof(double) * m, hipMemcpyHostToDevice));
-            a.n = (int64_t)m; a.memo_keys = ctx->retry.keys.get(); a.db_first = (int64_t)base; a.dns = ctx->retry.dns.get(); a.status = ctx->retry.meta.get(); a.nodal = ctx->retry.nodal.get();
-            a.load_scale = have_scale ? ctx->retry.scale.get() + base : nullptr;
-            rc = dense ? launch_eval(ctx, 6, a, &rows) : launch_eval(ctx, 4, a, &rows, nullptr, nullptr, level + 1);
-            if (rc) return rc;
-            const double before = ctx->last_kernel_ms;
-            rc = finish_timing(ctx);
-            if (rc) return rc;
-            if (ms) *ms += ctx->last_kernel_ms;
-            ctx->last_kernel_ms = before;
+        a.n = (int64_t)m; a.memo_keys = R.keys.get(); a.db_first = (int64_t)base; a.dns = R.dns.get(); a.status = R.meta.get(); a.nodal = R.nodal.get();
+        a.load_scale = have_scale ? R.scale.get() + base : nullptr;
+        int rows = 0;
+        int rc = dense ? launch_eval(ctx, 6, a, &rows) : launch_eval(ctx, 4, a, &rows, nullptr, nullptr, have ? level + 1 : 0);
+        if (rc) return rc;
+        const double before = ctx->last_kernel_ms;
+        rc = finish_timing(ctx);
+        if (rc) return rc;
+        if (ms) *ms += ctx->last_kernel_ms;
+        ctx->last_kernel_ms = before;
+        if (base) {
             for (size_t q = 0; q < m; ++q) {
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->retry.dns.get() + idx[q], ctx->retry.dns.get() + base + q, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->retry.meta.get() + idx[q], ctx->retry.meta.get() + base + q, sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->retry.nodal.get() + (size_t)idx[q] * nb, ctx->retry.nodal.get() + (base + q) * nb, sizeof(double) * nb, hipMemcpyDeviceToDevice, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(R.dns.get() + idx[q], R.dns.get() + base + q, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(R.meta.get() + idx[q], R.meta.get() + base + q, sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(R.nodal.get() + (size_t)idx[q] * nb, R.nodal.get() + (base + q) * nb, sizeof(double) * nb, hipMemcpyDeviceToDevice, ctx->stream));
             }
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (dense) {
-                std::vector<int32_t> m2(m);
-                HIP_TRY(ctx, hipMemcpy(m2.data(), ctx->retry.meta.get() + base, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
-                for (size_t q = 0; q < m; ++q) if ((m2[q] & 3) == 0 || (m2[q] & 3) == 3) ctx->retry_dense_converged += 1;
-            } else {
-                HIP_TRY(ctx, hipMemcpy(out.meta.data(), ctx->retry.meta.get(), sizeof(int32_t) * cnt, hipMemcpyDeviceToHost));      // what is still left, for the next level
-            }
         }
+        HIP_TRY(ctx, hipMemcpy(out.meta.data(), R.meta.get(), sizeof(int32_t) * cnt, hipMemcpyDeviceToHost));      // what is still left, for the next level
+        if (dense) {
+            ctx->retry_dense_units += (int64_t)m;
+            for (size_t q = 0; q < m; ++q) if (converged(out.meta[idx[q]])) ctx->retry_dense_converged += 1;
+        }
+        base = (size_t)R.rows;
     }
     HIP_TRY(ctx, hipMemcpy(out.dns.data(), ctx->retry.dns.get(), sizeof(double) * cnt, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(out.meta.data(), ctx->retry.meta.get(), sizeof(int32_t) * cnt, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(out.nodal.data(), ctx->retry.nodal.get(), sizeof(double) * cnt * nb, hipMemcpyDeviceToHost));
     ctx->retry_units += cnt;
-    for (uint32_t r = 0; r < cnt; ++r) if ((out.meta[r] & 3) == 0 || (out.meta[r] & 3) == 3) ctx->retry_converged += 1;
+    for (uint32_t r = 0; r < cnt; ++r) if (converged(out.meta[r])) ctx->retry_converged += 1;
     return RELMC_OK;
 }
 
 // the accumulators of one unit (what the kernel's output section adds for it), count-weighted
-void acc_add_unit(relmc_acc* acc, const FailRec& rec, double dns, int32_t meta, const double* nodal, int nb, int ncomp, double fail_threshold)
+void acc_add_unit(relmc_acc* acc, const RetryUnit& u, int nb, int ncomp, double fail_threshold)
 {
-    const long long w = (long long)rec.weight;
-    const int status = meta & 3, it = (int)((uint32_t)meta >> 8);
-    const bool fail = dns > fail_threshold;
+    const long long w = u.weight;
+    const bool fail = u.dns > fail_threshold;
     acc->n += w;
     if (fail) acc->n_fail += w;
-    if (status == 3) acc->n_singular += w;
-    if (status == 1 || status == 2) acc->n_nonconverged += w;
-    if (meta & 4) acc->n_infeasible += w;
-    acc->sum_iters += (long long)it * w;
-    if (dns != 0.0) { acc->sum_dns += (double)w * dns; acc->sum_dns2 += (double)w * dns * dns; }
-    if (fail) for (int k = 0; k < ncomp; ++k) if ((rec.mask[k >> 5] >> (k & 31)) & 1u) acc->comp_fail[k] += w;
-    for (int i = 0; i < nb; ++i) acc->sum_nodal[i] += (double)w * nodal[i];
+    if (u.status == 3) acc->n_singular += w;
+    if (u.status == 1 || u.status == 2) acc->n_nonconverged += w;
+    if (u.island_rule) acc->n_infeasible += w;
+    acc->sum_iters += (long long)u.iters * w;
+    if (u.dns != 0.0) { acc->sum_dns += (double)w * u.dns; acc->sum_dns2 += (double)w * u.dns * u.dns; }
+    if (fail) for (int k = 0; k < ncomp; ++k) if ((u.mask[k >> 5] >> (k & 31)) & 1u) acc->comp_fail[k] += w;
+    for (int i = 0; i < nb; ++i) acc->sum_nodal[i] += (double)w * u.nodal[i];
 }
 
 }  // namespace relmc_host

@@ -117,9 +117,7 @@ int32_t relmc_seq_mcsimulation(relmc_ctx* ctx, const uint8_t* states_host, const
     if (n < 0 || (n > 0 && (!states_host || !dns_host || !load_scale_host))) return fail(ctx, RELMC_ERR_INVALID, "relmc_seq_mcsimulation: bad arguments");
     if (n == 0) return RELMC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    relmc_solver_opts o;
-    if (opts) o = *opts; else relmc_solver_opts_default(&o);
-    return pipe_run(ctx, states_host, load_scale_host, n, o, 0.01 /* CURTAIL_THRESHOLD, seqMain.m:41 */, dns_host, nodal_host, status_host, iters_host);
+    return pipe_run(ctx, states_host, load_scale_host, n, solver_opts_or_default(opts), 0.01 /* CURTAIL_THRESHOLD, seqMain.m:41 */, dns_host, nodal_host, status_host, iters_host);
 }
 
 int32_t relmc_seq_years(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int32_t n_years, const relmc_solver_opts* opts,
@@ -131,8 +129,7 @@ int32_t relmc_seq_years(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int3
     relmc_acc_zero(acc_out);
     if (n_years == 0) return RELMC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    relmc_solver_opts o;
-    if (opts) o = *opts; else relmc_solver_opts_default(&o);
+    const relmc_solver_opts o = solver_opts_or_default(opts);
     const int hpy = ctx->hseq.hpy;
     // the device buffers of a step live in the context and only ever grow
     const size_t nh = (size_t)n_years * hpy, words = nh * (size_t)ctx->hseq.mw;
@@ -149,7 +146,7 @@ int32_t relmc_seq_years(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int3
     bool ok = hipMemsetAsync(dcurt, 0, nh * sizeof(double), ctx->stream) == hipSuccess;
     // screen = 1 (relmc_screen.hip): the contingency hours are counted as before, but only the ones the zero-curtailment certificate does not cover
     // -- at the hour's own load factor -- are listed for the interior point; a covered hour's curtailment stays the 0 it was set to above
-    const bool screen = o.screen != 0 && ctx->screen.tab.valid != 0;
+    const bool screen = screen_active(ctx, o);
     uint32_t* const dncont = dcounts + Q.counts.size() / 2;
     if (screen) ok = ok && screen_seq_compact(ctx, dm, n_years, dhours, dcounts, dncont) == RELMC_OK;
     else hipLaunchKernelGGL(relmc_seq_compact_kernel, dim3(n_years), dim3(256), 0, ctx->stream, dm, hpy, ctx->hseq.mw, dhours, dcounts);
@@ -172,26 +169,18 @@ int32_t relmc_seq_years(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int3
         a.fail_threshold = curtail_threshold;
         a.n = nlp; a.seq_masks = dm; a.seq_offsets = doff; a.seq_hours = dhours; a.load_factors = ctx->dlf.get(); a.curt = dcurt;
         a.seq_nyears = n_years; a.seq_hpy = hpy;
-        int blocks = 0;
-        rc = fail_arm(ctx, a, 0, true, a.n);
+        Collected c;
+        rc = eval_collect(ctx, "relmc_seq_years", 2, a, 0, a.n, acc_out, c);
         if (rc) return rc;
-        rc = launch_eval(ctx, 2, a, &blocks);
-        if (rc) return rc;
-        // accumulators and the count of listed hours in one synchronisation (pinned staging), as in the fused non-sequential pass
-        if (launch_finalize(ctx, blocks) != RELMC_OK || hipMemcpyAsync(&ctx->hstage.get()->acc, ctx->dacc.get(), sizeof(relmc_acc), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            (a.fail_count && hipMemcpyAsync(&ctx->hstage.get()->fail_cnt, ctx->retry.fail_count.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)) return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: finalize failed");
-        rc = finish_timing(ctx);
-        if (rc) return rc;
-        *acc_out = ctx->hstage.get()->acc;
-        const uint32_t listed = a.fail_count ? ctx->hstage.get()->fail_cnt : 0u;
-        ms += ctx->last_kernel_ms;
+        ms += c.ms;
         RetryOut ro;                                                   // hours the primary elimination order did not converge on
         const ScaleFn scale = [&](unsigned long long u) { return ctx->hlf[(size_t)(u % (unsigned long long)hpy)]; };
-        rc = fail_retry(ctx, o, curtail_threshold, &scale, ro, &ms, a.fail_count ? &listed : nullptr);
+        rc = fail_retry(ctx, o, curtail_threshold, &scale, ro, &ms, c.known());
         if (rc) return rc;
-        for (size_t r = 0; r < ro.rec.size(); ++r) {
-            acc_add_unit(acc_out, ro.rec[r], ro.dns[r], ro.meta[r], &ro.nodal[r * (size_t)ctx->nb], ctx->nb, ctx->ncomp, curtail_threshold);
-            if (hipMemcpy(dcurt + ro.rec[r].unit, &ro.dns[r], sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: H2D failed");
+        acc_add_retry(acc_out, ro, ctx->ncomp, curtail_threshold);
+        for (size_t r = 0; r < ro.size(); ++r) {
+            const RetryUnit u = ro[r];
+            if (hipMemcpy(dcurt + u.unit, &u.dns, sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: H2D failed");
         }
     }
     acc_out->n += certified; acc_out->n_screened += certified;

@@ -105,12 +105,12 @@ int pipe_run(relmc_ctx* ctx, const uint8_t* states, const double* load_scale, in
     const ScaleFn scale = [&](unsigned long long u) { return load_scale[u]; };
     rc = fail_retry(ctx, o, fail_threshold, load_scale ? &scale : nullptr, ro, &kernel_ms);
     if (rc) return rc;
-    for (size_t r = 0; r < ro.rec.size(); ++r) {              // the second attempt's results in the place of the first's
-        const size_t u = (size_t)ro.rec[r].unit;
-        dns[u] = ro.dns[r];
-        if (nodal) std::memcpy(nodal + u * nb, &ro.nodal[r * nb], sizeof(double) * nb);
-        if (status) status[u] = ro.meta[r] & 3;
-        if (iters) iters[u] = (int32_t)((uint32_t)ro.meta[r] >> 8);
+    for (size_t r = 0; r < ro.size(); ++r) {                  // the second attempt's results in the place of the first's
+        const RetryUnit u = ro[r];
+        dns[u.unit] = u.dns;
+        if (nodal) std::memcpy(nodal + u.unit * nb, u.nodal, sizeof(double) * nb);
+        if (status) status[u.unit] = u.status;
+        if (iters) iters[u.unit] = u.iters;
     }
     ctx->last_kernel_ms = kernel_ms;
     return RELMC_OK;
@@ -124,13 +124,12 @@ int nsq_accumulate_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int
     if (n < 0 || !acc_out) return fail(ctx, RELMC_ERR_INVALID, "relmc_nsq_accumulate: bad arguments");
     relmc_acc_zero(acc_out);
     if (n == 0) return RELMC_OK;
-    relmc_solver_opts o;
-    if (opts) o = *opts; else relmc_solver_opts_default(&o);
+    const relmc_solver_opts o = solver_opts_or_default(opts);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // a wavefront row counts its scenarios in 32 bits: split very large ranges
     // screen = 1 (relmc_screen.hip): a pre-pass draws the masks and runs the zero-curtailment certificate, one thread per sample; only the samples it
     // does not cover are solved (MODE 7, from the stored masks, in ascending sample order), the others add 1 to n and to n_screened
-    const bool screen = o.screen != 0 && ctx->screen.tab.valid != 0;
+    const bool screen = screen_active(ctx, o);
     const int64_t kMaxPerLaunch = screen ? kScreenChunk : (int64_t)1 << 31;
     double ms_total = 0.0;
     for (int64_t done = 0; done < n;) {
@@ -147,41 +146,29 @@ int nsq_accumulate_impl(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int
             certified = m - (int64_t)ns;
             a.n = (int64_t)ns; a.memo_keys = ctx->screen.keys.get(); a.memo_perm = ctx->screen.idx.get();
         }
-        int blocks = 0;
         relmc_acc part;
         relmc_acc_zero(&part);
-        uint32_t listed = 0;
+        Collected c;
         for (int attempt = 0; a.n > 0; ++attempt) {
-            int rc = fail_arm(ctx, a, done, true, m);
+            int rc = eval_collect(ctx, "relmc_nsq_accumulate", screen ? 7 : 0, a, done, m, &part, c);
             if (rc) return rc;
-            rc = launch_eval(ctx, screen ? 7 : 0, a, &blocks);
-            if (rc) return rc;
-            rc = launch_finalize(ctx, blocks);
-            if (rc) return rc;
-            // accumulators and the count of listed units come back in ONE synchronisation, through the context's pinned staging words (two more
-            // blocking 4-byte copies per launch used to follow the kernel)
-            HIP_TRY(ctx, hipMemcpyAsync(&ctx->hstage.get()->acc, ctx->dacc.get(), sizeof(relmc_acc), hipMemcpyDeviceToHost, ctx->stream));
-            if (a.fail_count) HIP_TRY(ctx, hipMemcpyAsync(&ctx->hstage.get()->fail_cnt, ctx->retry.fail_count.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            rc = finish_timing(ctx);
-            if (rc) return rc;
-            ms_total += ctx->last_kernel_ms;
-            part = ctx->hstage.get()->acc;
+            ms_total += c.ms;
             // more non-converged units than the list holds (a case the calibration did not foresee): a longer list and the same chunk again --
             // the launch is a function of (seed, range) alone, so the second one lists them all
-            listed = a.fail_count ? ctx->hstage.get()->fail_cnt : 0u;
-            if (a.fail_list == nullptr || listed <= ctx->retry.fail.size() || ctx->retry.fail.size() >= kFailCapMax || attempt >= 2) break;
+            if (!c.armed || c.listed <= ctx->retry.fail.size() || ctx->retry.fail.size() >= kFailCapMax || attempt >= 2) break;
             HIP_TRY(ctx, hipMemset(ctx->retry.fail_count.get(), 0, ctx->retry.kCountBytes));
-            rc = fail_list_ensure(ctx, listed + listed / 8 > kFailCapMax ? kFailCapMax : listed + listed / 8);
+            rc = fail_list_ensure(ctx, c.listed + c.listed / 8 > kFailCapMax ? kFailCapMax : c.listed + c.listed / 8);
             if (rc) return rc;
         }
         part.n += certified; part.n_screened += certified;
         int rc = RELMC_OK;
         RetryOut ro;
-        if (a.n > 0) rc = fail_retry(ctx, o, a.fail_threshold, nullptr, ro, &ms_total, a.fail_count ? &listed : nullptr);
+        if (a.n > 0) rc = fail_retry(ctx, o, a.fail_threshold, nullptr, ro, &ms_total, c.known());
         if (rc) return rc;
-        for (size_t r = 0; r < ro.rec.size(); ++r) {
-            acc_add_unit(&part, ro.rec[r], ro.dns[r], ro.meta[r], &ro.nodal[r * (size_t)ctx->nb], ctx->nb, ctx->ncomp, a.fail_threshold);
-            if (dns_dev) HIP_TRY(ctx, hipMemcpy(dns_dev + ro.rec[r].unit, &ro.dns[r], sizeof(double), hipMemcpyHostToDevice));
+        acc_add_retry(&part, ro, ctx->ncomp, a.fail_threshold);
+        for (size_t r = 0; dns_dev && r < ro.size(); ++r) {
+            const RetryUnit u = ro[r];
+            HIP_TRY(ctx, hipMemcpy(dns_dev + u.unit, &u.dns, sizeof(double), hipMemcpyHostToDevice));
         }
         relmc_acc_merge(acc_out, &part);
         done += m;
@@ -198,37 +185,27 @@ int mc_simulation_dev_impl(relmc_ctx* ctx, const uint8_t* states_dev, int64_t n,
     if (!ctx->has_case) return fail(ctx, RELMC_ERR_NO_CASE, "relmc_mc_simulation: no case loaded");
     if (n < 0 || (n > 0 && (!states_dev || !dns_dev))) return fail(ctx, RELMC_ERR_INVALID, "relmc_mc_simulation: bad arguments");
     if (n == 0) return RELMC_OK;
-    relmc_solver_opts o;
-    if (opts) o = *opts; else relmc_solver_opts_default(&o);
+    const relmc_solver_opts o = solver_opts_or_default(opts);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     EvalArgs a = make_args(o);
     a.n = n; a.states = states_dev; a.dns = dns_dev; a.nodal = nodal_dev; a.status = status_dev; a.iters = iters_dev;
-    int blocks = 0;
-    int rc = fail_arm(ctx, a, 0, true, n);
+    relmc_acc acc;                                        // the launch's partial records hold the island-rule count (of the units it did not list)
+    Collected c;
+    int rc = eval_collect(ctx, "relmc_mc_simulation", 1, a, 0, n, n_infeasible_out ? &acc : nullptr, c);
     if (rc) return rc;
-    rc = launch_eval(ctx, 1, a, &blocks);
-    if (rc) return rc;
-    if (n_infeasible_out) {                               // the launch's partial records hold the count (of the units it did not list)
-        rc = launch_finalize(ctx, blocks);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(&ctx->hstage.get()->acc, ctx->dacc.get(), sizeof(relmc_acc), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    rc = finish_timing(ctx);
-    if (rc) return rc;
-    if (n_infeasible_out) *n_infeasible_out = ctx->hstage.get()->acc.n_infeasible;
+    if (n_infeasible_out) *n_infeasible_out = acc.n_infeasible;
     RetryOut ro;
-    double ms = ctx->last_kernel_ms;
-    rc = fail_retry(ctx, o, a.fail_threshold, nullptr, ro, &ms);
+    rc = fail_retry(ctx, o, a.fail_threshold, nullptr, ro, &c.ms, c.known());
     if (rc) return rc;
-    ctx->last_kernel_ms = ms;
-    for (size_t r = 0; r < ro.rec.size(); ++r) {          // the second attempt's results in the place of the first's
-        const size_t u = (size_t)ro.rec[r].unit, nb = (size_t)ctx->nb;
-        const int32_t st = ro.meta[r] & 3, it = (int32_t)((uint32_t)ro.meta[r] >> 8);
-        if (n_infeasible_out && (ro.meta[r] & 4)) ++*n_infeasible_out;
-        HIP_TRY(ctx, hipMemcpy(dns_dev + u, &ro.dns[r], sizeof(double), hipMemcpyHostToDevice));
-        if (nodal_dev) HIP_TRY(ctx, hipMemcpy(nodal_dev + u * nb, &ro.nodal[r * nb], sizeof(double) * nb, hipMemcpyHostToDevice));
-        if (status_dev) HIP_TRY(ctx, hipMemcpy(status_dev + u, &st, sizeof(int32_t), hipMemcpyHostToDevice));
-        if (iters_dev) HIP_TRY(ctx, hipMemcpy(iters_dev + u, &it, sizeof(int32_t), hipMemcpyHostToDevice));
+    ctx->last_kernel_ms = c.ms;
+    const size_t nb = (size_t)ctx->nb;
+    for (size_t r = 0; r < ro.size(); ++r) {              // the second attempt's results in the place of the first's
+        const RetryUnit u = ro[r];
+        if (n_infeasible_out && u.island_rule) ++*n_infeasible_out;
+        HIP_TRY(ctx, hipMemcpy(dns_dev + u.unit, &u.dns, sizeof(double), hipMemcpyHostToDevice));
+        if (nodal_dev) HIP_TRY(ctx, hipMemcpy(nodal_dev + u.unit * nb, u.nodal, sizeof(double) * nb, hipMemcpyHostToDevice));
+        if (status_dev) HIP_TRY(ctx, hipMemcpy(status_dev + u.unit, &u.status, sizeof(int32_t), hipMemcpyHostToDevice));
+        if (iters_dev) HIP_TRY(ctx, hipMemcpy(iters_dev + u.unit, &u.iters, sizeof(int32_t), hipMemcpyHostToDevice));
     }
     return RELMC_OK;
 }
@@ -253,9 +230,7 @@ int32_t relmc_mc_simulation(relmc_ctx* ctx, const uint8_t* states_host, int64_t 
     if (n < 0 || (n > 0 && (!states_host || !dns_host))) return fail(ctx, RELMC_ERR_INVALID, "relmc_mc_simulation: bad arguments");
     if (n == 0) return RELMC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    relmc_solver_opts o;
-    if (opts) o = *opts; else relmc_solver_opts_default(&o);
-    return pipe_run(ctx, states_host, nullptr, n, o, 1e-4 /* nsqMain.m:270 */, dns_host, nodal_host, status_host, iters_host);
+    return pipe_run(ctx, states_host, nullptr, n, solver_opts_or_default(opts), 1e-4 /* nsqMain.m:270 */, dns_host, nodal_host, status_host, iters_host);
 }
 
 int32_t relmc_nsq_accumulate(relmc_ctx* ctx, uint64_t seed, uint64_t first_index, int64_t n, const relmc_solver_opts* opts,

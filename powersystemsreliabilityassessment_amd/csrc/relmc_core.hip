@@ -231,9 +231,7 @@ int case_load_impl(relmc_ctx* ctx, const relmc_case_desc* d, DevCaseT<TL>& C, in
 
 int case_load_image(relmc_ctx* ctx, const relmc_case_desc* d, int order_variant)
 {
-    if (ctx->tile == 0) { auto C = std::make_unique<DevCaseT<Tile24>>(); return case_load_impl<Tile24>(ctx, d, *C, order_variant); }
-    auto C = std::make_unique<DevCaseT<Tile96>>();
-    return case_load_impl<Tile96>(ctx, d, *C, order_variant);
+    return with_case_tile(ctx->tile == 0, [&](auto& C) { return case_load_impl(ctx, d, C, order_variant); });
 }
 
 namespace {

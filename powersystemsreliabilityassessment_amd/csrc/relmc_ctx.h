@@ -26,7 +26,9 @@
 #include <cmath>
 #include <cstdint>
 #include <functional>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/relmc.h"
@@ -271,6 +273,23 @@ extern template int case_symbolic<Tile96>(const relmc_case_desc*, DevCaseT<Tile9
 inline bool fits_tile24(const relmc_case_desc* d)
 {
     return d->nb <= Tile24::NBT && d->nl <= Tile24::NLT && d->ng + d->nd <= Tile24::NIT && d->ng + d->nl <= Tile24::NCOMPMAX;
+}
+// The tile dispatch of the host code: fn(C) with a DevCaseT of the 16-lane tile or of the wide one on the heap; fn is generic in the tile
+template <class F>
+auto with_case_tile(bool tile24, F&& fn)
+{
+    if (tile24) { auto C = std::make_unique<DevCaseT<Tile24>>(); return fn(*C); }
+    auto C = std::make_unique<DevCaseT<Tile96>>();
+    return fn(*C);
+}
+// The device image of a case on the smallest tile that holds it: case_symbolic, then fn(image) -> code if that succeeded
+template <class F>
+int with_symbolic(const relmc_case_desc* d, int order_variant, const SymOpts& so, SymGeom& geom, std::string& err, F&& fn)
+{
+    return with_case_tile(fits_tile24(d), [&](auto& C) {
+        const int rc = case_symbolic(d, C, order_variant, so, geom, err);
+        return rc == RELMC_OK ? (int)fn(C) : rc;
+    });
 }
 
 // ---- relmc_core.hip -----------------------------------------------------------------------------------------------------------

@@ -97,16 +97,7 @@ int32_t relmc_debug_shape(const relmc_case_desc* d, const int32_t* order_hint, i
         if (order_hint && n_hint > 0) { so.order_hint = order_hint; so.n_hint = n_hint; }
         std::string err;
         SymGeom g;
-        int rc;
-        if (fits_tile24(d)) {
-            auto C = std::make_unique<DevCaseT<Tile24>>();
-            rc = case_symbolic<Tile24>(d, *C, 0, so, g, err);
-            if (rc == RELMC_OK) shape_of(*C, g.stash_off, g.scen_doubles, case_out);
-        } else {
-            auto C = std::make_unique<DevCaseT<Tile96>>();
-            rc = case_symbolic<Tile96>(d, *C, 0, so, g, err);
-            if (rc == RELMC_OK) shape_of(*C, g.stash_off, g.scen_doubles, case_out);
-        }
+        const int rc = with_symbolic(d, 0, so, g, err, [&](const auto& C) { shape_of(C, g.stash_off, g.scen_doubles, case_out); return (int)RELMC_OK; });
         if (rc) return rc < 0 ? rc : -rc;
     }
     return SF_COUNT;

@@ -113,6 +113,29 @@ def test_tune_order_is_deterministic_never_worse_and_validated():
         si.symbolic(case, 0, o1[:-1])
 
 
+def test_symbolic_images_match_their_pinned_digests():
+    """Everything relmc_debug_symbolic and relmc_debug_task_image write (headers and arrays) for RTS-24 / RTS-96 under the rule's three orders
+    and their shipped orders and for the random networks of this file and of tests/test_pass_shadow.py, as SHA-256 against
+    tests/golden/symbolic_image_digest.json (a refused case: its return code).  Every result of the solver is a function of these bytes, so
+    a refactoring of the scheduler must leave them alone; a deliberate change of the scheduler, the placement or the shadowing regenerates
+    the fixture (tests/golden/make_symbolic_digest.py), and such a change owes the parity pins a run (tests/tools/order_select.py)."""
+    import importlib.util
+    import json
+    import os
+    from powersystemsreliabilityassessment_amd import _lib
+    here = os.path.dirname(os.path.abspath(__file__))
+    spec = importlib.util.spec_from_file_location("make_symbolic_digest", os.path.join(here, "golden", "make_symbolic_digest.py"))
+    msd = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(msd)
+    with open(msd.FIXTURE) as f:
+        want = json.load(f)
+    cases = msd.cases()
+    assert [c[0] for c in cases] == list(want)
+    L = _lib.load()
+    got = {name: msd.digest(L, case, variant, order) for name, case, variant, order in cases}
+    assert got == want, [name for name in want if got[name] != want[name]]
+
+
 def test_shipped_rts24_order_is_what_the_tuner_returns():
     """Provenance of case24.RTS24_ELIM_ORDER: relmc_tune_order(60000 evaluations, seed 11) from the rule's order, bit for bit (the tuner is
     deterministic; a change of the scheduler or of its cost model shows up here, and the shipped orders are then due for a new tuning and a

@@ -483,6 +483,51 @@ int32_t relmc_hl1_area(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int6
  * relmc_hl1_area hold with it as they are. */
 int32_t relmc_hl1_area_tie_outages(relmc_ctx* ctx, int32_t n_ties, const double* tie_mttf_h, const double* tie_mttr_h);
 
+/* ---- sweep of the multi-area chronology: one fleet and tie history against up to 8 levels of load, tie capacity and fleet (an extension) ---- */
+/* How an area's risk falls as tie capacity is added, how much more load an area carries because it is interconnected, and what a unit is
+ * worth once neighbours lean on it are each a curve of relmc_hl1_area results; this call gives up to 8 points of such a curve from ONE
+ * walk of every chain.  It runs on the model of relmc_hl1_area_load, and on relmc_hl1_area_tie_outages' data when set: under one seed,
+ * chain c of every level sees exactly the unit and tie history of chain c of relmc_hl1_area.  The policy is INTERCONNECTED.
+ * Level j is the model it is equivalent to:
+ *   load    of area a at hour h: load_scale[a] * load[a][h] + load_shift[a], the product and the sum each rounded (no FMA; numpy's
+ *           scale * load + shift).  Entries at or above n_areas are not read.
+ *   fleet   0: every unit; 1: every unit except those whose bit is set in `withheld` (bit k & 31 of word k >> 5, k the GLOBAL unit index):
+ *           a withheld unit adds 0.0 in the same ascending loop (relmc_hl1_seq_sweep's rule and mask format).
+ *   ties    the capacity of tie t is tie_scale * cap_t (rounded) where tie_scaled is NULL or tie_scaled[t] != 0, else cap_t.  T is formed
+ *           from those capacities exactly as relmc_hl1_area forms it: parallel ties summed in tie order, only the UP ties on a step with a
+ *           tie DOWN.
+ *   Everything after T is relmc_hl1_area's: margins, the transfer solve, c_i, the flags, events, and the year's EUE in that kernel's order.
+ * Two guarantees follow:
+ *   1. Level j's year records are BITWISE those of relmc_hl1_area(INTERCONNECTED, flow) on the model loaded with level j's load curves
+ *      (numpy's scale * load + shift), the scaled tie capacities, and the withheld units' capacities as 0.0.
+ *   2. A level whose scaled ties all have tie_scale == 0 (tie_scaled == NULL: every tie) is bitwise RELMC_HL1_AREA_ISOLATED.
+ * A level's year records depend on (seed, chain, start, years_per_chain, flow, data, that level, the two masks) only: not on the other
+ * levels, their order, or how a chain range is split into calls.  acc is summed in a fixed order, so a repeated call is bitwise identical.
+ * Only the system row under RELMC_HL1_AREA_FLOW_MAX_FLOW is monotone in load and in tie capacity, and only up to the solve's 1e-4
+ * thresholds; an area's own row, and any row under FLOW_REFERENCE, need not be. */
+#define RELMC_HL1_AREA_SWEEP_MAX_LEVELS (8)
+typedef struct {
+    double load_scale[RELMC_AREA_MAX], load_shift[RELMC_AREA_MAX];
+    double tie_scale;
+    int32_t fleet;
+    int32_t reserved;
+} relmc_hl1_area_level;   /* 144 bytes, reserved = 0 */
+/* chains [first_chain, first_chain + n_chains), each years_per_chain consecutive years; flow RELMC_HL1_AREA_FLOW_*.
+ *   withheld    optional [4] mask words (128 units)
+ *   tie_scaled  optional [n_ties of relmc_hl1_area_load]
+ *   acc         [n_levels][n_areas + 1], row n_areas = the system
+ *   years_host  optional [n_levels][n_chains * years_per_chain][n_areas + 1], level-major, then chain-major
+ * RELMC_ERR_INVALID, with relmc_last_error naming the level, area, bit or tie, for: a null levels or acc; n_levels outside
+ * 1 .. RELMC_HL1_AREA_SWEEP_MAX_LEVELS; a non-finite scale or shift among the first n_areas entries; tie_scale not finite or below 0 (or a
+ * scaled capacity that is not finite); fleet not 0 or 1; reserved != 0; fleet 1 with withheld == NULL; a withheld bit at or above ngen;
+ * anything relmc_hl1_area refuses.  A refused call changes nothing; n_chains == 0 zeroes the outputs.  RELMC_ERR_NO_CASE before
+ * relmc_hl1_area_load.  The call never changes the loaded model: a relmc_hl1_area run after it is bitwise what it was before.
+ * Long chain ranges go in launches of at most ~4M year records counted over levels and rows; relmc_last_kernel_ms covers every launch. */
+int32_t relmc_hl1_area_sweep(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain,
+                             int32_t start, int32_t flow, int32_t n_levels, const relmc_hl1_area_level* levels,
+                             const uint32_t* withheld, const uint8_t* tie_scaled, relmc_hl1_seq_acc* acc,
+                             relmc_hl1_seq_year* years_host);
+
 /* ---- HL1 planning model: maintenance, energy-limited units, LFU (generating_adequancy_comparative.jl:15-120, tail_risk.jl:12-91) ---- */
 /* Year y is the global index first_year + i; hour h is 0-based; every year starts with every ELU's energy at 0; years are independent.
  * Block b of hour h of year y: philox4x32_10(ctr = (y_lo, y_hi, 0x20000000 | h, b), key = (seed_lo, seed_hi)); word j = word j & 3 of

@@ -638,6 +638,65 @@ function run_fast_sequential_simulation(eng::Engine, units_per_area::Vector{Int3
             year_indices=[getfield(y[r, t], f) for t in 1:n_years, r in 1:n + 1, f in (:lole, :eue, :lolf)])
 end
 
+"relmc_hl1_area_level (include/relmc.h): one level of relmc_hl1_area_sweep; fleet 0 = every unit, 1 = without the withheld units"
+struct Hl1AreaLevel
+    load_scale::NTuple{8,Cdouble}; load_shift::NTuple{8,Cdouble}; tie_scale::Cdouble; fleet::Int32; reserved::Int32
+end
+const HL1_AREA_SWEEP_MAX_LEVELS = 8                                           # RELMC_HL1_AREA_SWEEP_MAX_LEVELS
+
+"""
+run_area_sweep (an extension beyond the reference): the INTERCONNECTED chronology of the model that run_fast_sequential_simulation loaded
+last on this engine (tie outages included), same chains under one seed, against up to 8 levels in one walk of the chains.  `levels`
+holds (load_scale, load_shift, tie_scale, withheld) with one scale and one shift per area: area a sees load_scale[a] * load + load_shift[a],
+every scaled tie tie_scale times its capacity and, if withheld, the fleet without the units `withheld_units` (1-based global indices).
+`scaled_ties` (1-based) are the ties tie_scale applies to (default: all).  Returns LOLE, EUE and LOLF as n_levels x (n_areas + 1) (the last
+column is the system) and the per-year indices (n_levels x years x (n_areas + 1) x 3).  Only the system row under :max_flow is monotone in
+load and tie capacity.
+"""
+function run_area_sweep(eng::Engine, n_areas::Integer, n_ties::Integer, n_years::Integer,
+                        levels::Vector{<:Tuple{Vector{Float64},Vector{Float64},Real,Bool}};
+                        withheld_units::Vector{<:Integer}=Int[], scaled_ties::Union{Nothing,Vector{<:Integer}}=nothing, seed::Integer=1,
+                        chains::Integer=1, start::Symbol=:all_up, flow::Symbol=:max_flow)
+    (n_years >= 1 && chains >= 1 && n_years % chains == 0) || throw(ArgumentError("n_years must be a positive multiple of chains"))
+    nl = length(levels)
+    1 <= nl <= HL1_AREA_SWEEP_MAX_LEVELS || throw(ArgumentError("between 1 and $HL1_AREA_SWEEP_MAX_LEVELS levels"))
+    1 <= n_areas <= AREA_MAX || throw(ArgumentError("1..$AREA_MAX areas"))
+    all(length(l[1]) == n_areas && length(l[2]) == n_areas for l in levels) || throw(ArgumentError("one load scale and shift per area"))
+    all(1 <= k <= 128 for k in withheld_units) || throw(ArgumentError("withheld_units must be unit indices"))
+    (isempty(withheld_units) && any(l[4] for l in levels)) && throw(ArgumentError("a withheld level needs withheld_units"))
+    pad(v) = ntuple(i -> i <= n_areas ? Float64(v[i]) : 0.0, 8)
+    lv = [Hl1AreaLevel(pad(l[1]), pad(l[2]), Float64(l[3]), l[4] ? Int32(1) : Int32(0), Int32(0)) for l in levels]
+    mask = zeros(UInt32, 4)
+    for k in withheld_units
+        mask[((k - 1) >> 5) + 1] |= UInt32(1) << ((k - 1) & 31)
+    end
+    tmask = zeros(UInt8, max(n_ties, 1))
+    if scaled_ties !== nothing
+        all(1 <= t <= n_ties for t in scaled_ties) || throw(ArgumentError("scaled_ties must be tie indices"))
+        tmask[scaled_ties] .= 0x01
+    end
+    rows = n_areas + 1
+    yrs = Vector{Hl1SeqYear}(undef, nl * n_years * rows)
+    raw = zeros(UInt8, 56 * nl * rows)                                        # relmc_hl1_seq_acc[nl][rows], contiguous
+    check(ccall((:relmc_hl1_area_sweep, LIB), Int32,
+                (Ptr{Cvoid}, UInt64, UInt64, Int64, Int32, Int32, Int32, Int32, Ptr{Hl1AreaLevel}, Ptr{UInt32}, Ptr{UInt8}, Ptr{UInt8},
+                 Ptr{Hl1SeqYear}),
+                eng.h, seed, 0, chains, n_years ÷ chains, HL1_START[start], HL1_AREA_FLOW[flow], nl, lv,
+                isempty(withheld_units) ? C_NULL : mask, scaled_ties === nothing ? C_NULL : tmask, raw, yrs),
+          eng.h, "relmc_hl1_area_sweep")
+    sums = reshape(reinterpret(Float64, raw), 7, rows, nl)                    # rows 2 .. 4: sum_lole, sum_eue, sum_lolf
+    Y = reshape(yrs, rows, n_years, nl)
+    return (lole=[sums[2, r, j] / n_years for j in 1:nl, r in 1:rows], eue=[sums[3, r, j] / n_years for j in 1:nl, r in 1:rows],
+            lolf=[sums[4, r, j] / n_years for j in 1:nl, r in 1:rows],
+            year_indices=[getfield(Y[r, t, j], f) for j in 1:nl, t in 1:n_years, r in 1:rows, f in (:lole, :eue, :lolf)])
+end
+
+# Layout of the multi-area sweep level, kept apart from LAYOUT (tests/test_hl1_area_sweep_host.py compares it with the C compiler's and
+# with ctypes)
+const LAYOUT_HL1_AREA_SWEEP = [
+    ("relmc_hl1_area_level", 144, [("load_scale", 0), ("load_shift", 64), ("tie_scale", 128), ("fleet", 136), ("reserved", 140)]),
+]
+
 # Structs the HL1 planning wrappers pass (the planning calls reuse the sequential model's records; no struct of their own), checked
 # against the C compiler by tests/test_hl1_plan_host.py
 const LAYOUT_HL1_PLAN = [

@@ -150,6 +150,12 @@ AREA_MAX = 8                                       # RELMC_AREA_MAX
 HL1_AREA_ISOLATED, HL1_AREA_INTERCONNECTED = 0, 1  # RELMC_HL1_AREA_*
 HL1_AREA_FLOW_REFERENCE, HL1_AREA_FLOW_MAX_FLOW = 0, 1   # RELMC_HL1_AREA_FLOW_*
 HL1_TIE_MAX, HL1_TIE_DRAW_BASE = 32, 128           # RELMC_HL1_TIE_MAX, RELMC_HL1_TIE_DRAW_BASE
+HL1_AREA_SWEEP_MAX_LEVELS = 8                      # RELMC_HL1_AREA_SWEEP_MAX_LEVELS
+
+
+class Hl1AreaLevel(C.Structure):                   # relmc_hl1_area_level (144 bytes)
+    _fields_ = [("load_scale", C.c_double * AREA_MAX), ("load_shift", C.c_double * AREA_MAX), ("tie_scale", C.c_double),
+                ("fleet", C.c_int32), ("reserved", C.c_int32)]
 
 
 class SeqOpts(C.Structure):

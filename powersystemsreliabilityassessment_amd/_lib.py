@@ -23,7 +23,7 @@ EXPORTS = [
     "relmc_mc_simulation", "relmc_mc_simulation_dev", "relmc_nsq_accumulate", "relmc_nsq_accumulate_distinct",
     "relmc_last_kernel_ms", "relmc_acc_zero", "relmc_acc_merge", "relmc_nsq_indices",
     "relmc_nsq_run", "relmc_hl1_load", "relmc_hl1_nsq", "relmc_hl1_seq_load", "relmc_hl1_seq", "relmc_hl1_seq_events", "relmc_hl1_seq_sweep",
-    "relmc_hl1_plan_load", "relmc_hl1_plan", "relmc_hl1_area_load", "relmc_hl1_area", "relmc_hl1_area_tie_outages",
+    "relmc_hl1_plan_load", "relmc_hl1_plan", "relmc_hl1_area_load", "relmc_hl1_area", "relmc_hl1_area_tie_outages", "relmc_hl1_area_sweep",
     "relmc_comm_unique_id", "relmc_comm_init", "relmc_comm_allreduce_acc", "relmc_comm_destroy", "relmc_comm_set_host_allreduce", "relmc_comm_info",
     "relmc_db_reset", "relmc_nsq_db_batch", "relmc_db_accumulate", "relmc_db_size", "relmc_db_export", "relmc_db_import",
     "relmc_seq_load", "relmc_seq_mcsampling", "relmc_seq_mcsimulation", "relmc_seq_years", "relmc_retry_stats", "relmc_retry_overflow", "relmc_retry_dense_stats", "relmc_case_order",
@@ -157,6 +157,9 @@ def load():
     L.relmc_hl1_area.restype = C.c_int32
     L.relmc_hl1_area_tie_outages.argtypes = [vp, C.c_int32, dp, dp]
     L.relmc_hl1_area_tie_outages.restype = C.c_int32
+    L.relmc_hl1_area_sweep.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.POINTER(_abi.Hl1AreaLevel), _abi.c_uint32_p, u8p, C.POINTER(_abi.Hl1SeqAcc), C.POINTER(_abi.Hl1SeqYear)]
+    L.relmc_hl1_area_sweep.restype = C.c_int32
     L.relmc_comm_unique_id.argtypes = [u8p]
     L.relmc_comm_unique_id.restype = C.c_int32
     L.relmc_comm_init.argtypes = [vp, C.c_int32, C.c_int32, u8p]

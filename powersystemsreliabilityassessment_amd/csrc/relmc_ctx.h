@@ -16,6 +16,7 @@
 //                        the record reduction and unit check of every HL1 chronology track
 //   relmc_plan.hip       the HL1 planning model's Monte Carlo (relmc_hl1_plan)
 //   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area); its rows are summed by relmc_seq.hip's record reduction
+//   relmc_area_sweep.hip the sweep of that chronology over load, tie and fleet levels (relmc_hl1_area_sweep, kernel in relmc_area_sweep_kernels.h)
 //   relmc_screen.hip     the zero-curtailment pre-screen (relmc_solver_opts.screen): certificate tables, pre-pass kernels, worklists
 //   relmc_importance.hip importance sampling for the non-sequential track: tilted sampler with likelihood ratios, weighted reductions (kernels in
 //                        relmc_is_kernels.h), the cross-entropy tuner and the weighted run loop
@@ -199,6 +200,8 @@ struct relmc_ctx {
         int ngen = 0, nhours = 0, n_areas = 0; DevBuf<relmc::AreaCase> dcase; DevBuf<double> load, years, part;
         std::vector<int32_t> tie_from, tie_to; std::vector<double> tie_cap;
         bool tie_outages = false, tie_fail = false; DevBuf<relmc::AreaTies> dties;
+        // relmc_hl1_area_sweep (relmc_area_sweep.hip): the levels' table of a call, grow-only per-level, per-row year records and partials
+        DevBuf<relmc::AreaSweepTab> sweep_tab; DevBuf<double> sweep_years, sweep_part;
     } hl1_area;
     // zero-curtailment pre-screen (relmc_screen.hip): certificate tables of the case (device pointers inside tab), grow-only work buffers of a pre-pass
     struct Screen {

@@ -287,6 +287,22 @@ struct AreaTies {
     double cap[AREA_TIE_MAX], mttf[AREA_TIE_MAX], mttr[AREA_TIE_MAX];
     double q[AREA_TIE_MAX];                                  // mttr / (mttf + mttr)
 };
-
+// The levels of relmc_hl1_area_sweep as the kernel reads them (AREA_SWEEP_MAX_LEVELS = RELMC_HL1_AREA_SWEEP_MAX_LEVELS), prepared by the
+// host: 7.2 KB at 8 levels, beyond the 4 KB kernel-argument segment, so the table lives in a device buffer of the context and every read
+// of it is a scalar load at a wave-uniform address.
+constexpr int AREA_SWEEP_MAX_LEVELS = 8;
+struct AreaSweepLevelTab {
+    double scale[AREA_MAX], shift[AREA_MAX];                 // load of area a: scale[a] * load[a][h] + shift[a]
+    double tie[AREA_MAX * AREA_MAX];                         // the level's T with every tie UP, formed as relmc_hl1_area_load forms AreaCase::tie
+    double cap[AREA_TIE_MAX];                                // the level's capacity of tie t (read with outage data only)
+};
+struct AreaSweepTab {
+    AreaSweepLevelTab lv[AREA_SWEEP_MAX_LEVELS];
+    uint32_t withheld[4];                                    // bit k & 31 of word k >> 5: global unit k is not part of fleet 1
+    int32_t n_levels;
+    uint32_t fleet1;                                         // bit j: level j uses fleet 1
+    uint32_t solve;                                          // bit j: a tie of level j has a capacity > 0 (else T is all zero in every step)
+    int32_t pad;
+};
 
 }  // namespace relmc

@@ -427,6 +427,61 @@ int32_t relmc_hl1_seq_sweep(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain,
                             const uint32_t* withheld, relmc_hl1_seq_acc* acc,
                             relmc_hl1_seq_year* years_host);
 
+/* ---- energy storage on the HL1 sequential chronology: state of charge carried from hour to hour (an extension beyond the reference) ---- */
+/* What a battery does to LOLE, EUE and LOLF exists only on a chronology: its state of charge couples the hours.  Up to 8 storages, given
+ * in the call (as the sweep's levels are: no load call, no model state in the context), discharge into a shortfall of the fleet of
+ * relmc_hl1_seq_load and charge from its surplus generation only.  Storages never fail.
+ * Chronology  relmc_hl1_seq's, word for word (model of relmc_hl1_seq_load, draws (seed, chain, k | 0x40000000, event), start rules, no FMA,
+ *             DOWN on steps [ceil(T_odd), ceil(T_even)), cap = sum over the UP units in ascending order): under one seed, chain c sees
+ *             exactly the fleet history of chain c of relmc_hl1_seq.
+ * Load        L(h) = scale * load[h] + shift, the product and the sum each rounded (relmc_hl1_seq_sweep's rule).
+ * State       storage i has a state of charge s_i in MWh: soc0_mwh before step 1 of every chain, carried from step to step and from year
+ *             to year inside a chain.
+ * Arithmetic  every operation below is a separate, correctly rounded fp64 operation (no contraction, no FMA); min / max of two numbers.
+ * Short step, cap < L:   need = L - cap; for i ascending while need > 0:
+ *                            avail = min(discharge_mw_i, s_i * eta_discharge_i), x = min(avail, need),
+ *                            s_i = max(0, s_i - x / eta_discharge_i), need = need - x.
+ *                        The step is a loss step iff need > 0 afterwards, with deficit need; with need == 0 afterwards it counts in
+ *                        served_hours.  The sum of the x (i ascending) goes to discharged_mwh.
+ * Long step, cap > L:    surplus = cap - L; for i ascending while surplus > 0:
+ *                            room = (energy_mwh_i - s_i) / eta_charge_i, y = min(min(charge_mw_i, room), surplus),
+ *                            s_i = min(energy_mwh_i, s_i + y * eta_charge_i), surplus = surplus - y.
+ *                        The sum of the y (i ascending) goes to charged_mwh.  A step with cap == L does nothing.
+ * Year records  loss hours, EUE and loss events of the steps left after storage by relmc_hl1_seq's rules (step 1 counts, an event across a
+ *             year boundary counts once, in the year it starts); the EUE of a year is summed in relmc_hl1_seq's order (the lanes'
+ *             partials, then the fixed butterfly).  served_hours, discharged_mwh and charged_mwh of a year are summed over its steps in
+ *             that same fixed order.
+ * Consequences
+ *   - With n_storage == 0 the year records are bitwise those of relmc_hl1_seq_sweep's level (scale, shift, fleet 0), and so are they when
+ *     every storage has discharge_mw == 0, or energy_mwh == 0, or soc0_mwh == 0 together with charge_mw == 0; at (1.0, 0.0) they are
+ *     bitwise relmc_hl1_seq's.  The storage records are then all zero.
+ *   - served_hours + lole of a year equals that no-storage run's lole of the year exactly.
+ *   - The storages deliver at most sum of discharge_mw in any hour, so for LOLE and EUE the risk with storage at load L + x is at least the
+ *     no-storage risk at L once x >= sum of discharge_mw: the ELCC of a set of storages lies in [0, sum of discharge_mw]. */
+#define RELMC_HL1_MAX_STORAGE 8
+typedef struct { double charge_mw, discharge_mw, energy_mwh, eta_charge, eta_discharge, soc0_mwh; } relmc_hl1_storage;          /* 48 bytes */
+typedef struct { double served_hours, discharged_mwh, charged_mwh; } relmc_hl1_storage_year;   /* short hours fully served, MWh delivered, MWh of surplus taken */
+typedef struct {
+    int64_t years;                                                          /* simulated years summed */
+    double sum_lole, sum_eue, sum_lolf, sum_lole2, sum_eue2, sum_lolf2;
+    double sum_served, sum_discharged, sum_charged, sum_served2, sum_discharged2, sum_charged2;
+} relmc_hl1_storage_acc;
+/* chains [first_chain, first_chain + n_chains), each years_per_chain consecutive years, of the model loaded by relmc_hl1_seq_load
+ * (RELMC_ERR_NO_CASE before that call).  RELMC_ERR_INVALID, with relmc_last_error naming the storage and the field, for: a null ctx or
+ * acc; n_storage outside 0 .. RELMC_HL1_MAX_STORAGE; n_storage > 0 with storage == NULL; a non-finite scale, shift or storage field; a
+ * negative charge_mw, discharge_mw or energy_mwh; an efficiency outside (0, 1]; soc0_mwh outside [0, energy_mwh]; anything relmc_hl1_seq
+ * refuses.  A refused call changes nothing; n_chains == 0 zeroes the outputs.
+ *   storage             [n_storage], taken in this order at every step
+ *   years_host          optional [n_chains * years_per_chain], chain-major
+ *   storage_years_host  optional [n_chains * years_per_chain], chain-major
+ * Results depend on (seed, chain, start, years_per_chain, data, scale, shift, storage) only, not on how a chain range is split into
+ * calls; the sums of `acc` are taken in a fixed order, so a repeated call is bitwise identical.  Long chain ranges go in launches of at
+ * most ~4M year records counted over both record rows, as in relmc_hl1_seq; relmc_last_kernel_ms covers every launch. */
+int32_t relmc_hl1_seq_storage(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain,
+                              int32_t start, double scale, double shift, int32_t n_storage, const relmc_hl1_storage* storage,
+                              relmc_hl1_storage_acc* acc, relmc_hl1_seq_year* years_host,
+                              relmc_hl1_storage_year* storage_years_host);
+
 /* ---- HL1 multi-area chronology with tie-line transfers (AdequacyAssessmentII.jl:73-250 solve_curtailment_fast / run_fast_sequential_simulation) ---- */
 /* The chronology is relmc_hl1_seq's, word for word: draws (seed, chain, k | 0x40000000, event) with k the GLOBAL unit index (units stored
  * area-major: area 0's units, then area 1's, ...), the same start rules, steps n = 1 .. Y*H with the state carried across years, no FMA.

@@ -559,6 +559,46 @@ const LAYOUT_HL1_SWEEP = [
     ("relmc_hl1_sweep_level", 24, [("scale", 0), ("shift", 8), ("fleet", 16), ("reserved", 20)]),
 ]
 
+"relmc_hl1_storage (include/relmc.h, 48 bytes): one energy storage of relmc_hl1_seq_storage; powers in MW, energies in MWh, efficiencies in (0, 1]"
+struct Hl1Storage
+    charge_mw::Cdouble; discharge_mw::Cdouble; energy_mwh::Cdouble; eta_charge::Cdouble; eta_discharge::Cdouble; soc0_mwh::Cdouble
+end
+"relmc_hl1_storage_year: short hours fully served by the storages, MWh delivered and MWh of surplus taken in one simulated year"
+struct Hl1StorageYear
+    served_hours::Cdouble; discharged_mwh::Cdouble; charged_mwh::Cdouble
+end
+mutable struct Hl1StorageAcc
+    years::Int64; sum_lole::Cdouble; sum_eue::Cdouble; sum_lolf::Cdouble; sum_lole2::Cdouble; sum_eue2::Cdouble; sum_lolf2::Cdouble
+    sum_served::Cdouble; sum_discharged::Cdouble; sum_charged::Cdouble; sum_served2::Cdouble; sum_discharged2::Cdouble; sum_charged2::Cdouble
+    Hl1StorageAcc() = new()
+end
+const HL1_MAX_STORAGE = 8                                                  # RELMC_HL1_MAX_STORAGE
+
+"""
+run_sequential_storage (an extension beyond the reference): run_sequential_mc's chronology, same arguments and same chains under one
+seed, at the load scale * hourly_load + shift with up to 8 energy storages.  A storage discharges into a shortfall of the fleet and
+charges from its surplus only; its state of charge carries from hour to hour and from year to year inside a chain.  Returns LOLE, EUE and
+LOLF of the hours left after storage, the hours served and the MWh cycled per year, and the per-year records.
+"""
+function run_sequential_storage(eng::Engine, capacity::Vector{Float64}, mttf::Vector{Float64}, mttr::Vector{Float64},
+                                hourly_load::Vector{Float64}, storages::Vector{Hl1Storage}, years::Integer;
+                                scale::Real=1.0, shift::Real=0.0, seed::Integer=1, chains::Integer=1, start::Symbol=:all_up)
+    (years >= 1 && chains >= 1 && years % chains == 0) || throw(ArgumentError("years must be a positive multiple of chains"))
+    length(storages) <= HL1_MAX_STORAGE || throw(ArgumentError("at most $HL1_MAX_STORAGE storages"))
+    check(ccall((:relmc_hl1_seq_load, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}),
+                eng.h, length(capacity), capacity, mttf, mttr, length(hourly_load), hourly_load), eng.h, "relmc_hl1_seq_load")
+    acc = Hl1StorageAcc()
+    yrs = Vector{Hl1SeqYear}(undef, years); sty = Vector{Hl1StorageYear}(undef, years)
+    check(ccall((:relmc_hl1_seq_storage, LIB), Int32,
+                (Ptr{Cvoid}, UInt64, UInt64, Int64, Int32, Int32, Cdouble, Cdouble, Int32, Ptr{Hl1Storage}, Ref{Hl1StorageAcc}, Ptr{Hl1SeqYear},
+                 Ptr{Hl1StorageYear}),
+                eng.h, seed, 0, chains, years ÷ chains, HL1_START[start], Float64(scale), Float64(shift), length(storages),
+                isempty(storages) ? C_NULL : storages, acc, yrs, sty), eng.h, "relmc_hl1_seq_storage")
+    return (lole_hours_yr=acc.sum_lole / years, eue_mwh_yr=acc.sum_eue / years, lolf_occ_yr=acc.sum_lolf / years,
+            served_hours_yr=acc.sum_served / years, discharged_mwh_yr=acc.sum_discharged / years, charged_mwh_yr=acc.sum_charged / years,
+            years=yrs, storage_years=sty)
+end
+
 # Layout of the HL1 sequential structs, kept apart from LAYOUT (tests/test_hl1_seq_host.py compares it with the C compiler's)
 const LAYOUT_HL1_SEQ = [
     ("relmc_hl1_seq_year", 24, [("lole", 0), ("eue", 8), ("lolf", 16)]),

@@ -137,6 +137,23 @@ class Hl1SweepLevel(C.Structure):         # relmc_hl1_sweep_level (24 bytes)
 
 
 HL1_SWEEP_MAX_LEVELS = 16                 # RELMC_HL1_SWEEP_MAX_LEVELS
+HL1_MAX_STORAGE = 8                       # RELMC_HL1_MAX_STORAGE
+
+
+class Hl1Storage(C.Structure):            # relmc_hl1_storage (48 bytes)
+    _fields_ = [("charge_mw", C.c_double), ("discharge_mw", C.c_double), ("energy_mwh", C.c_double), ("eta_charge", C.c_double),
+                ("eta_discharge", C.c_double), ("soc0_mwh", C.c_double)]
+
+
+class Hl1StorageYear(C.Structure):        # relmc_hl1_storage_year
+    _fields_ = [("served_hours", C.c_double), ("discharged_mwh", C.c_double), ("charged_mwh", C.c_double)]
+
+
+class Hl1StorageAcc(C.Structure):         # relmc_hl1_storage_acc
+    _fields_ = [("years", C.c_int64), ("sum_lole", C.c_double), ("sum_eue", C.c_double), ("sum_lolf", C.c_double),
+                ("sum_lole2", C.c_double), ("sum_eue2", C.c_double), ("sum_lolf2", C.c_double),
+                ("sum_served", C.c_double), ("sum_discharged", C.c_double), ("sum_charged", C.c_double),
+                ("sum_served2", C.c_double), ("sum_discharged2", C.c_double), ("sum_charged2", C.c_double)]
 
 
 class Hl1EventAcc(C.Structure):           # relmc_hl1_event_acc

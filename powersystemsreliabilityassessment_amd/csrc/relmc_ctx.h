@@ -14,6 +14,7 @@
 //                        sequential chronology (relmc_hl1_seq), its loss events (relmc_hl1_seq_events, kernels in relmc_event_kernels.h), its
 //                        load sweep (relmc_hl1_seq_sweep, kernel in relmc_sweep_kernels.h) and
 //                        the record reduction and unit check of every HL1 chronology track
+//   relmc_storage.hip    energy storage with a state of charge on that chronology (relmc_hl1_seq_storage, kernel in relmc_storage_kernels.h)
 //   relmc_plan.hip       the HL1 planning model's Monte Carlo (relmc_hl1_plan)
 //   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area); its rows are summed by relmc_seq.hip's record reduction
 //   relmc_area_sweep.hip the sweep of that chronology over load, tie and fleet levels (relmc_hl1_area_sweep, kernel in relmc_area_sweep_kernels.h)
@@ -189,6 +190,8 @@ struct relmc_ctx {
     } hl1_events;
     // load sweep on that model (relmc_hl1_seq_sweep): grow-only per-level year records and reduction partials
     struct Hl1Sweep { DevBuf<double> years, part; } hl1_sweep;
+    // storage on that model (relmc_hl1_seq_storage): grow-only year records of both rows and reduction partials
+    struct Hl1Storage { DevBuf<double> years, part; } hl1_storage;
     // HL1 planning model (relmc_hl1_plan): its own fleet / maintenance / ELUs / load curve, grow-only per-year records, ELU energies,
     // hour loss counts and reduction partials
     bool has_hl1_plan = false;

@@ -2,8 +2,9 @@
 tests/test_hl1_edges_host.py (host models against the reference loops): unit counts around the 4-unit Philox blocks, the 32-bit mask words
 and the two lanes' slots, years shorter than a 64-lane group or straddling the 512-step window, transitions far shorter than a step or far
 longer than the horizon, zero capacities, loads equal to reachable capacity sums, 8 areas on the topologies where augmenting paths are
-long, 32 failing ties on years around the window length, and the planning model's 8 ELU slots in week 53.  Every value is computed
-here; nothing is read from disk."""
+long, 32 failing ties on years around the window length, and the planning model's 8 ELU slots in week 53.  tests/test_hl1_chrono_edges.py
+and its _host companion run the sweep, storage and event kernels on the same seq shapes (chrono_shapes), with the storages, sweep levels,
+withheld units and coverage conditions defined beside them.  Every value is computed here; nothing is read from disk."""
 from __future__ import annotations
 
 import math
@@ -125,6 +126,73 @@ def seq_fleet(ngen, nhours, seed=0):
 def seq_years(nhours, steps=1600):
     """Years per chain so that a chain runs about `steps` steps (several 512-step windows), at least 2."""
     return max(2, -(-steps // nhours))
+
+
+NHOURS_EDGES = (1, 24, 63, 64, 65, 511, 512, 513)                # year lengths of the seq edge tests: below, at and around a group and a window
+NGEN_EDGES = (1, 32, 33, 64, 65, 128)                            # unit counts of the seq edge tests: mask words and lane slots full and one over
+
+
+def chrono_shapes():
+    """The shapes of the seq edge tests as (label, fleet, seed, first_chain, n_chains, years, start), start 0 = all UP, 1 = stationary:
+    seq_fleet(8, nhours) on chains 40 .. 47 under both start rules, and seq_fleet(ngen, 100), 6 years, all UP from chain 0 and stationary
+    across first_chain = 2^32."""
+    out = []
+    for nhours in NHOURS_EDGES:
+        for start in (0, 1):
+            out.append(("h%d-%d" % (nhours, start), seq_fleet(8, nhours), 13, 40, 8, seq_years(nhours), start))
+    for ngen in NGEN_EDGES:
+        for start, first in ((0, 0), (1, (1 << 32) - 4)):
+            out.append(("g%d-%d" % (ngen, start), seq_fleet(ngen, 100), 3, first, 8, 6, start))
+    return out
+
+
+def edge_storages(cap):
+    """Three storages (charge_mw, discharge_mw, energy_mwh, eta_charge, eta_discharge, soc0_mwh) as fractions of the installed capacity:
+    a lossy one that starts full, a small one that starts empty and discharges without loss, and a large slow one (it charges at 5 % and
+    delivers 0.4 % of the fleet an hour) that starts half full and charges without loss."""
+    tot = float(np.sum(np.asarray(cap, dtype=np.float64)))
+    return [(0.02 * tot, 0.03 * tot, 0.08 * tot, 0.9, 0.95, 0.08 * tot),
+            (0.01 * tot, 0.015 * tot, 0.02 * tot, 0.85, 1.0, 0.0),
+            (0.05 * tot, 0.004 * tot, 0.5 * tot, 1.0, 0.8, 0.5 * (0.5 * tot))]
+
+
+def storage_coverage(label, cnt):
+    """The conditions on a shape's inputs under edge_storages, on hl1_storage_model's counters: some short step is lost although the
+    first storage delivers; on every year longer than an hour some step is long, some short step is served in full and some storage
+    charges.  nhours = 1 is a flat curve without a surplus hour, so the three surplus conditions do not apply to it."""
+    assert cnt["short"] > 0 and cnt["lost"] > 0 and cnt["discharge"][0] > 0, (label, cnt)
+    if not label.startswith("h1-"):
+        assert cnt["long"] > 0 and cnt["served"] > 0 and sum(cnt["charge"]) > 0, (label, cnt)
+
+
+def event_coverage(label, nhours, kinds):
+    """The conditions on a shape's events, on hl1_event_model.kinds' counts: with a year of 63 hours or more some event crosses a
+    64-step group edge, one a 512-step window edge and one a year boundary."""
+    assert kinds["n"] > 0, (label, kinds)
+    if nhours >= 63:
+        assert kinds["edge64"] >= 1 and kinds["edge512"] >= 1 and kinds["year"] >= 1, (label, kinds)
+
+
+NEVER_LOSES, ALWAYS_LOSES =(0.0, -1.0, 0), (0.0, 1e9, 0)        # L = -1 is below every capacity sum, L = 1e9 above every one
+_SPREAD = [(0.9, 0.0, 0), (1.12, -0.5, 0), (0.85, 2.75, 1), (0.95, 1.5, 0), (0.65, 0.0, 1), (1.03, -1.25, 0), (0.85, 4.0, 0), (1.2, 0.0, 0),
+           (0.9, 0.0, 1), (1.0, -3.5, 0), (1.16, 0.25, 0)]
+
+
+def edge_levels(n):
+    """n sweep levels (scale, shift, fleet), 1 <= n <= 16: the identity, a level on fleet 1 at the loaded curve, one that never loses,
+    one that always loses, a lowered level on fleet 1, then levels of both fleets spread between the extremes (scales 0.65 .. 1.2, dyadic
+    shifts of a few MW; the fleet-1 levels are lowered by different amounts, since two withheld units of eight weigh more than four of
+    128).  Every n >= 5 holds the first five; a shorter list is a prefix, so level j is the same level at every n."""
+    levels = [(1.0, 0.0, 0), (1.0, 0.0, 1), NEVER_LOSES, ALWAYS_LOSES, (0.75, 0.75, 1)] + _SPREAD
+    assert 1 <= n <= len(levels) == 16
+    return levels[:n]
+
+
+def edge_withheld(ngen):
+    """The withheld units of the fleet-1 levels: the first and the last unit of the first and of the last mask word the fleet has (at
+    128 units: both lane slots, words 0 and 3)."""
+    last = 32 * ((ngen - 1) // 32)
+    return sorted({0, min(31, ngen - 1), last, ngen - 1})
 
 
 # ---- relmc_hl1_area --------------------------------------------------------------------------------------------------------------

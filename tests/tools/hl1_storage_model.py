@@ -7,6 +7,10 @@ correctly rounded fp64 operation.  A storage is a tuple (charge_mw, discharge_mw
 Besides the year records the model counts how often each path of the step loop ran, so that a test can show its fixtures reach them,
 and how many 64-step groups of a chain are not quiet (a lane short, or a storage that can charge and is not full at the group's first
 step): the groups that take the device kernel's serial stage.
+
+literal_storage_chain restates the contract without any of that: the reference's hour loop for the units (hl1_seq_model.literal_chain's)
+with the storages inside it, sharing only the draws with storage_model.  tests/test_hl1_chrono_edges_host.py holds the two against each
+other, and both against lane_edge_pattern, a second pattern worked out by hand whose short steps sit at the device's lane and group edges.
 """
 import importlib.util
 import os
@@ -134,6 +138,124 @@ def hand_pattern():
     rec = np.array([[3.0, 29.0, 2.0, 3.0, 31.0, 32.0],
                     [5.0, 44.0, 1.0, 1.0, 16.0, 32.0]])
     return curve, storage, soc, deficit, rec
+
+
+def lane_edge_pattern():
+    """One 100 MW unit that never fails, a 130-hour year (two 64-step groups and two steps: the year's place in the device's groups moves
+    by two lanes a year) and one storage of 3 MW charge / 16 MW discharge / 32 MWh with efficiencies 1.0 (charge) and 0.5 (discharge),
+    started full: every number is dyadic, so every sum is exact in any order.  The load is 96 MW (a surplus of 4) except on the 0-based
+    hours 62, 63, 64 (needs 4, 16, 8) and 127, 128, 129 (needs 6, 12, 2).  Three years: 390 steps, so the chain's last group has six steps.
+
+    0-based steps of the short hours -> lane of their 64-step group (step mod 64):
+      year 1: 62, 63, 64 -> lanes 62, 63 | 0 (the run crosses a group edge);  127, 128, 129 -> lanes 63 | 0, 1; the year ends at lane 1
+      year 2: 192, 193, 194 -> lanes 0, 1, 2;  257, 258, 259 -> lanes 1, 2, 3
+      year 3: 322, 323, 324 -> lanes 2, 3, 4;  387, 388, 389 -> lanes 3, 4, 5 of the six-step last group; step 389 ends the chain
+    Every year (s = state of charge; a delivered MW costs 2 MWh):
+      hour 62   need 4:  avail min(16, 32 * .5) = 16, x 4,  s 32 - 8  = 24             served
+      hour 63   need 16: avail min(16, 12) = 12,      x 12, s 24 - 24 = 0, deficit 4   the storage runs empty inside the run: event 1
+      hour 64   need 8:  avail 0                                           deficit 8   still event 1
+      65 - 126  surplus 4: y = min(3, room, 4) = 3 for ten hours (s 30), then room 2: y 2 (s 32, exactly full), then y 0: charged 32
+      hour 127  need 6:  avail 16,                    x 6,  s 32 - 12 = 20             served
+      hour 128  need 12: avail min(16, 10) = 10,      x 10, s 20 - 20 = 0, deficit 2   event 2
+      hour 129  need 2:  avail 0                                           deficit 2   still event 2; the year ends empty
+      per year  lole 4, eue 4 + 8 + 2 + 2 = 16, lolf 2, served 2, discharged 4 + 12 + 6 + 10 = 32
+    Hours 0 - 61: full in year 1 (nothing charged: 32 in the year); empty in years 2 and 3, filled as in hours 65 - 126 (64 in the year).
+    -> (curve, storage, years, rec[3, 6])."""
+    curve = [96.0] * 130
+    for h, need in ((62, 4.0), (63, 16.0), (64, 8.0), (127, 6.0), (128, 12.0), (129, 2.0)):
+        curve[h] = 100.0 + need
+    storage = (3.0, 16.0, 32.0, 1.0, 0.5, 32.0)
+    rec = np.array([[4.0, 16.0, 2.0, 2.0, 32.0, 32.0],
+                    [4.0, 16.0, 2.0, 2.0, 32.0, 64.0],
+                    [4.0, 16.0, 2.0, 2.0, 32.0, 64.0]])
+    return curve, storage, 3, rec
+
+
+def literal_storage_chain(seed: int, chain: int, cap, mttf, mttr, load, years: int, start: int, storages, scale: float = 1.0,
+                          shift: float = 0.0, counters=None) -> np.ndarray:
+    """The contract of relmc_hl1_seq_storage (include/relmc.h) as one plain loop, in Python floats: hours outside, units and then
+    storages inside; no groups, lanes, bits or skipped steps.  The unit states are hl1_seq_model.literal_chain's hour loop (`ttf -= 1;
+    while ttf <= 0: toggle, ttf += duration`, the reference's), so the capacity side does not come from the interval form either; only
+    the draws (SEQ.chronology's U) are shared.  Nothing of storage_chain is used.  -> rec[years, 6] = per year lole, eue, lolf,
+    served_hours, discharged_mwh, charged_mwh, each summed over the year's hours in hour order.  counters: an optional dict that
+    receives how often the steps were short / long / served / lost and how often storage i delivered or took energy."""
+    K, H = len(cap), len(load)
+    _, _, U = SEQ.chronology(seed, [chain], mttf, mttr, start, years * H)
+    u, lnU = U[0].tolist(), np.log(U[0]).tolist()
+    mttf, mttr, cap, load = ([float(x) for x in v] for v in (mttf, mttr, cap, load))
+    scale, shift = float(scale), float(shift)
+    status, ttf, ev = [True] * K, [0.0] * K, [0] * K
+    for i in range(K):
+        if start == SEQ.STATIONARY:
+            status[i] = not (u[i][0] < mttr[i] / (mttf[i] + mttr[i]))
+            ev[i] = 1
+        ttf[i] = -(mttf[i] if status[i] else mttr[i]) * lnU[i][ev[i]]
+        ev[i] += 1
+    P = [dict(zip(("charge", "discharge", "energy", "eta_c", "eta_d"), (float(v) for v in s[:5]))) for s in storages]
+    soc = [float(s[5]) for s in storages]
+    cnt = counters if counters is not None else {}
+    for key in ("short", "long", "served", "lost"):
+        cnt.setdefault(key, 0)
+    cnt.setdefault("discharge", [0] * 8)
+    cnt.setdefault("charge", [0] * 8)
+    rec = np.zeros((years, 6))
+    was_loss = False
+    for y in range(years):
+        lole = eue = lolf = served = discharged = charged = 0.0
+        for h in range(H):
+            cap_avail = 0.0
+            for i in range(K):
+                ttf[i] -= 1.0
+                while ttf[i] <= 0:
+                    status[i] = not status[i]
+                    ttf[i] += -(mttf[i] if status[i] else mttr[i]) * lnU[i][ev[i]]
+                    ev[i] += 1
+                if status[i]:
+                    cap_avail += cap[i]
+            product = scale * load[h]
+            L = product + shift
+            loss = False
+            if cap_avail < L:
+                cnt["short"] += 1
+                need = L - cap_avail
+                delivered = 0.0
+                for i, p in enumerate(P):
+                    if not need > 0.0:
+                        break
+                    avail = min(p["discharge"], soc[i] * p["eta_d"])
+                    x = min(avail, need)
+                    soc[i] = max(0.0, soc[i] - x / p["eta_d"])
+                    need = need - x
+                    delivered = delivered + x
+                    cnt["discharge"][i] += x > 0.0
+                discharged += delivered
+                if need > 0.0:
+                    loss = True
+                    cnt["lost"] += 1
+                    lole += 1.0
+                    eue += need
+                    if not was_loss:
+                        lolf += 1.0
+                else:
+                    cnt["served"] += 1
+                    served += 1.0
+            elif cap_avail > L:
+                cnt["long"] += 1
+                surplus = cap_avail - L
+                taken = 0.0
+                for i, p in enumerate(P):
+                    if not surplus > 0.0:
+                        break
+                    room = (p["energy"] - soc[i]) / p["eta_c"]
+                    yv = min(min(p["charge"], room), surplus)
+                    soc[i] = min(p["energy"], soc[i] + yv * p["eta_c"])
+                    surplus = surplus - yv
+                    taken = taken + yv
+                    cnt["charge"][i] += yv > 0.0
+                charged += taken
+            was_loss = loss
+        rec[y] = (lole, eue, lolf, served, discharged, charged)
+    return rec
 
 
 def storage_model(seed: int, chains, cap, mttf, mttr, load, years: int, start: int, storages, scale: float = 1.0, shift: float = 0.0,

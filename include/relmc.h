@@ -482,6 +482,62 @@ int32_t relmc_hl1_seq_storage(relmc_ctx* ctx, uint64_t seed, uint64_t first_chai
                               relmc_hl1_storage_acc* acc, relmc_hl1_seq_year* years_host,
                               relmc_hl1_storage_year* storage_years_host);
 
+/* ---- HL1 sequential chronology with derated states: three-state Markov units (an extension beyond the reference) ---- */
+/* A large thermal unit that loses a feed pump or a mill runs at part load for days: the textbook third state (Billinton & Allan), with
+ * its own capacity and transition rates.  The reference's units, and every other HL1 track here, are two-state.
+ * States      0 = UP at capacity_mw, 1 = DERATED at derated_mw (0 <= derated_mw <= capacity_mw), 2 = DOWN at 0.
+ * Unit        a continuous-time Markov chain, given per state i by mean_h[i], the mean holding time in hours, and first_p[i], the
+ *             probability that the sojourn ends in the FIRST-LISTED destination:
+ *                 from UP: (DOWN, DERATED)      from DERATED: (UP, DOWN)      from DOWN: (UP, DERATED)
+ *             A two-state unit is mean_h = (mttf, any, mttr), first_p = (1, any, 1).  Means and branch probabilities, not a rate matrix,
+ *             are the ABI form: only so is the two-state case bitwise relmc_hl1_seq's (-mttf * ln U with the caller's own mttf).
+ * Chronology  relmc_hl1_seq's (steps n = 1 .. Y*H, state carried from year to year), extended.  With T_1 < T_2 < ... a unit's transition
+ *             times and T_0 = 0, the sojourn that starts at T_j covers steps ceil(T_j) .. ceil(T_j+1) - 1 (none when both ends round up to
+ *             the same step).  T_j+1 = T_j + (-mean_h[state] * ln U), the product and the sum each rounded (no FMA); duration draw e of
+ *             unit k is relmc_hl1_seq's draw e: (seed, chain, k | 0x40000000, e), the same stream and numbering.
+ * Branches    the destination of the transition that ends the sojourn timed by duration draw e is taken from draw e of a second stream,
+ *             (seed, chain, k | RELMC_HL1_MS_BRANCH_TAG, e), formed as the duration draws are: the first-listed destination iff
+ *             U < first_p[state].  With first_p exactly 1 or 0 the draw cannot matter (and is not generated).
+ * Start       RELMC_HL1_START_ALL_UP as relmc_hl1_seq.  RELMC_HL1_START_STATIONARY: draw 0 picks the state from the stationary law pi,
+ *             DOWN iff U < pi_2, else DERATED iff U < pi_2 + pi_1, else UP; durations from draw 1 on.  pi_i is proportional to
+ *             nu_i * mean_h[i] with nu the stationary vector of the embedded jump chain over the states reachable from UP,
+ *                 nu_0 = f_2 + f_1 (1 - f_2),  nu_1 = (1 - f_2) + f_2 (1 - f_0),  nu_2 = (1 - f_1) + f_1 f_0      (f = first_p),
+ *                 w_i = nu_i * mean_h[i],  pi_2 = w_2 / ((w_0 + w_1) + w_2),  pi_1 = w_1 / ((w_0 + w_1) + w_2);
+ *             a unit that never reaches DERATED has pi_1 = 0 and pi_2 = mean_h[2] / (mean_h[0] + mean_h[2]), relmc_hl1_seq_load's own
+ *             expression, and one that never reaches DOWN pi_2 = 0 and pi_1 = mean_h[1] / (mean_h[0] + mean_h[1]).
+ * Per step    cap_avail summed in ascending unit order: capacity_mw for UP, derated_mw for DERATED, 0.0 for DOWN; loss iff
+ *             cap_avail < load (strict); events, year attribution and the EUE summation order are relmc_hl1_seq's.  A year's second
+ *             record counts its (unit, step) pairs DERATED and DOWN.
+ * The pin     a model whose units all have first_p[0] == first_p[2] == 1 gives year records that are bitwise relmc_hl1_seq's on the
+ *             relmc_hl1_seq_load model (capacity_mw, mean_h[0], mean_h[2]), under both start rules. */
+#define RELMC_HL1_MS_MAX_HOURS 1073741824      /* 2^30: the longest load curve relmc_hl1_ms_load takes */
+#define RELMC_HL1_MS_BRANCH_TAG 0x50000000u   /* counter word 2 of a branch draw is k | this; 0x80000000, 0x40000000, 0x20000000 are the other streams' */
+typedef struct { double capacity_mw, derated_mw, mean_h[3], first_p[3]; } relmc_hl1_ms_unit;          /* 64 bytes */
+typedef struct { double derated_unit_h, down_unit_h; } relmc_hl1_ms_year;      /* unit-hours of one simulated year spent DERATED / DOWN, over the fleet */
+typedef struct {
+    int64_t years;                                                          /* simulated years summed */
+    double sum_lole, sum_eue, sum_lolf, sum_lole2, sum_eue2, sum_lolf2;
+    double sum_derated, sum_down, sum_derated2, sum_down2;
+} relmc_hl1_ms_acc;
+/* Fleet (ngen <= 128 units) and the hourly load curve of one year (nhours >= 1).  The model lives in a slot of its own: relmc_hl1_load,
+ * relmc_hl1_seq_load, relmc_hl1_plan_load and relmc_hl1_area_load do not disturb it, and it does not disturb them.
+ * RELMC_ERR_INVALID, with relmc_last_error naming the unit (and the state) or the hour, for: what the input rule of the four HL1 load
+ * calls refuses; a non-finite field; derated_mw outside [0, capacity_mw]; a first_p outside [0, 1] or a mean_h <= 0 of a state that can be
+ * reached from UP; a chain in which some state reachable from UP cannot return to UP (the stationary law is then not unique).  A state that
+ * cannot be reached from UP is ignored entirely: its fields need only be finite.  RELMC_ERR_UNSUPPORTED for more than 128 units or more than
+ * RELMC_HL1_MS_MAX_HOURS hours (the kernel counts a lane's unit-hours of a year in 32 bits).  A refused call changes nothing. */
+int32_t relmc_hl1_ms_load(relmc_ctx* ctx, int32_t ngen, const relmc_hl1_ms_unit* units, int32_t nhours, const double* load_mw);
+/* chains [first_chain, first_chain + n_chains), each years_per_chain consecutive years, of the model loaded by relmc_hl1_ms_load
+ * (RELMC_ERR_NO_CASE before that call); arguments are checked as relmc_hl1_seq checks them, a refused call changes nothing,
+ * n_chains == 0 zeroes the outputs.
+ *   years_host        optional [n_chains * years_per_chain], chain-major
+ *   state_years_host  optional [n_chains * years_per_chain], chain-major
+ * Results depend on (seed, chain, start, years_per_chain, data) only, not on how a chain range is split into calls; the sums of `acc`
+ * are taken in a fixed order, so a repeated call is bitwise identical.  Long chain ranges go in launches of at most ~4M year records
+ * counted over both record rows, as in relmc_hl1_seq_storage; relmc_last_kernel_ms covers every launch. */
+int32_t relmc_hl1_ms_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain, int32_t start,
+                         relmc_hl1_ms_acc* acc, relmc_hl1_seq_year* years_host, relmc_hl1_ms_year* state_years_host);
+
 /* ---- HL1 multi-area chronology with tie-line transfers (AdequacyAssessmentII.jl:73-250 solve_curtailment_fast / run_fast_sequential_simulation) ---- */
 /* The chronology is relmc_hl1_seq's, word for word: draws (seed, chain, k | 0x40000000, event) with k the GLOBAL unit index (units stored
  * area-major: area 0's units, then area 1's, ...), the same start rules, steps n = 1 .. Y*H with the state carried across years, no FMA.

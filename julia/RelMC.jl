@@ -599,6 +599,42 @@ function run_sequential_storage(eng::Engine, capacity::Vector{Float64}, mttf::Ve
             years=yrs, storage_years=sty)
 end
 
+"relmc_hl1_ms_unit (include/relmc.h, 64 bytes): a three-state unit, UP / DERATED / DOWN: capacities in MW, per state the mean holding time in hours and the probability of the first-listed destination (from UP: DOWN, DERATED; from DERATED: UP, DOWN; from DOWN: UP, DERATED)"
+struct Hl1MsUnit
+    capacity_mw::Cdouble; derated_mw::Cdouble; mean_h::NTuple{3,Cdouble}; first_p::NTuple{3,Cdouble}
+end
+"relmc_hl1_ms_year: unit-hours of one simulated year spent DERATED and DOWN, over the fleet"
+struct Hl1MsYear
+    derated_unit_h::Cdouble; down_unit_h::Cdouble
+end
+mutable struct Hl1MsAcc
+    years::Int64; sum_lole::Cdouble; sum_eue::Cdouble; sum_lolf::Cdouble; sum_lole2::Cdouble; sum_eue2::Cdouble; sum_lolf2::Cdouble
+    sum_derated::Cdouble; sum_down::Cdouble; sum_derated2::Cdouble; sum_down2::Cdouble
+    Hl1MsAcc() = new()
+end
+"A two-state unit as a three-state one: mttf / mttr verbatim as the means of UP and DOWN, DERATED never reached"
+two_state_unit(capacity::Real, mttf::Real, mttr::Real) =
+    Hl1MsUnit(Float64(capacity), 0.0, (Float64(mttf), 1.0, Float64(mttr)), (1.0, 1.0, 1.0))
+
+"""
+run_sequential_multistate (an extension beyond the reference): run_sequential_mc's chronology with units that have a derated state.
+Units whose first_p are (1, any, 1) are two-state, and a fleet of them gives run_sequential_mc's year records bit for bit.  Returns LOLE,
+EUE and LOLF, the unit-hours per year spent DERATED and DOWN, and the per-year records.
+"""
+function run_sequential_multistate(eng::Engine, units::Vector{Hl1MsUnit}, hourly_load::Vector{Float64}, years::Integer;
+                                   seed::Integer=1, chains::Integer=1, start::Symbol=:all_up)
+    (years >= 1 && chains >= 1 && years % chains == 0) || throw(ArgumentError("years must be a positive multiple of chains"))
+    check(ccall((:relmc_hl1_ms_load, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Hl1MsUnit}, Int32, Ptr{Cdouble}),
+                eng.h, length(units), units, length(hourly_load), hourly_load), eng.h, "relmc_hl1_ms_load")
+    acc = Hl1MsAcc()
+    yrs = Vector{Hl1SeqYear}(undef, years); sty = Vector{Hl1MsYear}(undef, years)
+    check(ccall((:relmc_hl1_ms_seq, LIB), Int32,
+                (Ptr{Cvoid}, UInt64, UInt64, Int64, Int32, Int32, Ref{Hl1MsAcc}, Ptr{Hl1SeqYear}, Ptr{Hl1MsYear}),
+                eng.h, seed, 0, chains, years ÷ chains, HL1_START[start], acc, yrs, sty), eng.h, "relmc_hl1_ms_seq")
+    return (lole_hours_yr=acc.sum_lole / years, eue_mwh_yr=acc.sum_eue / years, lolf_occ_yr=acc.sum_lolf / years,
+            derated_unit_h_yr=acc.sum_derated / years, down_unit_h_yr=acc.sum_down / years, years=yrs, state_years=sty)
+end
+
 # Layout of the HL1 sequential structs, kept apart from LAYOUT (tests/test_hl1_seq_host.py compares it with the C compiler's)
 const LAYOUT_HL1_SEQ = [
     ("relmc_hl1_seq_year", 24, [("lole", 0), ("eue", 8), ("lolf", 16)]),

@@ -156,6 +156,24 @@ class Hl1StorageAcc(C.Structure):         # relmc_hl1_storage_acc
                 ("sum_served2", C.c_double), ("sum_discharged2", C.c_double), ("sum_charged2", C.c_double)]
 
 
+HL1_MS_BRANCH_TAG = 0x50000000            # RELMC_HL1_MS_BRANCH_TAG
+HL1_MS_MAX_HOURS = 1 << 30                # RELMC_HL1_MS_MAX_HOURS
+
+
+class Hl1MsUnit(C.Structure):             # relmc_hl1_ms_unit (64 bytes)
+    _fields_ = [("capacity_mw", C.c_double), ("derated_mw", C.c_double), ("mean_h", C.c_double * 3), ("first_p", C.c_double * 3)]
+
+
+class Hl1MsYear(C.Structure):             # relmc_hl1_ms_year
+    _fields_ = [("derated_unit_h", C.c_double), ("down_unit_h", C.c_double)]
+
+
+class Hl1MsAcc(C.Structure):              # relmc_hl1_ms_acc
+    _fields_ = [("years", C.c_int64), ("sum_lole", C.c_double), ("sum_eue", C.c_double), ("sum_lolf", C.c_double),
+                ("sum_lole2", C.c_double), ("sum_eue2", C.c_double), ("sum_lolf2", C.c_double),
+                ("sum_derated", C.c_double), ("sum_down", C.c_double), ("sum_derated2", C.c_double), ("sum_down2", C.c_double)]
+
+
 class Hl1EventAcc(C.Structure):           # relmc_hl1_event_acc
     _fields_ = [("years", C.c_int64), ("events", C.c_int64), ("censored", C.c_int64), ("sum_dur", C.c_int64), ("sum_dur2", C.c_int64),
                 ("max_dur", C.c_int64), ("sum_energy", C.c_double), ("sum_energy2", C.c_double), ("max_energy", C.c_double),

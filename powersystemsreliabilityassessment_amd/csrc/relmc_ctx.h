@@ -15,6 +15,7 @@
 //                        load sweep (relmc_hl1_seq_sweep, kernel in relmc_sweep_kernels.h) and
 //                        the record reduction and unit check of every HL1 chronology track
 //   relmc_storage.hip    energy storage with a state of charge on that chronology (relmc_hl1_seq_storage, kernel in relmc_storage_kernels.h)
+//   relmc_multistate.hip that chronology with three-state units (relmc_hl1_ms_load, relmc_hl1_ms_seq, kernel in relmc_multistate_kernels.h)
 //   relmc_plan.hip       the HL1 planning model's Monte Carlo (relmc_hl1_plan)
 //   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area); its rows are summed by relmc_seq.hip's record reduction
 //   relmc_area_sweep.hip the sweep of that chronology over load, tie and fleet levels (relmc_hl1_area_sweep, kernel in relmc_area_sweep_kernels.h)
@@ -192,6 +193,10 @@ struct relmc_ctx {
     struct Hl1Sweep { DevBuf<double> years, part; } hl1_sweep;
     // storage on that model (relmc_hl1_seq_storage): grow-only year records of both rows and reduction partials
     struct Hl1Storage { DevBuf<double> years, part; } hl1_storage;
+    // HL1 sequential chronology with three-state units (relmc_hl1_ms_load / relmc_hl1_ms_seq): its own fleet / load curve, apart from every
+    // other HL1 model; grow-only year records of both rows and reduction partials
+    bool has_hl1_ms = false;
+    struct Hl1Ms { int ngen = 0, nhours = 0; DevBuf<relmc::Hl1MsCase> dcase; DevBuf<double> load, years, part; } hl1_ms;
     // HL1 planning model (relmc_hl1_plan): its own fleet / maintenance / ELUs / load curve, grow-only per-year records, ELU energies,
     // hour loss counts and reduction partials
     bool has_hl1_plan = false;

@@ -239,6 +239,16 @@ struct Hl1SeqCase {
     double q[NCOMPMAX];              // mttr / (mttf + mttr): RELMC_HL1_START_STATIONARY starts unit k DOWN iff draw 0 < q[k]
 };
 constexpr int HL1_SEQ_WINDOW = 512;  // hours per LDS window of relmc_hl1_seq_kernel (a wavefront's masks: WINDOW x 4 x u32 = 8 KB)
+// HL1 sequential chronology with three-state units (relmc_hl1_ms_seq): per unit the capacities of UP and DERATED, per state the mean
+// holding time and the probability of the first-listed destination, and the stationary start thresholds, as include/relmc.h's contract
+struct Hl1MsCase {
+    int32_t ngen, nhours;
+    double cap[NCOMPMAX][2];         // capacity_mw, derated_mw
+    double mean[3][NCOMPMAX], first_p[3][NCOMPMAX];
+    double thr_down[NCOMPMAX];       // pi_2: RELMC_HL1_START_STATIONARY starts unit k DOWN iff draw 0 < thr_down[k],
+    double thr_out[NCOMPMAX];        // pi_2 + pi_1: else DERATED iff draw 0 < thr_out[k], else UP
+};
+constexpr int HL1_MS_WINDOW = 256;   // hours per LDS window of relmc_hl1_ms_kernel (a wavefront's two planes: 2 x WINDOW x 4 x u32 = 8 KB)
 // Loss events of the HL1 sequential chronology (relmc_hl1_seq_events) in summary: one chain's, or one reduction slice's.  The integer
 // fields add exactly, the maxima combine by max.
 struct Hl1EventRec {

@@ -1,0 +1,401 @@
+"""Three-state units on the HL1 sequential chronology on the GPU (relmc_hl1_ms_load / relmc_hl1_ms_seq): the host model
+(tests/tools/hl1_multistate_model.py) on shapes at the kernel's edges, two-state fleets against relmc_hl1_seq bit for bit, the tie rule,
+split / chunk / repeat invariance, the exact expectations at 4.5 standard errors, every error code, and the Python layer."""
+import ctypes as C
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+from powersystemsreliabilityassessment_amd import _abi, hl1, hl1_multistate as ms
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_spec = importlib.util.spec_from_file_location("hl1_multistate_model", os.path.join(ROOT, "tests", "tools", "hl1_multistate_model.py"))
+MM = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(MM)
+SEQ = MM.SEQ
+
+dp = _abi.c_double_p
+ACC_FIELDS = [f for f, _ in _abi.Hl1MsAcc._fields_]
+WINDOW = 256                                           # HL1_MS_WINDOW
+MM_STATES = ("UP", "DERATED", "DOWN")
+
+
+def _tuples(units):
+    return [(u.capacity, u.derated_capacity, u.mean_h, u.first_p) for u in units]
+
+
+def _unit_array(units):
+    return (_abi.Hl1MsUnit * max(len(units), 1))(*[_abi.Hl1MsUnit(u[0], u[1], (C.c_double * 3)(*u[2]), (C.c_double * 3)(*u[3])) for u in units])
+
+
+def _ms_load(eng, units, load, h=None, ngen=None, nhours=None):
+    ld = np.ascontiguousarray(load, dtype=np.float64)
+    rc = eng.L.relmc_hl1_ms_load(h or eng._h, len(units) if ngen is None else ngen, _unit_array(units), ld.size if nhours is None else nhours,
+                                 ld.ctypes.data_as(dp))
+    if h is None:
+        eng._check(rc, "relmc_hl1_ms_load")
+        eng._hl1_ms_loaded = None                      # hl1_multistate's cache no longer describes the device
+    return rc
+
+
+def _ms(eng, seed, first, n, years, start, h=None):
+    """-> (acc, yr[n * years, 3], sy[n * years, 2], rc)"""
+    acc = _abi.Hl1MsAcc()
+    yr, sy = np.zeros((max(n * years, 0), 3)), np.zeros((max(n * years, 0), 2))
+    rc = eng.L.relmc_hl1_ms_seq(h or eng._h, seed, first, n, years, start, C.byref(acc), yr.ctypes.data_as(C.POINTER(_abi.Hl1SeqYear)),
+                                sy.ctypes.data_as(C.POINTER(_abi.Hl1MsYear)))
+    if h is None:
+        eng._check(rc, "relmc_hl1_ms_seq")
+    return acc, yr, sy, rc
+
+
+def _ms_sums(eng, seed, n, start):
+    """n one-year chains, the sums only (both record buffers are optional)"""
+    acc = _abi.Hl1MsAcc()
+    eng._check(eng.L.relmc_hl1_ms_seq(eng._h, seed, 0, n, 1, start, C.byref(acc), None, None), "relmc_hl1_ms_seq")
+    return acc
+
+
+def _seq_load(eng, cap, mttf, mttr, load):
+    arrs = [np.ascontiguousarray(x, dtype=np.float64) for x in (cap, mttf, mttr, load)]
+    eng._check(eng.L.relmc_hl1_seq_load(eng._h, arrs[0].size, *[a.ctypes.data_as(dp) for a in arrs[:3]], arrs[3].size, arrs[3].ctypes.data_as(dp)),
+               "relmc_hl1_seq_load")
+    eng._hl1_seq_loaded = None
+
+
+def _seq(eng, seed, first, n, years, start):
+    acc = _abi.Hl1SeqAcc()
+    yr = np.zeros((n * years, 3))
+    eng._check(eng.L.relmc_hl1_seq(eng._h, seed, first, n, years, start, C.byref(acc), yr.ctypes.data_as(C.POINTER(_abi.Hl1SeqYear))), "relmc_hl1_seq")
+    return acc, yr
+
+
+def _acc_tuple(a):
+    return tuple(getattr(a, f) for f in ACC_FIELDS)
+
+
+def _mean_se(acc, s, s2):
+    n = acc.years
+    m = s / n
+    return m, np.sqrt(max(s2 / n - m * m, 0.0) / n)
+
+
+def _rts24():
+    gens, load = hl1.rts24_generators(), hl1.rts24_load()
+    return (np.array([g.capacity for g in gens]), np.array([g.mttf for g in gens]), np.array([g.mttr for g in gens]), load.hourly_load)
+
+
+def _fleet(name):
+    if name == "six":
+        return MM.six_unit_fleet()
+    if name == "short":
+        return MM.short_fleet()
+    if name.startswith("rts24"):
+        return _tuples(ms.derated_rts24()), hl1.rts24_load().hourly_load
+    return MM.edge_fleet(int(name), WINDOW + 1 if name == "128" else 200)
+
+
+def _assert_model(eng, units, load, seed, first, n, years, start):
+    """Every per-year count equal, EUE to 1e-9 (relative: the device sums a year's deficits lane by lane and then by a butterfly, the
+    model in step order; at most ~1e4 terms of one sign, so the two orders differ by ~1e-12), acc against its own records."""
+    _ms_load(eng, units, load)
+    acc, yr, sy, _ = _ms(eng, seed, first, n, years, start)
+    rec = MM.interval_model(seed, range(first, first + n), units, load, years, start)
+    np.testing.assert_array_equal(yr[:, 0], rec[:, 0])
+    np.testing.assert_array_equal(yr[:, 2], rec[:, 2])
+    np.testing.assert_array_equal(sy[:, 0], rec[:, 3])
+    np.testing.assert_array_equal(sy[:, 1], rec[:, 4])
+    np.testing.assert_allclose(yr[:, 1], rec[:, 1], rtol=1e-9, atol=0.0)
+    assert acc.years == n * years
+    both = np.concatenate([yr, sy], axis=1)
+    for q, f in ((0, "sum_lole"), (1, "sum_eue"), (2, "sum_lolf"), (3, "sum_derated"), (4, "sum_down")):
+        assert getattr(acc, f) == pytest.approx(both[:, q].sum(), rel=1e-12), f
+        assert getattr(acc, f + "2") == pytest.approx((both[:, q] ** 2).sum(), rel=1e-12), f
+    return rec
+
+
+# fleet -> (first chain, chains, years): six: a 168-hour year, two years inside one window; 33 / 65: a derated unit at 31, 32 (the
+# mask-word edge) and 63, 64 (the slot edge); 128: every lane owns two units, non-integer capacities, a year one step longer than the
+# window (H = 257: no multiple of 64, the years straddle the windows); rts24x64 / rts24x1: derated_rts24(), 35 windows per year
+_MODEL_SHAPES = {"six": (0, 8, 3), "33": (3, 4, 2), "65": (0, 5, 2), "128": (1, 4, 3), "rts24x64": (0, 64, 3), "rts24x1": (9, 1, 40)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("start", [MM.ALL_UP, MM.STATIONARY])
+@pytest.mark.parametrize("fleet", list(_MODEL_SHAPES))
+def test_records_equal_the_host_model(engine, fleet, start):
+    units, load = _fleet(fleet)
+    first, n, years = _MODEL_SHAPES[fleet]
+    rec = _assert_model(engine, units, load, 7, first, n, years, start)
+    assert rec[:, 3].sum() > 0 and rec[:, 4].sum() > 0                 # the chains do see derated and down hours
+    assert rec[:, 0].sum() > 0 and rec[:, 2].sum() > 0                 # and loss hours
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("start", [MM.ALL_UP, MM.STATIONARY])
+def test_short_means_equal_the_host_model(engine, start):
+    """Means of a few hours and less: the fixture reaches, by the model's own count, sojourns that cover no step, DERATED -> DOWN ->
+    DERATED inside one 64-step group, and sojourns across a group edge, the window edge and a year boundary."""
+    units, load = _fleet("short")
+    n, years = 8, 3
+    reached = MM.path_counts(7, range(n), units, load, years, start)
+    assert all(reached[k] > 0 for k in ("zero", "der_down_der", "group", "window", "year")), reached
+    assert years * len(load) > 3 * WINDOW
+    rec = _assert_model(engine, units, load, 7, 0, n, years, start)
+    assert rec[:, 0].sum() > 0 and rec[:, 3].sum() > 0 and rec[:, 4].sum() > 0
+
+
+def _down_hours_of_the_two_state_model(seed, chains, mttf, mttr, H, years, start):
+    """(unit, step) pairs DOWN per year in tests/tools/hl1_seq_model.py's chronology"""
+    down0, T, _ = SEQ.chronology(seed, np.asarray(list(chains), dtype=np.uint64), mttf, mttr, start, years * H)
+    n = np.arange(1, years * H + 1, dtype=np.float64)
+    out = np.zeros((down0.shape[0], years))
+    for c in range(down0.shape[0]):
+        for k in range(down0.shape[1]):
+            down = down0[c, k] ^ (np.searchsorted(T[c, k], n, side="right") & 1).astype(bool)
+            out[c] += down.reshape(years, H).sum(1)
+    return out.reshape(-1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("start", [MM.ALL_UP, MM.STATIONARY])
+@pytest.mark.parametrize("fleet", ["rts24", "100"])
+def test_two_state_fleets_are_bitwise_the_sequential_kernel(engine, fleet, start):
+    """The pin: units with first_p (1, any, 1) give relmc_hl1_seq's year records byte for byte, from the same context and seed; the
+    model of relmc_hl1_seq_load gives the same records before and after; down_unit_h is the two-state host model's count."""
+    cap, mttf, mttr, load = _rts24() if fleet == "rts24" else SEQ.fleet100(1000)
+    _seq_load(engine, cap, mttf, mttr, load)
+    args = (11, 2, 5, 3, start)                        # chains 2 .. 6: an offset range, a count that is no multiple of 4
+    acc0, before = _seq(engine, *args)
+    assert before[:, 0].sum() > 0
+    units = [(float(c), 0.0, (float(f), -3.0 if k % 2 else 1e300, float(r)), (1.0, 7.5 if k % 2 else -1.0, 1.0))    # DERATED is never reached: any finite value
+             for k, (c, f, r) in enumerate(zip(cap, mttf, mttr))]
+    _ms_load(engine, units, load)
+    acc, yr, sy, _ = _ms(engine, *args)
+    assert yr.tobytes() == before.tobytes()
+    assert _acc_tuple(acc)[:7] == tuple(getattr(acc0, f) for f, _ in _abi.Hl1SeqAcc._fields_)
+    assert not sy[:, 0].any() and acc.sum_derated == 0.0
+    np.testing.assert_array_equal(sy[:, 1], _down_hours_of_the_two_state_model(11, range(2, 7), mttf, mttr, len(load), 3, start))
+    _, after = _seq(engine, *args)
+    assert after.tobytes() == before.tobytes()
+
+
+@pytest.mark.gpu
+def test_tie_rule_and_unreachable_state(engine):
+    """Unit 0 leaves UP within the first hour for DERATED (first_p[0] = 0) and stays; unit 1 stays UP.  Available capacity is 37.625 +
+    50.25 = 87.875 MW at every step: a load of exactly that is no loss, one ulp more is.  DOWN of unit 0 cannot be reached, so its
+    negative mean and its first_p of 7 are ignored."""
+    units = [(100.0, 37.625, (1e-3, 1e15, -5.0), (0.0, 1.0, 7.0)), (50.25, 50.25, (1e15, 1.0, 1.0), (1.0, 1.0, 1.0))]
+    edge = 87.875
+    load = [edge, np.nextafter(edge, 100.0), 80.0, edge, np.nextafter(edge, 0.0)]
+    _ms_load(engine, units, load)
+    acc, yr, sy, _ = _ms(engine, 3, 0, 6, 2, MM.ALL_UP)
+    np.testing.assert_array_equal(yr, np.tile([1.0, load[1] - edge, 1.0], (12, 1)))
+    np.testing.assert_array_equal(sy, np.tile([5.0, 0.0], (12, 1)))
+    assert (acc.years, acc.sum_lole, acc.sum_derated, acc.sum_down) == (12, 12.0, 60.0, 0.0)
+
+
+@pytest.mark.gpu
+def test_split_and_repeat(engine):
+    units, load = _fleet("128")
+    _ms_load(engine, units, load)
+    args = (9, 3, 11, 3, MM.STATIONARY)
+    acc, yr, sy, _ = _ms(engine, *args)
+    acc2, yr2, sy2, _ = _ms(engine, *args)
+    assert yr.tobytes() == yr2.tobytes() and sy.tobytes() == sy2.tobytes() and _acc_tuple(acc) == _acc_tuple(acc2)
+    a, ya, sa, _ = _ms(engine, 9, 3, 6, 3, MM.STATIONARY)
+    b, yb, sb, _ = _ms(engine, 9, 9, 5, 3, MM.STATIONARY)
+    assert np.concatenate([ya, yb]).tobytes() == yr.tobytes() and np.concatenate([sa, sb]).tobytes() == sy.tobytes()
+    assert a.years + b.years == acc.years == 33
+    for f in ("sum_lole", "sum_lolf", "sum_derated", "sum_down", "sum_lole2", "sum_lolf2", "sum_derated2", "sum_down2"):
+        assert getattr(a, f) + getattr(b, f) == getattr(acc, f), f
+    assert yr[:, 0].sum() > 0 and sy[:, 0].sum() > 0 and sy[:, 1].sum() > 0
+
+
+@pytest.mark.gpu
+def test_two_launches(engine):
+    """2100 chains x 1000 years of 24 hours: a launch holds 2^22 / (1000 * 2) = 2097 chains, so the second has three and the second
+    record row starts elsewhere in it.  Both rows against two calls split at the cut, bitwise; the four chains around the cut against
+    the model."""
+    units, load = MM.six_unit_fleet()
+    load = load[:24]
+    _ms_load(engine, units, load)
+    N, Y = 2100, 1000
+    per = (1 << 22) // (Y * 2)
+    assert per == 2097 and per < N < 2 * per
+    acc, yr, sy, _ = _ms(engine, 8, 0, N, Y, MM.STATIONARY)
+    acc1, yr1, sy1, _ = _ms(engine, 8, 0, per, Y, MM.STATIONARY)
+    acc2, yr2, sy2, _ = _ms(engine, 8, per, N - per, Y, MM.STATIONARY)
+    assert np.array_equal(yr[:per * Y], yr1) and np.array_equal(yr[per * Y:], yr2)
+    assert np.array_equal(sy[:per * Y], sy1) and np.array_equal(sy[per * Y:], sy2)
+    assert sy2[:, 0].sum() > 0 and sy2[:, 1].sum() > 0 and yr2[:, 0].sum() > 0
+    assert acc.years == N * Y
+    for f in ("sum_lole", "sum_lolf", "sum_derated", "sum_down"):
+        assert getattr(acc1, f) + getattr(acc2, f) == getattr(acc, f), f
+    w0, w1 = per - 2, per + 2
+    rec = MM.interval_model(8, range(w0, w1), units, load, Y, MM.STATIONARY)
+    got = np.concatenate([yr[w0 * Y:w1 * Y], sy[w0 * Y:w1 * Y]], axis=1)
+    np.testing.assert_array_equal(got[:, [0, 2, 3, 4]], rec[:, [0, 2, 3, 4]])
+    np.testing.assert_allclose(got[:, 1], rec[:, 1], rtol=1e-9, atol=0.0)
+
+
+@pytest.mark.gpu
+def test_derated_rts24_against_the_exact_answers(engine):
+    """2e5 one-year chains, stationary start: LOLE and EUE = the three-term COPT's (run_analytical_multistate, step 1 MW), the derated and
+    down unit-hours per year = H * the sum of the units' pi_1 and pi_2, each within 4.5 standard errors.  All-UP first years lie below
+    the stationary values: the down unit-hours by far more than their standard error, the LOLE by its sign."""
+    fleet, load = ms.derated_rts24(), hl1.rts24_load()
+    _ms_load(engine, _tuples(fleet), load.hourly_load)
+    n, H = 200000, load.hourly_load.size
+    ref = ms.run_analytical_multistate(fleet, load, step_size=1.0)
+    pi = np.array([ms.stationary(u) for u in fleet])
+    acc = _ms_sums(engine, 21, n, MM.STATIONARY)
+    for s, s2, want in ((acc.sum_lole, acc.sum_lole2, ref.lole_hours_yr), (acc.sum_eue, acc.sum_eue2, ref.eue_mwh_yr),
+                        (acc.sum_derated, acc.sum_derated2, H * pi[:, 1].sum()), (acc.sum_down, acc.sum_down2, H * pi[:, 2].sum())):
+        m, se = _mean_se(acc, s, s2)
+        print(f"stationary: {m:.6g} against {want:.6g}, standard error {se:.3g}")
+        assert abs(m - want) < 4.5 * se, (m, want, se)
+    up = _ms_sums(engine, 22, n, MM.ALL_UP)
+    ml, _ = _mean_se(up, up.sum_lole, up.sum_lole2)
+    md, sd = _mean_se(up, up.sum_down, up.sum_down2)
+    print(f"all UP: LOLE {ml:.6g} against {ref.lole_hours_yr:.6g}; down unit-hours {md:.6g} (se {sd:.3g}) against {H * pi[:, 2].sum():.6g}")
+    assert ml < ref.lole_hours_yr and md + 4.5 * sd < H * pi[:, 2].sum()
+
+
+@pytest.mark.gpu
+def test_small_fleet_frequency_against_enumeration(engine):
+    """Four three-state units: stationary LOLE, EUE and LOLF of 2e5 one-year chains against the enumeration of the 81 joint states."""
+    units, load = MM.lolf_fleet()
+    _ms_load(engine, units, load)
+    acc = _ms_sums(engine, 4, 200000, MM.STATIONARY)
+    el, ee, ef = MM.small_fleet_stationary(units, load)
+    for s, s2, e in ((acc.sum_lole, acc.sum_lole2, el), (acc.sum_eue, acc.sum_eue2, ee), (acc.sum_lolf, acc.sum_lolf2, ef)):
+        m, se = _mean_se(acc, s, s2)
+        print(f"{m:.6g} against {e:.6g}, standard error {se:.3g}")
+        assert abs(m - e) < 4.5 * se, (m, e, se)
+
+
+@pytest.mark.gpu
+def test_error_codes(engine):
+    L = engine.L
+    h = C.c_void_p()
+    assert L.relmc_ctx_create(0, C.byref(h)) == 0
+    try:
+        units, load = MM.six_unit_fleet()
+        err = lambda: L.relmc_last_error(h).decode()
+        run = lambda n=4, years=2, start=0: _ms(engine, 1, 0, n, years, start, h=h)
+        assert run()[3] == -5 and "relmc_hl1_ms_load" in err()                           # RELMC_ERR_NO_CASE
+        assert _ms_load(engine, units, load, h=h) == 0
+        good = run()
+        assert good[3] == 0 and good[0].years == 8 and good[0].sum_down > 0
+        nan, inf = float("nan"), float("inf")
+
+        def changed(k, **kw):
+            u = dict(zip(("cap", "der", "mean", "fp"), units[k]))
+            for name, v in kw.items():
+                if name in ("mean", "fp"):
+                    x = list(u[name]); x[v[0]] = v[1]; u[name] = tuple(x)
+                else:
+                    u[name] = v
+            out = list(units); out[k] = (u["cap"], u["der"], u["mean"], u["fp"])
+            return out
+
+        refused = lambda us, **kw: _ms_load(engine, us, load, h=h, **kw)
+        for v in (nan, inf, -inf):                                                       # every field, non-finite (unit 3 is three-state)
+            assert refused(changed(3, cap=v)) == -1 and "unit 3" in err() and "capacity" in err(), err()
+            assert refused(changed(3, der=v)) == -1 and "unit 3" in err() and "derated_mw" in err(), err()
+            for s in range(3):
+                assert refused(changed(3, mean=(s, v))) == -1 and "unit 3" in err() and MM_STATES[s] in err(), err()
+                assert refused(changed(3, fp=(s, v))) == -1 and "unit 3" in err() and MM_STATES[s] in err(), err()
+            assert refused(changed(1, mean=(1, v))) == -1 and "unit 1" in err()          # an unreachable state's fields must still be finite
+        assert refused(changed(3, der=-2.0 ** -60)) == -1 and "derated_mw" in err()      # derated_mw outside [0, capacity_mw]
+        assert refused(changed(3, der=np.nextafter(units[3][0], 1e9))) == -1 and "derated_mw" in err()
+        assert refused(changed(3, der=0.0)) == 0 and refused(changed(3, der=units[3][0])) == 0      # the edges are inside
+        for s in range(3):
+            for v in (-2.0 ** -60, 1.0 + 2.0 ** -52):                                    # a first_p outside [0, 1] of a reachable state
+                assert refused(changed(3, fp=(s, v))) == -1 and "first_p" in err() and MM_STATES[s] in err() and "unit 3" in err(), err()
+            for v in (0.0, -1.0):                                                        # a reachable state that is left at once or never entered properly
+                assert refused(changed(3, mean=(s, v))) == -1 and "mean_h" in err() and MM_STATES[s] in err() and "unit 3" in err(), err()
+        assert refused(changed(1, mean=(0, 0.0))) == -1 and "UP" in err()                # UP is always reachable
+        assert refused(changed(1, mean=(1, -4.0), fp=(1, 9.0))) == 0                     # DERATED of a two-state unit is not: anything finite
+        assert refused(changed(3, fp=(1, 0.0), mean=(2, 5.0))) == 0                      # DERATED -> DOWN -> (UP or DERATED): still returns
+        both_stuck = changed(3, fp=(1, 0.0))
+        both_stuck[3] = (both_stuck[3][0], both_stuck[3][1], both_stuck[3][2], (both_stuck[3][3][0], 0.0, 0.0))
+        assert refused(both_stuck) == -1 and "cannot return to UP" in err() and "unit 3" in err(), err()      # DERATED <-> DOWN for ever
+        bad_load = np.array(load); bad_load[17] = nan
+        assert _ms_load(engine, units, bad_load, h=h) == -1 and "hour 17" in err()
+        assert refused(units, ngen=0) == -1 and refused(units, nhours=0) == -1
+        ld = np.ascontiguousarray(load)
+        assert L.relmc_hl1_ms_load(h, 6, None, ld.size, ld.ctypes.data_as(dp)) == -1 and L.relmc_hl1_ms_load(h, 6, _unit_array(units), ld.size, None) == -1
+        assert L.relmc_hl1_ms_load(None, 6, _unit_array(units), ld.size, ld.ctypes.data_as(dp)) == -1
+        many = [units[k % 6] for k in range(129)]
+        assert _ms_load(engine, many, load, h=h) == -4 and "128" in err()                # RELMC_ERR_UNSUPPORTED
+        assert refused(units, nhours=(1 << 30) + 1) == -4 and "2^30" in err()            # refused before the load curve is read
+        assert _ms_load(engine, many[:128], load, h=h) == 0 and _ms_load(engine, units, load, h=h) == 0
+        # the refused load calls left the model alone; the accepted ones above put it back
+        again = run()
+        assert again[1].tobytes() == good[1].tobytes() and again[2].tobytes() == good[2].tobytes()
+        assert refused(changed(3, cap=nan)) == -1
+        again = run()
+        assert again[3] == 0 and again[1].tobytes() == good[1].tobytes() and again[2].tobytes() == good[2].tobytes()
+        # relmc_hl1_ms_seq: what relmc_hl1_seq refuses
+        assert run(start=2)[3] == -1 and run(start=-1)[3] == -1 and run(years=0)[3] == -1 and run(n=-1)[3] == -1
+        acc = _abi.Hl1MsAcc()
+        assert L.relmc_hl1_ms_seq(None, 1, 0, 4, 1, 0, C.byref(acc), None, None) == -1
+        assert L.relmc_hl1_ms_seq(h, 1, 0, 4, 1, 0, None, None, None) == -1
+        assert L.relmc_hl1_ms_seq(h, 1, 0, 4, 1, 0, C.byref(acc), None, None) == 0 and acc.years == 4      # both records optional
+        # a refused call changes nothing
+        acc.years, acc.sum_lole, acc.sum_down2 = -7, 3.5, 2.5
+        yr, sy = np.full((8, 3), -7.0), np.full((8, 2), -7.0)
+        assert L.relmc_hl1_ms_seq(h, 1, 0, 4, 2, 5, C.byref(acc), yr.ctypes.data_as(C.POINTER(_abi.Hl1SeqYear)),
+                                  sy.ctypes.data_as(C.POINTER(_abi.Hl1MsYear))) == -1
+        assert (acc.years, acc.sum_lole, acc.sum_down2) == (-7, 3.5, 2.5) and np.all(yr == -7.0) and np.all(sy == -7.0)
+        # n_chains == 0 zeroes the outputs
+        assert L.relmc_hl1_ms_seq(h, 1, 0, 0, 2, 0, C.byref(acc), None, None) == 0
+        assert _acc_tuple(acc) == (0,) + (0.0,) * 10
+    finally:
+        L.relmc_ctx_destroy(h)
+
+
+@pytest.mark.gpu
+def test_the_other_hl1_models_are_left_alone(engine):
+    """relmc_hl1_ms_load lives in a slot of its own: relmc_hl1_seq's records are the same before and after it, and its own are the same
+    before and after relmc_hl1_seq_load with another fleet."""
+    cap, mttf, mttr, load = SEQ.small_fleet()
+    _seq_load(engine, cap, mttf, mttr, load)
+    _, before = _seq(engine, 5, 0, 6, 2, MM.STATIONARY)
+    units, ld = _fleet("33")
+    _ms_load(engine, units, ld)
+    _, yr, sy, _ = _ms(engine, 5, 0, 6, 2, MM.STATIONARY)
+    _, after = _seq(engine, 5, 0, 6, 2, MM.STATIONARY)
+    assert after.tobytes() == before.tobytes()
+    _seq_load(engine, *SEQ.fleet100(300))
+    _, yr2, sy2, _ = _ms(engine, 5, 0, 6, 2, MM.STATIONARY)
+    assert yr2.tobytes() == yr.tobytes() and sy2.tobytes() == sy.tobytes() and sy[:, 0].sum() > 0
+
+
+@pytest.mark.gpu
+def test_python_surface(engine):
+    gens, load = hl1.rts24_generators(), hl1.rts24_load()
+    kw = dict(seed=2, chains=2000, start="stationary", engine=engine)
+    base = hl1.run_sequential_mc(gens, load, 2000, **kw)
+    two = ms.run_sequential_multistate([ms.MultiStateUnit.from_generator(g) for g in gens], load, 2000, **kw)
+    for f in ("year_lole", "year_eue", "year_lolf"):
+        assert getattr(two, f).tobytes() == getattr(base, f).tobytes(), f
+    assert (two.lole_hours_yr, two.eue_mwh_yr, two.lolf_occ_yr) == (base.lole_hours_yr, base.eue_mwh_yr, base.lolf_occ_yr)
+    assert two.derated_unit_h_yr == 0.0 and not two.year_derated.any() and two.down_unit_h_yr == pytest.approx(two.year_down.mean(), rel=1e-12) and two.down_unit_h_yr > 0
+    fleet = ms.derated_rts24()
+    res = ms.run_sequential_multistate(fleet, load, 2000, **kw)
+    again = ms.run_sequential_multistate(fleet, load, 2000, **kw)                          # the model is already on the device
+    assert res.year_eue.tobytes() == again.year_eue.tobytes() and res.year_derated.shape == (2000,) and len(res.convergence_history) == 200
+    assert res.derated_unit_h_yr == pytest.approx(res.year_derated.mean(), rel=1e-12) and res.derated_unit_h_yr > 0 and len(res.units) == 32
+    ref = ms.run_analytical_multistate(fleet, load, 1.0)
+    assert abs(res.lole_hours_yr - ref.lole_hours_yr) < 4.5 * res.year_lole.std(ddof=1) / np.sqrt(2000)
+    txt = hl1.compare_results([ref, base, res])
+    assert "Analytical 3-state" in txt and "Sequential MC 3-state" in txt and ("%.4f" % res.lole_hours_yr) in txt
+    one = ms.run_sequential_multistate(fleet, load, 30, seed=2, engine=engine)             # the reference's shape: one chain, all UP
+    m = MM.interval_model(2, [0], _tuples(fleet), load.hourly_load, 30, MM.ALL_UP)
+    np.testing.assert_array_equal(one.year_lole, m[:, 0])
+    np.testing.assert_array_equal(one.year_down, m[:, 4])

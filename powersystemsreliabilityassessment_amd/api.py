@@ -410,8 +410,8 @@ class Engine:
         return buf.value.decode()
 
     def debug_set(self, key: str, value: bool = True):
-        """Diagnosis switch of the context (tests): no_retry, retry_dense_first, nsq_no_stretch, db_no_probe, dynamic_shape, static_tail
-        (relmc_debug_set)."""
+        """Diagnosis switch of the context (tests): no_retry, retry_dense_first, nsq_no_stretch, db_no_probe, dynamic_shape, static_tail,
+        norms_always (relmc_debug_set)."""
         self._check(self.L.relmc_debug_set(self._h, key.encode(), int(bool(value))), "relmc_debug_set")
 
     def shape_path(self) -> str:

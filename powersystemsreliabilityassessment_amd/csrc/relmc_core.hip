@@ -70,6 +70,7 @@ int launch_eval_t(relmc_ctx* ctx, EvalArgs& a, int* rows_out, hipEvent_t ev_star
     a.prio_mode = blocks != ctx->num_cu * ctx->blocks_per_cu ? 0u : (ctx->blocks_per_cu == 2 ? 1u : (ctx->blocks_per_cu == 1 && TL::WPB >= 8 ? 2u : 0u));
     a.stash_off = alt ? ctx->alt_stash_off[alt - 1] : ctx->stash_off;
     a.case_bytes = (uint32_t)offsetof(DevCaseT<TL>, task);
+    a.norms_always = ctx->sw.norms_always ? 1u : 0u;
 #if defined(RELMC_PHASE_TIMING) || defined(RELMC_TRACE)
     HIP_TRY(ctx, ctx->dtiming.grow(8 * 65536));
     a.timing = ctx->dtiming.get(); ctx->timing_waves = blocks * TL::WPB;

@@ -46,6 +46,7 @@ struct relmc_switches {
     bool db_no_probe = false;        // state database: every batch through the dedupe, no per-sample probe
     bool dynamic_shape = false;      // fused path: the run-time-shape evaluation kernel even when the case has the compiled-in shape
     bool static_tail = false;        // fused path on the 16-lane tile: no dynamic tail (T = 0), every group run by the wavefront that owns it
+    bool norms_always = false;       // evaluation kernels: the second-stage termination norms on every trip, not only on the trips that can end
 };
 
 namespace relmc_host {

@@ -74,6 +74,19 @@ int32_t relmc_debug_phase_cycles(relmc_ctx* ctx, unsigned long long* out8)
     return RELMC_OK;
 }
 
+// profiling hook (only meaningful in -DRELMC_PHASE_TIMING builds): the last launch's trips of the interior-point loop, summed over its wavefronts,
+// by the form of their evaluation: out2[0] without the second-stage termination norms, out2[1] with them
+int32_t relmc_debug_norm_trips(relmc_ctx* ctx, unsigned long long* out2)
+{
+    if (!ctx || !out2) return RELMC_ERR_INVALID;
+    out2[0] = out2[1] = 0;
+    if (!ctx->dtiming.get() || ctx->timing_waves <= 0) return RELMC_OK;
+    std::vector<unsigned long long> h((size_t)ctx->timing_waves * 2);
+    HIP_TRY(ctx, hipMemcpy(h.data(), ctx->dtiming.get() + (size_t)ctx->timing_waves * 8, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int w = 0; w < ctx->timing_waves; ++w) for (int k = 0; k < 2; ++k) out2[k] += h[(size_t)w * 2 + k];
+    return RELMC_OK;
+}
+
 // debug hook (only meaningful in -DRELMC_TRACE builds): per-iteration termination quantities of the first scenario
 // of the last launch, 8 doubles per iteration {feascond, gradcond, compcond, costcond, alpha_p, alpha_d, gamma, f}
 int32_t relmc_debug_trace(relmc_ctx* ctx, double* out, int32_t n_doubles)
@@ -143,10 +156,12 @@ int32_t relmc_debug_tail_groups(const relmc_ctx* ctx, int64_t* launches_out, int
     return ctx->last_tail_groups;
 }
 
-// diagnosis switches of the context (tests): "no_retry", "retry_dense_first", "nsq_no_stretch", "db_no_probe", "dynamic_shape", "static_tail";
-// value 0 / 1.  static_tail may change between launches: the fused path then runs without the dynamic tail (tests/test_tail_paths.py).
+// diagnosis switches of the context (tests): "no_retry", "retry_dense_first", "nsq_no_stretch", "db_no_probe", "dynamic_shape", "static_tail",
+// "norms_always"; value 0 / 1.  static_tail may change between launches: the fused path then runs without the dynamic tail (tests/test_tail_paths.py).
 // no_retry must be set before relmc_case_load (the order calibration and the list arming must agree).  dynamic_shape may change between
 // launches: the fused path then runs the run-time-shape kernel on a case that has the compiled-in shape (tests/test_shape_paths.py).
+// norms_always may change between launches: every evaluation kernel then accumulates the second-stage termination norms on every trip of the
+// interior-point loop instead of only on the trips that can end; same results bit for bit (tests/test_norm_paths.py).
 int32_t relmc_debug_set(relmc_ctx* ctx, const char* key, int32_t value)
 {
     if (!ctx || !key) return RELMC_ERR_INVALID;
@@ -157,6 +172,7 @@ int32_t relmc_debug_set(relmc_ctx* ctx, const char* key, int32_t value)
     else if (!std::strcmp(key, "db_no_probe")) ctx->sw.db_no_probe = v;
     else if (!std::strcmp(key, "dynamic_shape")) ctx->sw.dynamic_shape = v;
     else if (!std::strcmp(key, "static_tail")) ctx->sw.static_tail = v;
+    else if (!std::strcmp(key, "norms_always")) ctx->sw.norms_always = v;
     else return fail(ctx, RELMC_ERR_INVALID, std::string("relmc_debug_set: unknown switch ") + key);
     return RELMC_OK;
 }

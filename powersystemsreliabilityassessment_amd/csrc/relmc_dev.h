@@ -187,6 +187,7 @@ struct EvalArgs {
     // pointers share their words with MODE 6's, which no MODE 0 launch uses: the argument block keeps its size and every field its offset.
     union { double* dense; void* tail_rec; };
     union { uint64_t dense_stride; uint32_t* tail_count; };
+    uint32_t norms_always;          // diagnosis: every trip of the interior-point loop accumulates the second-stage termination norms (kNormSplitMask)
 };
 
 // Zero-curtailment certificate (relmc_screen.hip; SURVEY 8f rank 4, mc_simulation.m:57-59, 65): tables built by relmc_case_load on the host, resident in

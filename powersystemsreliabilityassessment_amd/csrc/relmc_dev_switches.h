@@ -10,6 +10,7 @@ inline void relmc_dev_switches_context(relmc_switches& sw)
 {
     sw.no_retry = std::getenv("RELMC_NO_RETRY") != nullptr; sw.retry_dense_first = std::getenv("RELMC_RETRY_DENSE_FIRST") != nullptr;
     sw.nsq_no_stretch = std::getenv("RELMC_NSQ_NO_STRETCH") != nullptr; sw.db_no_probe = std::getenv("RELMC_DB_NO_PROBE") != nullptr;
+    sw.norms_always = std::getenv("RELMC_NORMS_ALWAYS") != nullptr;
 }
 
 inline void relmc_dev_switches_schedule(relmc_host::SymOpts& so)

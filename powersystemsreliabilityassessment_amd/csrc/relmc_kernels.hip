@@ -59,17 +59,31 @@ constexpr int kPfMaskWide = 0xc6;    // 64-lane tile: sites 1, 2, 6, 7 (-2.9 %)
 // test) on the same device image.  Measurements and the choice per tile and mode: profiles/pass_shadow/README.md.
 constexpr int kShadowMask = 0xff;       // 16-lane tile
 constexpr int kShadowMaskWide = 0xff;   // 64-lane tile
+// Termination norms only on trips that can end (bit m = MODE m).  The first stage of the convergence test -- complementarity and cost change --
+// reads nothing the evaluation computes, so it is formed at the end of the update, for the next trip, with |x|inf and the NaN flag of x
+// accumulated where x is written.  A trip then evaluates and gathers in one of two forms, chosen per wavefront: with the four second-stage
+// norms (max |g, h|, max z, max |Lx|, max |lam, mu|) when the first stage holds for some iterating row, without them otherwise (~91 % of the
+// trips on RTS-24: the first stage passes on the converging trip only).  Same arithmetic into the KKT blocks, same verdicts.  Instantiations
+// outside the masks accumulate all five norms on every trip and test both stages behind the gathers.  EvalArgs::norms_always (diagnosis)
+// and RELMC_TRACE builds take the norms form on every trip.  Measurements: profiles/norm_paths/README.md.
+constexpr int kNormSplitMask = 0xff;       // 16-lane tile
+constexpr int kNormSplitMaskWide = 0;      // 64-lane tile: off (RTS-96 fused path +0.27 % with it, 1.1 x the run-to-run spread, and 16-60 B/lane more scratch in every mode)
 // the one compare a pass spends on its descriptor: field 0 == field 3 (updates, back substitution), fields 2, 3 non-zero (inversion)
 #define PASS_IDLE(d) (((d).x & 0xffffu) == ((d).y >> 16))
 #define PASS_IDLE_INV(d) ((d).y != 0u)
 // optional per-phase cycle accounting (profiling builds only: -DRELMC_PHASE_TIMING)
 #ifdef RELMC_PHASE_TIMING
-#define PT_DECL unsigned long long pt_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long pt0_ = __builtin_readcyclecounter();
+#define PT_DECL unsigned long long pt_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ptn_[2] = {0, 0}; unsigned long long pt0_ = __builtin_readcyclecounter();
 #define PT_MARK(k) { const unsigned long long n_ = __builtin_readcyclecounter(); pt_[k] += n_ - pt0_; pt0_ = n_; }
-#define PT_FLUSH if (a.timing && lane == 0) { for (int k = 0; k < 8; ++k) a.timing[((size_t)blockIdx.x * WPB + (tid >> 6)) * 8 + k] = pt_[k]; }
+// ... and the wavefront's trips of the interior-point loop by the form of their evaluation (0 without the second-stage norms, 1 with them):
+// two words per wavefront behind the [waves][8] cycle records
+#define PT_TRIP(k) ptn_[k] += 1;
+#define PT_FLUSH if (a.timing && lane == 0) { for (int k = 0; k < 8; ++k) a.timing[((size_t)blockIdx.x * WPB + (tid >> 6)) * 8 + k] = pt_[k]; \
+                                              for (int k = 0; k < 2; ++k) a.timing[(size_t)gridDim.x * WPB * 8 + ((size_t)blockIdx.x * WPB + (tid >> 6)) * 2 + k] = ptn_[k]; }
 #else
 #define PT_DECL
 #define PT_MARK(k)
+#define PT_TRIP(k)
 #define PT_FLUSH
 #endif
 // -DRELMC_PHASE_TIMING -DRELMC_PT_INIT: the per-scenario-group setup split instead (0 window sampling, 1 state from the window / masks,
@@ -109,6 +123,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
 #define PAIRSITE(k) (((PAIR_MASK >> (k)) & 1) != 0)
     constexpr int PF_MASK = TL::RW == 16 ? kPfMask : kPfMaskWide;                 // which LDS round trips are taken off the critical path (PFSITE)
     constexpr bool SHADOW = (((TL::RW == 16 ? kShadowMask : kShadowMaskWide) >> MODE) & 1) != 0;   // solver passes: all lanes compute, the stores are predicated (above)
+    constexpr bool NSPLIT = (((TL::RW == 16 ? kNormSplitMask : kNormSplitMaskWide) >> MODE) & 1) != 0;   // second-stage norms only on trips that can end (above)
     constexpr int RW = TL::RW, BS = TL::BS, LS = TL::LS, IS = TL::IS, NBT = TL::NBT, WPB = TL::WPB, SPW = TL::SPW, OW = TL::OW;
     using DevCase = DevCaseT<TL>;
     using Partial = PartialT<TL>;
@@ -345,7 +360,10 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
         uint32_t niq = 0;
         int it = 0, status = 0;
         bool infeas = false, singular = false, iterating = false;
-        uint32_t lozero = 0;                 // bit s: lower bound of injection slot s relaxed to 0 (island rules 3, 4)
+        // NSPLIT: what the update leaves for the next trip's test -- |x|inf and the NaN flag of the x it wrote, and the test's first stage
+        double x_inf = 0.0;
+        bool x_nan = false, stage1 = false;
+        uint32_t lozero = 0;                // bit s: lower bound of injection slot s relaxed to 0 (island rules 3, 4)
 #define ISC(s) ((RW * (s) + rlane >= ng) ? lscale : 1.0)      /* virtual generators (loads) scale with the hourly factor */
 #define ILOV(s, lo_) (((lozero >> (s)) & 1u) ? 0.0 : (lo_) * ISC(s))      /* lower bound of injection slot s from its table value lo_ */
 #pragma unroll
@@ -757,7 +775,18 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
 #pragma unroll
                 for (int t = 0; t < BS; ++t) __asm__ volatile("" : "+v"(vb[t]));
             }
-            if (iterating) {
+            // NSPLIT: can this trip end for some row of the wavefront?  Known before it starts (stage1 is the update's), wave-uniform: the
+            // front half of the trip runs as a whole in one of its two forms
+#ifdef RELMC_TRACE
+            const bool need_norms = true;
+#else
+            const bool need_norms = !NSPLIT || __builtin_amdgcn_readfirstlane((int)(__any(iterating && stage1) != 0 || a.norms_always != 0)) != 0;
+#endif
+            PT_TRIP(need_norms ? 1 : 0)
+            // The front half of a trip: evaluation, gathers, KKT blocks into the workspace, convergence and failure tests.  NORMS = false is the
+            // same text without the four second-stage norms; it runs only when no row's first stage holds, so no row can converge in it.
+            auto front_half = [&](auto norms_c) __attribute__((always_inline)) {
+                constexpr bool NORMS = decltype(norms_c)::value;
                 // ---- evaluate h, Lx, barrier terms; scatter to LDS; convergence norms -------------
                 double mx_gh = -DINF, mx_x = 0.0, mx_z = 0.0, mx_lx = 0.0, mx_lammu = 0.0;
                 bool nanx = false;
@@ -774,9 +803,11 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                         g = b * b * (lmup[s] * rzp + lmum[s] * rzm);
                         lx = __builtin_fma(b, lmup[s] - lmum[s], lx);
                         q = b * ((lmup[s] * hp + gamma) * rzp - (lmum[s] * hm + gamma) * rzm);
-                        mx_gh = vmax(mx_gh, vmax(hp, hm));
-                        mx_z = vmax(mx_z, vmax(lzp[s], lzm[s]));
-                        mx_lammu = vmax(mx_lammu, vmax(lmup[s], lmum[s]));
+                        if constexpr (NORMS) {
+                            mx_gh = vmax(mx_gh, vmax(hp, hm));
+                            mx_z = vmax(mx_z, vmax(lzp[s], lzm[s]));
+                            mx_lammu = vmax(mx_lammu, vmax(lmup[s], lmum[s]));
+                        }
                     }
                     gown[s] = g;
                     if (l < nlp) { st2(LR + 4 * l, g, lx); st2(LR + 4 * l + 2, lx + q, LFv[s]); }   // nl / ninj records (they alias W)
@@ -787,8 +818,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                     const int j = RW * s + rlane;
                     double invD = 0.0, npd = 0.0;
                     const double pv = ip[s];         // stays 0 on an injection out of service
-                    mx_x = vmax(mx_x, __builtin_fabs(pv));
-                    nanx = nanx || pv != pv;
+                    if constexpr (!NSPLIT) { mx_x = vmax(mx_x, __builtin_fabs(pv)); nanx = nanx || pv != pv; }
                     if (I_BOX(s)) {
                         const d2 hl = IHL(s, j);               // {upper, lower} bound
                         const double hp = pv - hl.x, hm = ILOV(s, hl.y) - pv;
@@ -807,10 +837,12 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                         const double np = lxp + (imup[s] * hp + gamma) * rzp - (imum[s] * hm + gamma) * rzm;
                         invD = frcp(D); npd = np * invD;
                         }
-                        mx_lx = vmax(mx_lx, __builtin_fabs(lxp));
-                        mx_gh = vmax(mx_gh, vmax(hp, hm));
-                        mx_z = vmax(mx_z, vmax(izp[s], izm[s]));
-                        mx_lammu = vmax(mx_lammu, vmax(imup[s], imum[s]));
+                        if constexpr (NORMS) {
+                            mx_lx = vmax(mx_lx, __builtin_fabs(lxp));
+                            mx_gh = vmax(mx_gh, vmax(hp, hm));
+                            mx_z = vmax(mx_z, vmax(izp[s], izm[s]));
+                            mx_lammu = vmax(mx_lammu, vmax(imup[s], imum[s]));
+                        }
                     }
                     if (j < nip) IR[j] = pv;
                     st2(Stash + 2 * RW * s, invD, npd);
@@ -878,22 +910,25 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                         }
                         if (B_PIN(t)) {                   // fixed angle: identity row; its multiplier is -lx
                             d00[t] = 1.0; r0[t] = 0.0;
-                            mx_lammu = vmax(mx_lammu, __builtin_fabs(lx));
+                            if constexpr (NORMS) mx_lammu = vmax(mx_lammu, __builtin_fabs(lx));
                         } else {
                             d00[t] = md; r0[t] = -nq_;
-                            mx_lx = vmax(mx_lx, __builtin_fabs(lx));
+                            if constexpr (NORMS) mx_lx = vmax(mx_lx, __builtin_fabs(lx));
                         }
                         if (B_DROP(t)) {                  // dependent balance row
                             d11[t] = -1.0; r1[t] = 0.0;
                         } else {
                             d11[t] = -E; r1[t] = -bal - ssum;
-                            mx_gh = vmax(mx_gh, __builtin_fabs(bal));
-                            mx_lammu = vmax(mx_lammu, __builtin_fabs(bla[t]));
+                            if constexpr (NORMS) {
+                                mx_gh = vmax(mx_gh, __builtin_fabs(bal));
+                                mx_lammu = vmax(mx_lammu, __builtin_fabs(bla[t]));
+                            }
                         }
-                        mx_x = vmax(mx_x, __builtin_fabs(bth[t]));
-                        nanx = nanx || bth[t] != bth[t];
+                        if constexpr (!NSPLIT) { mx_x = vmax(mx_x, __builtin_fabs(bth[t])); nanx = nanx || bth[t] != bth[t]; }
                     }
                 }
+                double o_ct = 0.0, o_cc = 0.0, o_am = 0.0;
+                if constexpr (NSPLIT && PFSITE(7)) o_am = A_(7, alpha_min);     // the one option the test still reads: requested ahead of the block stores
                 // ---- ... then overwrite the workspace (same LDS words as the evaluation arrays) ------
                 RELOAD_FENCE();
                 if constexpr (DENSE) {
@@ -957,12 +992,19 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 // The four conditions must hold together, so the two that need only |x| (complementarity and
                 // cost change) are tested first; the other three row reductions run only when some scenario
                 // of the wavefront passes them (never before the last 2-3 iterations).
-                double o_ct = 0.0, o_cc = 0.0, o_am = 0.0;
-                if constexpr (PFSITE(7)) { o_ct = A_(2, comptol); o_cc = A_(3, costtol); o_am = A_(7, alpha_min); }
-                mx_x = row_max<RW>(mx_x);
-                const bool xnan = row_any<RW>(nanx, lane);
-                if constexpr (!PFSITE(7)) { o_ct = A_(2, comptol); o_cc = A_(3, costtol); }
-                bool conv = it > 0 && zmu < o_ct * (1.0 + mx_x) && __builtin_fabs(fval - f0) < o_cc * (1.0 + __builtin_fabs(f0));
+                // NSPLIT: the first stage, |x|inf and the NaN flag are the update's (stage1, x_inf, x_nan: formed from the same values, below);
+                // the trips without the norms run only when no row passes it.
+                bool conv = false, xnan = false;
+                if constexpr (NSPLIT) {
+                    mx_x = x_inf; xnan = x_nan;
+                    conv = NORMS && stage1;
+                } else {
+                    if constexpr (PFSITE(7)) { o_ct = A_(2, comptol); o_cc = A_(3, costtol); o_am = A_(7, alpha_min); }
+                    mx_x = row_max<RW>(mx_x);
+                    xnan = row_any<RW>(nanx, lane);
+                    if constexpr (!PFSITE(7)) { o_ct = A_(2, comptol); o_cc = A_(3, costtol); }
+                    conv = it > 0 && zmu < o_ct * (1.0 + mx_x) && __builtin_fabs(fval - f0) < o_cc * (1.0 + __builtin_fabs(f0));
+                }
 #ifdef RELMC_TRACE
                 {   // debug builds: per-iteration termination quantities of scenario 0 (first launch row) -> a.timing as doubles
                     const double t_gh = row_max<RW>(mx_gh), t_z = row_max<RW>(mx_z), t_lx = row_max<RW>(mx_lx), t_lm = row_max<RW>(mx_lammu);
@@ -973,7 +1015,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                     }
                 }
 #endif
-                if (__any(conv)) {
+                if constexpr (NORMS) if (__any(conv)) {
                     mx_gh = row_max<RW>(mx_gh); mx_z = row_max<RW>(mx_z); mx_lx = row_max<RW>(mx_lx); mx_lammu = row_max<RW>(mx_lammu);
                     // feascond < feastol, gradcond < gradtol with the (positive) denominators multiplied out
                     conv = conv && mx_gh < A_(0, feastol) * (1.0 + vmax(mx_x, mx_z)) && mx_lx < A_(1, gradtol) * (1.0 + mx_lammu);
@@ -981,6 +1023,9 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 if (conv) { status = 0; iterating = false; }
                 else if (it > 0 && (xnan || alphap < (PFSITE(7) ? o_am : A_(7, alpha_min)) || alphad < (PFSITE(7) ? o_am : A_(7, alpha_min)) || gamma < eps || gamma > 1.0 / eps)) { status = 2; iterating = false; }
                 else if (it >= a.max_it) { status = 1; iterating = false; }
+            };
+            if (iterating) {
+                if (need_norms) front_half(std::true_type{}); else front_half(std::false_type{});
             }
             PT_MARK(3)
             RELOAD_FENCE();
@@ -1276,6 +1321,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                     alphap = tp > 0.0 ? vmin(o_xi * frcp(tp), 1.0) : 1.0;   // min(xi * min(z./-dz), 1)
                     alphad = td > 0.0 ? vmin(o_xi * frcp(td), 1.0) : 1.0;
                     double zl = 0.0, fl = 0.0;
+                    double xm = 0.0; bool xn = false;      // NSPLIT: |x|inf and the NaN flag of the x written here, as the next evaluation would take them
 #pragma unroll
                     for (int s = 0; s < LS; ++s) {
                         if (L_ACT(s)) {
@@ -1308,16 +1354,27 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                             zl = __builtin_fma(izp[s], imup[s], zl); zl = __builtin_fma(izm[s], imum[s], zl);
                         }
                         fl = __builtin_fma(ICOST(s, RW * s + rlane), ip[s], fl);      // p = 0 on an injection out of service
+                        if constexpr (NSPLIT) { xm = vmax(xm, __builtin_fabs(ip[s])); xn = xn || ip[s] != ip[s]; }
                         SLOT_FENCE();
                     }
+                    double o_ct = 0.0, o_cc = 0.0;
+                    if constexpr (NSPLIT) { o_ct = A_(2, comptol); o_cc = A_(3, costtol); }      // requested before the row reductions
 #pragma unroll
                     for (int t = 0; t < BS; ++t) {
                         bth[t] = __builtin_fma(alphap, dth[t], bth[t]); bla[t] = __builtin_fma(alphad, dla[t], bla[t]);
-                        if (vb[t] < nb) Lam[vb[t]] = bla[t];
+                        if (vb[t] < nb) {
+                            Lam[vb[t]] = bla[t];
+                            if constexpr (NSPLIT) { xm = vmax(xm, __builtin_fabs(bth[t])); xn = xn || bth[t] != bth[t]; }
+                        }
                     }
                     zmu = row_sum<RW>(zl);
                     fval = row_sum<RW>(fl);
                     if (niq > 0) gamma = (PFSITE(6) ? o_sg : A_(5, sigma)) * zmu / (double)niq;
+                    if constexpr (NSPLIT) {
+                        // the first stage of the next trip's test (mips.m compcond, costcond): it and f0 are already that trip's
+                        x_inf = row_max<RW>(xm); x_nan = row_any<RW>(xn, lane);
+                        stage1 = zmu < o_ct * (1.0 + x_inf) && __builtin_fabs(fval - f0) < o_cc * (1.0 + __builtin_fabs(f0));
+                    }
                 }
                 PT_MARK(6)
             }

@@ -17,3 +17,8 @@ o9 = (C.c_int32 * 9)()
 eng.L.relmc_debug_schedule.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
 eng.L.relmc_debug_schedule(eng._h, o9)
 print("schedule: upd/inv/bwd passes", o9[0], o9[1], o9[2], "noff", o9[3], "nzero", o9[4], "nws", o9[5], "lds_bytes", o9[6], "blocks/CU", o9[7], "tasks", o9[8])
+o2 = (C.c_ulonglong * 2)()
+eng.L.relmc_debug_norm_trips.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+eng.L.relmc_debug_norm_trips(eng._h, o2)
+if o2[0] + o2[1]:
+    print(f"wavefront trips without / with the second-stage norms: {o2[0]} / {o2[1]}  (share without: {o2[0] / (o2[0] + o2[1]):.4f})")

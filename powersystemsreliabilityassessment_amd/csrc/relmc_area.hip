@@ -5,7 +5,7 @@
 #include <cstring>
 #include <vector>
 
-#include "relmc_ctx.h"
+#include "relmc_hl1_host.h"
 #include "relmc_area_kernels.h"
 
 using namespace relmc_host;
@@ -101,7 +101,7 @@ int32_t relmc_hl1_area(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int6
 {
     if (!ctx) return RELMC_ERR_INVALID;
     if (!ctx->has_hl1_area) return fail(ctx, RELMC_ERR_NO_CASE, "relmc_hl1_area: relmc_hl1_area_load has not been called");
-    if (!acc || n_chains < 0 || years_per_chain < 1 || (start != RELMC_HL1_START_ALL_UP && start != RELMC_HL1_START_STATIONARY) ||
+    if (!hl1_chain_args_ok(acc, n_chains, years_per_chain, start) ||
         (policy != RELMC_HL1_AREA_ISOLATED && policy != RELMC_HL1_AREA_INTERCONNECTED) ||
         (flow != RELMC_HL1_AREA_FLOW_REFERENCE && flow != RELMC_HL1_AREA_FLOW_MAX_FLOW))
         return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_area: bad arguments");
@@ -110,44 +110,32 @@ int32_t relmc_hl1_area(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int6
     std::memset(acc, 0, sizeof(*acc) * rows);
     if (n_chains == 0) return RELMC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // chains go in launches of at most ~4M year records x rows (records [row][chain * years + year][3], rows one slice apart); a chain's
-    // records never depend on the launch it is in
-    const int64_t max_rec = (int64_t)1 << 22;
-    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_chains, max_rec / years_per_chain));
-    const int64_t rec_max = per * years_per_chain;
-    HIP_TRY(ctx, S.years.grow((size_t)rec_max * 3 * rows));
-    HIP_TRY(ctx, S.part.grow((size_t)hl1_reduce_blocks(rec_max) * 6 * rows));
     const bool inter = policy == RELMC_HL1_AREA_INTERCONNECTED;
     const int nw = (S.ngen + 31) >> 5;
     const bool ties = inter && S.tie_outages && S.tie_fail;       // the tie-outage kernel: one more mask row
     const size_t lds = sizeof(double) * 64 * (2 * S.n_areas + 1 + (inter ? S.n_areas * S.n_areas : 0)) +
                        sizeof(uint32_t) * (nw + (ties ? 1 : 0)) * relmc::HL1_SEQ_WINDOW;
-    std::vector<double> part, stage;
-    std::vector<double> sum((size_t)rows * 6, 0.0);
-    double kernel_ms = 0.0;
-    for (int64_t c0 = 0; c0 < n_chains; c0 += per) {
-        const int64_t nc = std::min(per, n_chains - c0), nrec = nc * years_per_chain;
-        (void)hipEventRecord(ctx->ev0, ctx->stream);
-        const auto kernel = ties ? relmc::relmc_hl1_area_kernel<true> : relmc::relmc_hl1_area_kernel<false>;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)nc), dim3(64), lds, ctx->stream, S.dcase.get(), ties ? S.dties.get() : nullptr, S.load.get(), seed,
-                           first_chain + (uint64_t)c0, years_per_chain, start, policy, flow, nrec, S.years.get());
-        if (const int rc = hl1_reduce_queue(ctx, "relmc_hl1_area", S.years.get(), nrec, rows, S.part.get(), part)) return rc;
-        if (years_host) {
-            stage.resize((size_t)nrec * 3 * rows);
-            HIP_TRY(ctx, hipMemcpyAsync(stage.data(), S.years.get(), sizeof(double) * stage.size(), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_area: synchronisation failed");
-        kernel_ms += ctx->last_kernel_ms;
-        hl1_reduce_add(part, rows, sum.data());
-        if (years_host)                                            // [row][record] -> [record][row]
-            for (int64_t i = 0; i < nrec; ++i)
-                for (int r = 0; r < rows; ++r) {
-                    relmc_hl1_seq_year& o = years_host[(size_t)(c0 * years_per_chain + i) * rows + r];
-                    const double* s = stage.data() + ((size_t)r * nrec + i) * 3;
-                    o.lole = s[0]; o.eue = s[1]; o.lolf = s[2];
-                }
-    }
-    ctx->last_kernel_ms = kernel_ms;
+    const auto kernel = ties ? relmc::relmc_hl1_area_kernel<true> : relmc::relmc_hl1_area_kernel<false>;
+    std::vector<double> stage, sum((size_t)rows * 6, 0.0);
+    // records [row][chain * years + year][3], rows one slice apart.  A chain counts the year records of ONE row here (the other models
+    // count every slice): a launch holds ~4M year records x rows, as it has since the model was added
+    const int64_t per = hl1_chunk_items(n_chains, kHl1RecordBudget, years_per_chain);
+    const int rc = hl1_run_records(ctx, "relmc_hl1_area", S.rec, n_chains, per, years_per_chain, rows, sum.data(),
+        [&](int64_t c0, int64_t nc, int64_t nrec) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)nc), dim3(64), lds, ctx->stream, S.dcase.get(), ties ? S.dties.get() : nullptr, S.load.get(), seed,
+                               first_chain + (uint64_t)c0, years_per_chain, start, policy, flow, nrec, S.rec.years.get());
+        },
+        [&](int64_t, int64_t, int64_t nrec) -> int {
+            if (years_host) {
+                stage.resize((size_t)nrec * 3 * rows);
+                HIP_TRY(ctx, hipMemcpyAsync(stage.data(), S.rec.years.get(), sizeof(double) * stage.size(), hipMemcpyDeviceToHost, ctx->stream));
+            }
+            return RELMC_OK;
+        },
+        [&](int64_t c0, int64_t, int64_t nrec) {                  // [row][record] -> [record][row]
+            if (years_host) hl1_rows_to_host(stage, 1, rows, nrec, n_chains * years_per_chain, c0 * years_per_chain, years_host);
+        });
+    if (rc) return rc;
     for (int r = 0; r < rows; ++r) hl1_acc_fill(acc + r, n_chains * years_per_chain, sum.data() + (size_t)r * 6);
     return RELMC_OK;
 }

@@ -8,7 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "relmc_ctx.h"
+#include "relmc_hl1_host.h"
 #include "relmc_area_sweep_kernels.h"
 
 using namespace relmc_host;
@@ -25,7 +25,7 @@ int32_t relmc_hl1_area_sweep(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain
     const std::string who = "relmc_hl1_area_sweep: ";
     if (!ctx) return RELMC_ERR_INVALID;
     if (!ctx->has_hl1_area) return fail(ctx, RELMC_ERR_NO_CASE, who + "relmc_hl1_area_load has not been called");
-    if (!acc || !levels || n_chains < 0 || years_per_chain < 1 || (start != RELMC_HL1_START_ALL_UP && start != RELMC_HL1_START_STATIONARY) ||
+    if (!levels || !hl1_chain_args_ok(acc, n_chains, years_per_chain, start) ||
         (flow != RELMC_HL1_AREA_FLOW_REFERENCE && flow != RELMC_HL1_AREA_FLOW_MAX_FLOW))
         return fail(ctx, RELMC_ERR_INVALID, who + "bad arguments");
     if (n_levels < 1 || n_levels > RELMC_HL1_AREA_SWEEP_MAX_LEVELS)
@@ -70,13 +70,7 @@ int32_t relmc_hl1_area_sweep(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain
     std::memset(acc, 0, sizeof(*acc) * slices);
     if (n_chains == 0) return RELMC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // chains go in launches of at most ~4M year records counted over levels and rows; a chain's records never depend on the launch it is in
-    const int64_t max_rec = (int64_t)1 << 22;
-    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_chains, max_rec / ((int64_t)years_per_chain * slices)));
-    const int64_t rec_max = per * years_per_chain;           // records of one slice in a launch
     HIP_TRY(ctx, S.sweep_tab.grow(1));
-    HIP_TRY(ctx, S.sweep_years.grow((size_t)rec_max * 3 * slices));
-    HIP_TRY(ctx, S.sweep_part.grow((size_t)hl1_reduce_blocks(rec_max) * 6 * slices));
     HIP_TRY(ctx, hipMemcpy(S.sweep_tab.get(), &tab, sizeof(tab), hipMemcpyHostToDevice));
     const int nw = (S.ngen + 31) >> 5;
     const bool ties = S.tie_outages && S.tie_fail;          // relmc_hl1_area's rule under INTERCONNECTED: the tie cursors, one more mask row
@@ -85,32 +79,24 @@ int32_t relmc_hl1_area_sweep(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain
     const auto kernel = ties ? relmc::relmc_hl1_area_sweep_kernel<true> : relmc::relmc_hl1_area_sweep_kernel<false>;
     if (lds > 64 * 1024)                                     // 8 levels x 8 areas: 83 KB of the CU's 160 KB
         HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    std::vector<double> part, stage;
-    std::vector<double> sum((size_t)slices * 6, 0.0);
-    double kernel_ms = 0.0;
-    for (int64_t c0 = 0; c0 < n_chains; c0 += per) {
-        const int64_t nc = std::min(per, n_chains - c0), nrec = nc * years_per_chain;
-        (void)hipEventRecord(ctx->ev0, ctx->stream);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)nc), dim3(64), lds, ctx->stream, S.dcase.get(), ties ? S.dties.get() : nullptr, S.sweep_tab.get(),
-                           S.load.get(), seed, first_chain + (uint64_t)c0, years_per_chain, start, flow, nrec, S.sweep_years.get());
-        if (const int rc = hl1_reduce_queue(ctx, "relmc_hl1_area_sweep", S.sweep_years.get(), nrec, slices, S.sweep_part.get(), part)) return rc;
-        if (years_host) {
-            stage.resize((size_t)nrec * 3 * slices);
-            HIP_TRY(ctx, hipMemcpyAsync(stage.data(), S.sweep_years.get(), sizeof(double) * stage.size(), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, who + "synchronisation failed");
-        kernel_ms += ctx->last_kernel_ms;
-        hl1_reduce_add(part, slices, sum.data());
-        if (years_host)                                            // [level][row][record] -> [level][record][row]
-            for (int j = 0; j < n_levels; ++j)
-                for (int64_t i = 0; i < nrec; ++i)
-                    for (int r = 0; r < rows; ++r) {
-                        relmc_hl1_seq_year& o = years_host[((size_t)j * total + (size_t)(c0 * years_per_chain + i)) * rows + r];
-                        const double* s = stage.data() + ((size_t)(j * rows + r) * nrec + i) * 3;
-                        o.lole = s[0]; o.eue = s[1]; o.lolf = s[2];
-                    }
-    }
-    ctx->last_kernel_ms = kernel_ms;
+    std::vector<double> stage, sum((size_t)slices * 6, 0.0);
+    const int64_t per = hl1_chunk_items(n_chains, kHl1RecordBudget, (int64_t)years_per_chain * slices);        // a chain counts its records of all levels and rows
+    const int rc = hl1_run_records(ctx, "relmc_hl1_area_sweep", S.sweep_rec, n_chains, per, years_per_chain, slices, sum.data(),
+        [&](int64_t c0, int64_t nc, int64_t nrec) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)nc), dim3(64), lds, ctx->stream, S.dcase.get(), ties ? S.dties.get() : nullptr, S.sweep_tab.get(),
+                               S.load.get(), seed, first_chain + (uint64_t)c0, years_per_chain, start, flow, nrec, S.sweep_rec.years.get());
+        },
+        [&](int64_t, int64_t, int64_t nrec) -> int {
+            if (years_host) {
+                stage.resize((size_t)nrec * 3 * slices);
+                HIP_TRY(ctx, hipMemcpyAsync(stage.data(), S.sweep_rec.years.get(), sizeof(double) * stage.size(), hipMemcpyDeviceToHost, ctx->stream));
+            }
+            return RELMC_OK;
+        },
+        [&](int64_t c0, int64_t, int64_t nrec) {                  // [level][row][record] -> [level][record][row]
+            if (years_host) hl1_rows_to_host(stage, n_levels, rows, nrec, total, c0 * years_per_chain, years_host);
+        });
+    if (rc) return rc;
     for (int s = 0; s < slices; ++s) hl1_acc_fill(acc + s, total, sum.data() + (size_t)s * 6);
     return RELMC_OK;
 }

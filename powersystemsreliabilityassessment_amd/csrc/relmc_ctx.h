@@ -14,10 +14,12 @@
 //                        sequential chronology (relmc_hl1_seq), its loss events (relmc_hl1_seq_events, kernels in relmc_event_kernels.h), its
 //                        load sweep (relmc_hl1_seq_sweep, kernel in relmc_sweep_kernels.h) and
 //                        the record reduction and unit check of every HL1 chronology track
+//   relmc_hl1_host.h     (a header, included by the six HL1 units around it) what their host code shares: the chunk rule, the loop over a
+//                        model's launches with the reduction of their year records (hl1_run_records), the argument and unit checks
 //   relmc_storage.hip    energy storage with a state of charge on that chronology (relmc_hl1_seq_storage, kernel in relmc_storage_kernels.h)
 //   relmc_multistate.hip that chronology with three-state units (relmc_hl1_ms_load, relmc_hl1_ms_seq, kernel in relmc_multistate_kernels.h)
 //   relmc_plan.hip       the HL1 planning model's Monte Carlo (relmc_hl1_plan)
-//   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area); its rows are summed by relmc_seq.hip's record reduction
+//   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area)
 //   relmc_area_sweep.hip the sweep of that chronology over load, tie and fleet levels (relmc_hl1_area_sweep, kernel in relmc_area_sweep_kernels.h)
 //   relmc_screen.hip     the zero-curtailment pre-screen (relmc_solver_opts.screen): certificate tables, pre-pass kernels, worklists
 //   relmc_importance.hip importance sampling for the non-sequential track: tilted sampler with likelihood ratios, weighted reductions (kernels in
@@ -86,11 +88,15 @@ private:
 };
 template <class T> using DevBuf = Buffer<T, false>;
 template <class T> using PinBuf = Buffer<T, true>;
+// The device buffers of an HL1 record model (relmc_hl1_host.h, hl1_run_records): the year records of one launch and the block partials of
+// their reduction, grow-only.  Every model keeps a pair of its own.
+struct Hl1Records { DevBuf<double> years, part; };
 }  // namespace relmc_host
 
 struct relmc_ctx {
     template <class T> using DevBuf = relmc_host::DevBuf<T>;
     template <class T> using PinBuf = relmc_host::PinBuf<T>;
+    using Hl1Records = relmc_host::Hl1Records;
     static constexpr size_t kCaseBytes = sizeof(relmc::DevCaseT<relmc::Tile96>) > sizeof(relmc::DevCaseT<relmc::Tile24>) ? sizeof(relmc::DevCaseT<relmc::Tile96>)
                                                                                                                       : sizeof(relmc::DevCaseT<relmc::Tile24>);
     int device = -1;
@@ -183,34 +189,32 @@ struct relmc_ctx {
     // HL1 copper-sheet model; lole / eue / part: relmc_hl1_nsq's device buffers, grow-only
     bool has_hl1 = false; int hl1_hours = 0;
     struct Hl1 { DevBuf<relmc::Hl1Case> dcase; DevBuf<double> sorted, suffix, lole, eue, part; } hl1;
-    // HL1 sequential chronology (relmc_hl1_seq): its own fleet / load curve, grow-only per-year records and reduction partials
+    // HL1 sequential chronology (relmc_hl1_seq): its own fleet / load curve, the call's records
     bool has_hl1_seq = false;
-    struct Hl1Seq { int ngen = 0, nhours = 0; DevBuf<relmc::Hl1SeqCase> dcase; DevBuf<double> load, years, part; } hl1_seq;
+    struct Hl1Seq { int ngen = 0, nhours = 0; DevBuf<relmc::Hl1SeqCase> dcase; DevBuf<double> load; Hl1Records rec; } hl1_seq;
     // loss events of that model (relmc_hl1_seq_events): grow-only chain records / counts / list offsets, reduction partials, histogram, list
     struct Hl1Events {
         DevBuf<relmc::Hl1EventRec> rec, part; DevBuf<long long> count, offset; DevBuf<unsigned long long> hist; DevBuf<relmc_hl1_event> list;
     } hl1_events;
-    // load sweep on that model (relmc_hl1_seq_sweep): grow-only per-level year records and reduction partials
-    struct Hl1Sweep { DevBuf<double> years, part; } hl1_sweep;
-    // storage on that model (relmc_hl1_seq_storage): grow-only year records of both rows and reduction partials
-    struct Hl1Storage { DevBuf<double> years, part; } hl1_storage;
+    // load sweep on that model (relmc_hl1_seq_sweep): per-level records; storage on that model (relmc_hl1_seq_storage): records of both rows
+    Hl1Records hl1_sweep, hl1_storage;
     // HL1 sequential chronology with three-state units (relmc_hl1_ms_load / relmc_hl1_ms_seq): its own fleet / load curve, apart from every
-    // other HL1 model; grow-only year records of both rows and reduction partials
+    // other HL1 model; records of both rows
     bool has_hl1_ms = false;
-    struct Hl1Ms { int ngen = 0, nhours = 0; DevBuf<relmc::Hl1MsCase> dcase; DevBuf<double> load, years, part; } hl1_ms;
-    // HL1 planning model (relmc_hl1_plan): its own fleet / maintenance / ELUs / load curve, grow-only per-year records, ELU energies,
-    // hour loss counts and reduction partials
+    struct Hl1Ms { int ngen = 0, nhours = 0; DevBuf<relmc::Hl1MsCase> dcase; DevBuf<double> load; Hl1Records rec; } hl1_ms;
+    // HL1 planning model (relmc_hl1_plan): its own fleet / maintenance / ELUs / load curve, per-year records, grow-only ELU energies and
+    // hour loss counts
     bool has_hl1_plan = false;
-    struct Hl1Plan { int nhours = 0, n_elu = 0; DevBuf<relmc::PlanCase> dcase; DevBuf<double> load, years, elu, part; DevBuf<unsigned long long> hours; } hl1_plan;
-    // HL1 multi-area chronology (relmc_hl1_area): its own areas / ties / load curves, grow-only per-row year records and reduction partials
+    struct Hl1Plan { int nhours = 0, n_elu = 0; DevBuf<relmc::PlanCase> dcase; DevBuf<double> load, elu; Hl1Records rec; DevBuf<unsigned long long> hours; } hl1_plan;
+    // HL1 multi-area chronology (relmc_hl1_area): its own areas / ties / load curves, per-row records
     bool has_hl1_area = false;
     // ties: the loaded ties one by one; tie_outages: relmc_hl1_area_tie_outages' data is in force (dties), tie_fail: with a finite mttf
     struct Hl1Area {
-        int ngen = 0, nhours = 0, n_areas = 0; DevBuf<relmc::AreaCase> dcase; DevBuf<double> load, years, part;
+        int ngen = 0, nhours = 0, n_areas = 0; DevBuf<relmc::AreaCase> dcase; DevBuf<double> load; Hl1Records rec;
         std::vector<int32_t> tie_from, tie_to; std::vector<double> tie_cap;
         bool tie_outages = false, tie_fail = false; DevBuf<relmc::AreaTies> dties;
-        // relmc_hl1_area_sweep (relmc_area_sweep.hip): the levels' table of a call, grow-only per-level, per-row year records and partials
-        DevBuf<relmc::AreaSweepTab> sweep_tab; DevBuf<double> sweep_years, sweep_part;
+        // relmc_hl1_area_sweep (relmc_area_sweep.hip): the levels' table of a call, per-level, per-row records
+        DevBuf<relmc::AreaSweepTab> sweep_tab; Hl1Records sweep_rec;
     } hl1_area;
     // zero-curtailment pre-screen (relmc_screen.hip): certificate tables of the case (device pointers inside tab), grow-only work buffers of a pre-pass
     struct Screen {
@@ -396,31 +400,6 @@ inline int64_t stretch_per(int64_t batch) { return kStretch / batch * batch; }  
 // round: samples of one round of the fused grid, below whose multiples other stretches end (0 = do not snap: the database form)
 struct Stretch { int64_t len; bool final; };
 Stretch stretch_length(int64_t batch, int64_t done, double beta, double beta_limit, int64_t per, int64_t round);
-
-// ---- relmc_seq.hip ------------------------------------------------------------------------------------------------------------
-// Host code the HL1 tracks share; `who` is the calling function's name, for the message.
-// relmc_hl1_seq_load and relmc_hl1_area_load: the per-unit rule of the chronology models (capacity finite, MTTF and MTTR finite and
-// positive); fills cap / mttf / mttr and q = mttr / (mttf + mttr)
-int hl1_units_fill(relmc_ctx* ctx, const char* who, int ngen, const double* capacity_mw, const double* mttf_h, const double* mttr_h,
-                   double* cap, double* mttf, double* mttr, double* q);
-inline int64_t hl1_reduce_blocks(int64_t n) { const int64_t b = (n + 255) / 256; return b < 1024 ? b : 1024; }   // workgroups over a slice of n records
-// relmc_hl1_seq, relmc_hl1_plan and relmc_hl1_area: the tail of a launch, after the model kernel: relmc_hl1_reduce_kernel over each of `rows` slices of n records (rec[row][n][3], fixed
-// order) into dpart[row][blocks][6], ev1 behind the last reduction, then the copy of the partials to `part` queued on the context's stream
-int hl1_reduce_queue(relmc_ctx* ctx, const char* who, const double* rec, int64_t n, int rows, double* dpart, std::vector<double>& part);
-// After finish_timing: sum[row][6] += the partials, block by block (the order is part of the results)
-inline void hl1_reduce_add(const std::vector<double>& part, int rows, double* sum)
-{
-    const size_t blocks = part.size() / 6 / (size_t)rows;
-    for (int r = 0; r < rows; ++r)
-        for (size_t b = 0; b < blocks; ++b)
-            for (int j = 0; j < 6; ++j) sum[(size_t)r * 6 + j] += part[((size_t)r * blocks + b) * 6 + j];
-}
-inline void hl1_acc_fill(relmc_hl1_seq_acc* acc, int64_t years, const double* sum)
-{
-    acc->years = years;
-    acc->sum_lole = sum[0]; acc->sum_eue = sum[1]; acc->sum_lolf = sum[2];
-    acc->sum_lole2 = sum[3]; acc->sum_eue2 = sum[4]; acc->sum_lolf2 = sum[5];
-}
 
 // ---- relmc_database.hip -------------------------------------------------------------------------------------------------------
 int db_accumulate(relmc_ctx* ctx, relmc_acc* acc_out);

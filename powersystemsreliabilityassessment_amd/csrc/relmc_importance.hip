@@ -8,7 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "relmc_ctx.h"
+#include "relmc_hl1_host.h"      // hl1_reduce_blocks: the weighted reductions take the HL1 record reduction's grid rule
 #include "relmc_is_kernels.h"
 
 namespace relmc_host {

@@ -8,7 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "relmc_ctx.h"
+#include "relmc_hl1_host.h"
 #include "relmc_multistate_kernels.h"
 
 using namespace relmc_host;
@@ -103,43 +103,34 @@ int32_t relmc_hl1_ms_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, in
     const std::string who = "relmc_hl1_ms_seq: ";
     if (!ctx) return RELMC_ERR_INVALID;
     if (!ctx->has_hl1_ms) return fail(ctx, RELMC_ERR_NO_CASE, who + "relmc_hl1_ms_load has not been called");
-    if (!acc || n_chains < 0 || years_per_chain < 1 || (start != RELMC_HL1_START_ALL_UP && start != RELMC_HL1_START_STATIONARY))
-        return fail(ctx, RELMC_ERR_INVALID, who + "bad arguments");
+    if (!hl1_chain_args_ok(acc, n_chains, years_per_chain, start)) return fail(ctx, RELMC_ERR_INVALID, who + "bad arguments");
     std::memset(acc, 0, sizeof(*acc));
     if (n_chains == 0) return RELMC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     auto& S = ctx->hl1_ms;
-    // the chunks of relmc_hl1_seq_storage: at most ~4M year records per launch over both rows; a chain's records never depend on the
-    // launch it is in
-    const int64_t max_rec = (int64_t)1 << 22;
-    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_chains, max_rec / ((int64_t)years_per_chain * 2)));
-    const int64_t rec_max = per * years_per_chain;                                       // records of one row in a launch
-    HIP_TRY(ctx, S.years.grow((size_t)rec_max * 3 * 2));
-    HIP_TRY(ctx, S.part.grow((size_t)hl1_reduce_blocks(rec_max) * 6 * 2));
-    std::vector<double> part, row1;
+    std::vector<double> row1;
     double sum[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    double kernel_ms = 0.0;
-    for (int64_t c0 = 0; c0 < n_chains; c0 += per) {
-        const int64_t nc = std::min(per, n_chains - c0), nrec = nc * years_per_chain;
-        (void)hipEventRecord(ctx->ev0, ctx->stream);
-        hipLaunchKernelGGL(relmc_hl1_ms_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
-                           first_chain + (uint64_t)c0, nc, years_per_chain, start, S.years.get());
-        if (const int rc = hl1_reduce_queue(ctx, "relmc_hl1_ms_seq", S.years.get(), nrec, 2, S.part.get(), part)) return rc;
-        if (years_host)
-            HIP_TRY(ctx, hipMemcpyAsync(years_host + c0 * years_per_chain, S.years.get(), sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
-        if (state_years_host) {
-            row1.resize((size_t)nrec * 3);
-            HIP_TRY(ctx, hipMemcpyAsync(row1.data(), S.years.get() + (size_t)nrec * 3, sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, who + "synchronisation failed");
-        kernel_ms += ctx->last_kernel_ms;
-        hl1_reduce_add(part, 2, sum);
-        if (state_years_host) {
+    const int64_t per = hl1_chunk_items(n_chains, kHl1RecordBudget, (int64_t)years_per_chain * 2);             // a chain counts its records of both rows
+    const int rc = hl1_run_records(ctx, "relmc_hl1_ms_seq", S.rec, n_chains, per, years_per_chain, 2, sum,
+        [&](int64_t c0, int64_t nc, int64_t) {
+            hipLaunchKernelGGL(relmc_hl1_ms_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
+                               first_chain + (uint64_t)c0, nc, years_per_chain, start, S.rec.years.get());
+        },
+        [&](int64_t c0, int64_t, int64_t nrec) -> int {
+            if (years_host)
+                HIP_TRY(ctx, hipMemcpyAsync(years_host + c0 * years_per_chain, S.rec.years.get(), sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
+            if (state_years_host) {
+                row1.resize((size_t)nrec * 3);
+                HIP_TRY(ctx, hipMemcpyAsync(row1.data(), S.rec.years.get() + (size_t)nrec * 3, sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
+            }
+            return RELMC_OK;
+        },
+        [&](int64_t c0, int64_t, int64_t nrec) {             // the second row leaves without its padding
+            if (!state_years_host) return;
             relmc_hl1_ms_year* const dst = state_years_host + c0 * years_per_chain;
             for (int64_t i = 0; i < nrec; ++i) { dst[i].derated_unit_h = row1[(size_t)3 * i]; dst[i].down_unit_h = row1[(size_t)3 * i + 1]; }
-        }
-    }
-    ctx->last_kernel_ms = kernel_ms;
+        });
+    if (rc) return rc;
     acc->years = n_chains * years_per_chain;
     acc->sum_lole = sum[0]; acc->sum_eue = sum[1]; acc->sum_lolf = sum[2]; acc->sum_lole2 = sum[3]; acc->sum_eue2 = sum[4]; acc->sum_lolf2 = sum[5];
     acc->sum_derated = sum[6]; acc->sum_down = sum[7]; acc->sum_derated2 = sum[9]; acc->sum_down2 = sum[10];

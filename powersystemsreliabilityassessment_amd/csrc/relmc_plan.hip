@@ -5,7 +5,7 @@
 #include <cstring>
 #include <vector>
 
-#include "relmc_ctx.h"
+#include "relmc_hl1_host.h"
 #include "relmc_plan_kernels.h"
 
 using namespace relmc_host;
@@ -73,35 +73,30 @@ int32_t relmc_hl1_plan(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int64
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // years go in launches of at most 2^20 (24 MB of records, 64 MB of ELU energies); a year's records never depend on the launch it is in
-    const int64_t per = std::min<int64_t>(n_years, (int64_t)1 << 20);
+    const int64_t per = hl1_chunk_items(n_years, (int64_t)1 << 20, 1);
     const bool want_elu = elu_energy_host && S.n_elu > 0;
-    HIP_TRY(ctx, S.years.grow((size_t)per * 3));
     if (want_elu) HIP_TRY(ctx, S.elu.grow((size_t)per * S.n_elu));
-    HIP_TRY(ctx, S.part.grow((size_t)hl1_reduce_blocks(per) * 6));
     HIP_TRY(ctx, S.hours.grow((size_t)S.nhours));
     HIP_TRY(ctx, hipMemsetAsync(S.hours.get(), 0, sizeof(unsigned long long) * S.nhours, ctx->stream));
-    std::vector<double> part;
     double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    double kernel_ms = 0.0;
-    for (int64_t y0 = 0; y0 < n_years; y0 += per) {
-        const int64_t ny = std::min(per, n_years - y0);
-        (void)hipEventRecord(ctx->ev0, ctx->stream);
-        hipLaunchKernelGGL(relmc_hl1_plan_kernel, dim3((unsigned)((ny + 255) / 256)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
-                           first_year + (uint64_t)y0, ny, S.years.get(), want_elu ? S.elu.get() : nullptr, S.hours.get());
-        if (const int rc = hl1_reduce_queue(ctx, "relmc_hl1_plan", S.years.get(), ny, 1, S.part.get(), part)) return rc;
-        if (years_host)
-            HIP_TRY(ctx, hipMemcpyAsync(years_host + y0, S.years.get(), sizeof(double) * 3 * ny, hipMemcpyDeviceToHost, ctx->stream));
-        if (want_elu)
-            HIP_TRY(ctx, hipMemcpyAsync(elu_energy_host + y0 * S.n_elu, S.elu.get(), sizeof(double) * S.n_elu * ny, hipMemcpyDeviceToHost, ctx->stream));
-        if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_plan: synchronisation failed");
-        kernel_ms += ctx->last_kernel_ms;
-        hl1_reduce_add(part, 1, sum);
-    }
+    const int rc = hl1_run_records(ctx, "relmc_hl1_plan", S.rec, n_years, per, 1, 1, sum,
+        [&](int64_t y0, int64_t ny, int64_t) {
+            hipLaunchKernelGGL(relmc_hl1_plan_kernel, dim3((unsigned)((ny + 255) / 256)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
+                               first_year + (uint64_t)y0, ny, S.rec.years.get(), want_elu ? S.elu.get() : nullptr, S.hours.get());
+        },
+        [&](int64_t y0, int64_t ny, int64_t) -> int {
+            if (years_host)
+                HIP_TRY(ctx, hipMemcpyAsync(years_host + y0, S.rec.years.get(), sizeof(double) * 3 * ny, hipMemcpyDeviceToHost, ctx->stream));
+            if (want_elu)
+                HIP_TRY(ctx, hipMemcpyAsync(elu_energy_host + y0 * S.n_elu, S.elu.get(), sizeof(double) * S.n_elu * ny, hipMemcpyDeviceToHost, ctx->stream));
+            return RELMC_OK;
+        },
+        hl1_no_host_step);
+    if (rc) return rc;
     if (hour_loss_count_host) {
         static_assert(sizeof(unsigned long long) == sizeof(int64_t), "hour counts are 64-bit");
         HIP_TRY(ctx, hipMemcpy(hour_loss_count_host, S.hours.get(), sizeof(int64_t) * S.nhours, hipMemcpyDeviceToHost));
     }
-    ctx->last_kernel_ms = kernel_ms;
     hl1_acc_fill(acc, n_years, sum);
     return RELMC_OK;
 }

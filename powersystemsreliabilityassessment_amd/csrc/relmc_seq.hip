@@ -7,7 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "relmc_ctx.h"
+#include "relmc_hl1_host.h"
 #include "relmc_seq_kernels.h"
 #include "relmc_event_kernels.h"
 #include "relmc_sweep_kernels.h"
@@ -414,34 +414,24 @@ int32_t relmc_hl1_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64
 {
     if (!ctx) return RELMC_ERR_INVALID;
     if (!ctx->has_hl1_seq) return fail(ctx, RELMC_ERR_NO_CASE, "relmc_hl1_seq: relmc_hl1_seq_load has not been called");
-    if (!acc || n_chains < 0 || years_per_chain < 1 || (start != RELMC_HL1_START_ALL_UP && start != RELMC_HL1_START_STATIONARY))
-        return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq: bad arguments");
+    if (!hl1_chain_args_ok(acc, n_chains, years_per_chain, start)) return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq: bad arguments");
     std::memset(acc, 0, sizeof(*acc));
     if (n_chains == 0) return RELMC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     auto& S = ctx->hl1_seq;
-    // chains go in launches of at most ~4M year records (96 MB); a chain's records never depend on the launch it is in
-    const int64_t max_rec = (int64_t)1 << 22;
-    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_chains, max_rec / years_per_chain));
-    const int64_t rec_max = per * years_per_chain;
-    HIP_TRY(ctx, S.years.grow((size_t)rec_max * 3));
-    HIP_TRY(ctx, S.part.grow((size_t)hl1_reduce_blocks(rec_max) * 6));
-    std::vector<double> part;
     double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    double kernel_ms = 0.0;
-    for (int64_t c0 = 0; c0 < n_chains; c0 += per) {
-        const int64_t nc = std::min(per, n_chains - c0), nrec = nc * years_per_chain;
-        (void)hipEventRecord(ctx->ev0, ctx->stream);
-        hipLaunchKernelGGL(relmc_hl1_seq_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
-                           first_chain + (uint64_t)c0, nc, years_per_chain, start, S.years.get());
-        if (const int rc = hl1_reduce_queue(ctx, "relmc_hl1_seq", S.years.get(), nrec, 1, S.part.get(), part)) return rc;
-        if (years_host)
-            HIP_TRY(ctx, hipMemcpyAsync(years_host + c0 * years_per_chain, S.years.get(), sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
-        if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_seq: synchronisation failed");
-        kernel_ms += ctx->last_kernel_ms;
-        hl1_reduce_add(part, 1, sum);
-    }
-    ctx->last_kernel_ms = kernel_ms;
+    const int rc = hl1_run_records(ctx, "relmc_hl1_seq", S.rec, n_chains, hl1_chunk_items(n_chains, kHl1RecordBudget, years_per_chain), years_per_chain, 1, sum,
+        [&](int64_t c0, int64_t nc, int64_t) {
+            hipLaunchKernelGGL(relmc_hl1_seq_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
+                               first_chain + (uint64_t)c0, nc, years_per_chain, start, S.rec.years.get());
+        },
+        [&](int64_t c0, int64_t, int64_t nrec) -> int {
+            if (years_host)
+                HIP_TRY(ctx, hipMemcpyAsync(years_host + c0 * years_per_chain, S.rec.years.get(), sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
+            return RELMC_OK;
+        },
+        hl1_no_host_step);
+    if (rc) return rc;
     hl1_acc_fill(acc, n_chains * years_per_chain, sum);
     return RELMC_OK;
 }
@@ -454,8 +444,7 @@ int32_t relmc_hl1_seq_events(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain
 {
     if (!ctx) return RELMC_ERR_INVALID;
     if (!ctx->has_hl1_seq) return fail(ctx, RELMC_ERR_NO_CASE, "relmc_hl1_seq_events: relmc_hl1_seq_load has not been called");
-    if (!acc || n_chains < 0 || years_per_chain < 1 || (start != RELMC_HL1_START_ALL_UP && start != RELMC_HL1_START_STATIONARY) ||
-        (dur_hist_host && (n_dur_bins < 1 || n_dur_bins > 4096)) || events_cap < 0)
+    if (!hl1_chain_args_ok(acc, n_chains, years_per_chain, start) || (dur_hist_host && (n_dur_bins < 1 || n_dur_bins > 4096)) || events_cap < 0)
         return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_events: bad arguments");
     std::memset(acc, 0, sizeof(*acc));
     if (dur_hist_host) std::memset(dur_hist_host, 0, sizeof(int64_t) * n_dur_bins);
@@ -464,8 +453,7 @@ int32_t relmc_hl1_seq_events(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain
     auto& S = ctx->hl1_seq;
     auto& E = ctx->hl1_events;
     // the chunks of relmc_hl1_seq: at most ~4M chain years per launch; a chain's events never depend on the launch it is in
-    const int64_t max_rec = (int64_t)1 << 22;
-    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_chains, max_rec / years_per_chain));
+    const int64_t per = hl1_chunk_items(n_chains, kHl1RecordBudget, years_per_chain);
     const int64_t pblocks = hl1_reduce_blocks(per);
     HIP_TRY(ctx, E.rec.grow((size_t)per));
     HIP_TRY(ctx, E.count.grow((size_t)per));
@@ -536,7 +524,7 @@ int32_t relmc_hl1_seq_sweep(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain,
 {
     if (!ctx) return RELMC_ERR_INVALID;
     if (!ctx->has_hl1_seq) return fail(ctx, RELMC_ERR_NO_CASE, "relmc_hl1_seq_sweep: relmc_hl1_seq_load has not been called");
-    if (!acc || !levels || n_chains < 0 || years_per_chain < 1 || (start != RELMC_HL1_START_ALL_UP && start != RELMC_HL1_START_STATIONARY))
+    if (!levels || !hl1_chain_args_ok(acc, n_chains, years_per_chain, start))
         return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_sweep: bad arguments");
     if (n_levels < 1 || n_levels > RELMC_HL1_SWEEP_MAX_LEVELS)
         return fail(ctx, RELMC_ERR_INVALID, "relmc_hl1_seq_sweep: n_levels " + std::to_string(n_levels) + " not in 1.." + std::to_string(RELMC_HL1_SWEEP_MAX_LEVELS));
@@ -564,31 +552,24 @@ int32_t relmc_hl1_seq_sweep(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain,
     if (n_chains == 0) return RELMC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     auto& X = ctx->hl1_sweep;
-    const int64_t max_rec = (int64_t)1 << 22;
-    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_chains, max_rec / ((int64_t)years_per_chain * n_levels)));
-    const int64_t rec_max = per * years_per_chain;                                       // records of one level in a launch
-    const int64_t pblocks = hl1_reduce_blocks(rec_max);
-    HIP_TRY(ctx, X.years.grow((size_t)rec_max * 3 * n_levels));
-    HIP_TRY(ctx, X.part.grow((size_t)pblocks * 6 * n_levels));
     const auto kernel = n_levels <= 1 ? relmc_hl1_sweep_kernel<1> : n_levels <= 4 ? relmc_hl1_sweep_kernel<4>
                       : n_levels <= 8 ? relmc_hl1_sweep_kernel<8> : relmc_hl1_sweep_kernel<16>;
-    std::vector<double> part, sum((size_t)6 * n_levels, 0.0);
-    double kernel_ms = 0.0;
-    for (int64_t c0 = 0; c0 < n_chains; c0 += per) {
-        const int64_t nc = std::min(per, n_chains - c0), nrec = nc * years_per_chain;
-        (void)hipEventRecord(ctx->ev0, ctx->stream);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
-                           first_chain + (uint64_t)c0, nc, years_per_chain, start, A, X.years.get());
-        if (const int rc = hl1_reduce_queue(ctx, "relmc_hl1_seq_sweep", X.years.get(), nrec, n_levels, X.part.get(), part)) return rc;
-        if (years_host)
-            for (int j = 0; j < n_levels; ++j)
-                HIP_TRY(ctx, hipMemcpyAsync(years_host + (size_t)j * total + c0 * years_per_chain, X.years.get() + (size_t)j * nrec * 3,
-                                            sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
-        if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, "relmc_hl1_seq_sweep: synchronisation failed");
-        kernel_ms += ctx->last_kernel_ms;
-        hl1_reduce_add(part, n_levels, sum.data());
-    }
-    ctx->last_kernel_ms = kernel_ms;
+    std::vector<double> sum((size_t)6 * n_levels, 0.0);
+    const int64_t per = hl1_chunk_items(n_chains, kHl1RecordBudget, (int64_t)years_per_chain * n_levels);      // a chain counts its records of all levels
+    const int rc = hl1_run_records(ctx, "relmc_hl1_seq_sweep", X, n_chains, per, years_per_chain, n_levels, sum.data(),
+        [&](int64_t c0, int64_t nc, int64_t) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
+                               first_chain + (uint64_t)c0, nc, years_per_chain, start, A, X.years.get());
+        },
+        [&](int64_t c0, int64_t, int64_t nrec) -> int {
+            if (years_host)
+                for (int j = 0; j < n_levels; ++j)
+                    HIP_TRY(ctx, hipMemcpyAsync(years_host + (size_t)j * total + c0 * years_per_chain, X.years.get() + (size_t)j * nrec * 3,
+                                                sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
+            return RELMC_OK;
+        },
+        hl1_no_host_step);
+    if (rc) return rc;
     for (int j = 0; j < n_levels; ++j) hl1_acc_fill(acc + j, total, sum.data() + (size_t)6 * j);
     return RELMC_OK;
 }

@@ -8,7 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "relmc_ctx.h"
+#include "relmc_hl1_host.h"
 #include "relmc_storage_kernels.h"
 
 using namespace relmc_host;
@@ -26,8 +26,7 @@ int32_t relmc_hl1_seq_storage(relmc_ctx* ctx, uint64_t seed, uint64_t first_chai
     const std::string who = "relmc_hl1_seq_storage: ";
     if (!ctx) return RELMC_ERR_INVALID;
     if (!ctx->has_hl1_seq) return fail(ctx, RELMC_ERR_NO_CASE, who + "relmc_hl1_seq_load has not been called");
-    if (!acc || n_chains < 0 || years_per_chain < 1 || (start != RELMC_HL1_START_ALL_UP && start != RELMC_HL1_START_STATIONARY))
-        return fail(ctx, RELMC_ERR_INVALID, who + "bad arguments");
+    if (!hl1_chain_args_ok(acc, n_chains, years_per_chain, start)) return fail(ctx, RELMC_ERR_INVALID, who + "bad arguments");
     if (!std::isfinite(scale) || !std::isfinite(shift)) return fail(ctx, RELMC_ERR_INVALID, who + "scale / shift not finite");
     if (n_storage < 0 || n_storage > RELMC_HL1_MAX_STORAGE)
         return fail(ctx, RELMC_ERR_INVALID, who + "n_storage " + std::to_string(n_storage) + " not in 0.." + std::to_string(RELMC_HL1_MAX_STORAGE));
@@ -53,32 +52,23 @@ int32_t relmc_hl1_seq_storage(relmc_ctx* ctx, uint64_t seed, uint64_t first_chai
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     auto& S = ctx->hl1_seq;
     auto& X = ctx->hl1_storage;
-    // the chunks of relmc_hl1_seq, counted over both record rows: at most ~4M year records per launch; a chain's records never depend on
-    // the launch it is in
-    const int64_t max_rec = (int64_t)1 << 22;
-    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(n_chains, max_rec / ((int64_t)years_per_chain * 2)));
-    const int64_t rec_max = per * years_per_chain;                                       // records of one row in a launch
-    HIP_TRY(ctx, X.years.grow((size_t)rec_max * 3 * 2));
-    HIP_TRY(ctx, X.part.grow((size_t)hl1_reduce_blocks(rec_max) * 6 * 2));
-    std::vector<double> part;
     double sum[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    double kernel_ms = 0.0;
-    for (int64_t c0 = 0; c0 < n_chains; c0 += per) {
-        const int64_t nc = std::min(per, n_chains - c0), nrec = nc * years_per_chain;
-        (void)hipEventRecord(ctx->ev0, ctx->stream);
-        hipLaunchKernelGGL(relmc_hl1_storage_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
-                           first_chain + (uint64_t)c0, nc, years_per_chain, start, A, X.years.get());
-        if (const int rc = hl1_reduce_queue(ctx, "relmc_hl1_seq_storage", X.years.get(), nrec, 2, X.part.get(), part)) return rc;
-        if (years_host)
-            HIP_TRY(ctx, hipMemcpyAsync(years_host + c0 * years_per_chain, X.years.get(), sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
-        if (storage_years_host)
-            HIP_TRY(ctx, hipMemcpyAsync(storage_years_host + c0 * years_per_chain, X.years.get() + (size_t)nrec * 3, sizeof(double) * 3 * nrec,
-                                        hipMemcpyDeviceToHost, ctx->stream));
-        if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, who + "synchronisation failed");
-        kernel_ms += ctx->last_kernel_ms;
-        hl1_reduce_add(part, 2, sum);
-    }
-    ctx->last_kernel_ms = kernel_ms;
+    const int64_t per = hl1_chunk_items(n_chains, kHl1RecordBudget, (int64_t)years_per_chain * 2);             // a chain counts its records of both rows
+    const int rc = hl1_run_records(ctx, "relmc_hl1_seq_storage", X, n_chains, per, years_per_chain, 2, sum,
+        [&](int64_t c0, int64_t nc, int64_t) {
+            hipLaunchKernelGGL(relmc_hl1_storage_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
+                               first_chain + (uint64_t)c0, nc, years_per_chain, start, A, X.years.get());
+        },
+        [&](int64_t c0, int64_t, int64_t nrec) -> int {
+            if (years_host)
+                HIP_TRY(ctx, hipMemcpyAsync(years_host + c0 * years_per_chain, X.years.get(), sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
+            if (storage_years_host)
+                HIP_TRY(ctx, hipMemcpyAsync(storage_years_host + c0 * years_per_chain, X.years.get() + (size_t)nrec * 3, sizeof(double) * 3 * nrec,
+                                            hipMemcpyDeviceToHost, ctx->stream));
+            return RELMC_OK;
+        },
+        hl1_no_host_step);
+    if (rc) return rc;
     acc->years = n_chains * years_per_chain;
     acc->sum_lole = sum[0]; acc->sum_eue = sum[1]; acc->sum_lolf = sum[2]; acc->sum_lole2 = sum[3]; acc->sum_eue2 = sum[4]; acc->sum_lolf2 = sum[5];
     acc->sum_served = sum[6]; acc->sum_discharged = sum[7]; acc->sum_charged = sum[8];

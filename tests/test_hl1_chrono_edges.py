@@ -296,7 +296,7 @@ def test_sweep_two_launches(engine):
     _load(engine, cap, mttf, mttr, load)
     N, Y = 4100, 64
     levels, wh = E.edge_levels(16), E.edge_withheld(6)
-    per = (1 << 22) // (Y * len(levels))
+    per = E.RECORD_BUDGET // (Y * len(levels))
     assert per == 4096 and per < N < 2 * per
     acc, yr = _sweep(engine, 8, 0, N, Y, SEQ.STATIONARY, levels, wh)
     w0, w1 = per - 3, per + 3
@@ -321,7 +321,7 @@ def test_storage_two_launches(engine):
     _load(engine, cap, mttf, mttr, load)
     N, Y = 2100, 1000
     st = E.edge_storages(cap)
-    per = (1 << 22) // (Y * 2)
+    per = E.RECORD_BUDGET // (Y * 2)
     assert per == 2097 and per < N < 2 * per
     acc, yr, sy = _storage(engine, 8, 0, N, Y, SEQ.STATIONARY, st)
     w0, w1 = per - 3, per + 3
@@ -348,7 +348,7 @@ def test_events_two_launches(engine):
     cap, mttf, mttr, load = E.seq_fleet(6, 24)
     _load(engine, cap, mttf, mttr, load)
     N, Y = 4300, 1000
-    per = (1 << 22) // Y
+    per = E.RECORD_BUDGET // Y
     assert per == 4194 and per < N < 2 * per
     args = (Y, SEQ.STATIONARY)
     count, hist0, none = _events(engine, 8, 0, N, *args, 0)          # no list: the summary alone, and the size of the list

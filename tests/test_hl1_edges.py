@@ -234,8 +234,8 @@ def test_seq_two_launches(engine):
     engine._check(_seq_load(engine.L, engine._h, cap, mttf, mttr, load), "relmc_hl1_seq_load")
     engine._hl1_seq_loaded = None
     N, Y = 4300, 1000
-    per = (1 << 22) // Y
-    assert N * Y > 1 << 22 and per < N
+    per = E.RECORD_BUDGET // Y
+    assert N * Y > E.RECORD_BUDGET and per < N
     acc, yr = _seq(engine, 8, 0, N, Y, SEQ.STATIONARY)
     w0, w1 = per - 3, per + 3
     model = np.stack(SEQ.interval_model(8, range(w0, w1), cap, mttf, mttr, load, Y, SEQ.STATIONARY), axis=1)
@@ -336,7 +336,7 @@ def test_area_two_launches(engine):
     engine._check(_area_load(engine.L, engine._h, units, cap, mttf, mttr, loads, ties), "relmc_hl1_area_load")
     engine._hl1_area_loaded = None
     N, Y = 4300, 1000
-    per = (1 << 22) // Y
+    per = E.RECORD_BUDGET // Y
     pol = (AREA.STATIONARY, AREA.INTERCONNECTED, AREA.MAX_FLOW)
     acc, yr = _area(engine, 3, 6, 0, N, Y, *pol)
     w0, w1 = per - 2, per + 2

@@ -20,6 +20,7 @@ if ROOT not in sys.path:
 from oracle.pyoracle import philox4x32_10  # noqa: E402
 
 FOR_EXTREMES = (0.0, 2.0 ** -32, 0.5, 1.0 - 2.0 ** -32, 1.0)
+RECORD_BUDGET = 1 << 22              # kHl1RecordBudget (csrc/relmc_hl1_host.h): the year records a launch of the chain models holds at most
 
 
 def unit_order_sum(cap, up):

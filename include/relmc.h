@@ -482,6 +482,70 @@ int32_t relmc_hl1_seq_storage(relmc_ctx* ctx, uint64_t seed, uint64_t first_chai
                               relmc_hl1_storage_acc* acc, relmc_hl1_seq_year* years_host,
                               relmc_hl1_storage_year* storage_years_host);
 
+/* ---- weather-year wind and solar resources on the HL1 sequential chronology, with storage (an extension beyond the reference) ---- */
+/* Wind and solar are not Markov units: their output is an hourly profile that differs from weather year to weather year and is correlated
+ * with the load of the same weather year.  A weather library holds n_weather such years, each with the hourly output of up to 8 resources
+ * and, optionally, its own load curve; every chain year of a run draws one weather year, the fleet of relmc_hl1_seq_load fails and
+ * repairs as ever, and the storages of relmc_hl1_seq_storage charge from the surplus that now includes the resources' output.  The
+ * resources themselves never fail.
+ * Chronology   relmc_hl1_seq's, word for word (model of relmc_hl1_seq_load, draws (seed, chain, k | 0x40000000, event), start rules, no FMA,
+ *              DOWN on steps [ceil(T_odd), ceil(T_even))): under one seed, chain c sees exactly the fleet history of chain c of relmc_hl1_seq.
+ * Weather year of chain year y (0-based) of chain c, w in 0 .. n_weather - 1:
+ *              RELMC_HL1_VAR_PICK_RANDOM  w = ((uint64)x * n_weather) >> 32, x = word 0 of philox4x32_10(ctr = (c_lo, c_hi,
+ *                                         RELMC_HL1_VAR_TAG, y), key = (seed_lo, seed_hi)): integer arithmetic, exact on every host
+ *              RELMC_HL1_VAR_PICK_CYCLE   w = (c * years_per_chain + y) mod n_weather in unsigned 64-bit arithmetic
+ *              w depends on nothing else, so not on how a chain range is split into calls.
+ * Load         base(w, h) = load_mw[w][h] when the library has load curves, else relmc_hl1_seq_load's load[h];
+ *              L = scale * base + shift, the product and the sum each rounded (relmc_hl1_seq_sweep's rule).
+ * Capacity     cap = sum over the UP units in ascending order, as everywhere; then for r = 0 .. n_resources - 1 ascending
+ *              cap = cap + resource_scale[r] * output_mw[w][r][h], the product and the sum each rounded (no contraction).  A scale of 0
+ *              withholds a resource: it adds + 0.0, which is exact.
+ * Storages     relmc_hl1_seq_storage's step rule, verbatim, with this cap and this L: the storages charge from the surplus, which includes
+ *              the resources' output.  The state of charge is carried over the year boundary; the next year may be another weather year.
+ * Year records, acc, the split and repeat guarantees and the launch chunk rule are relmc_hl1_seq_storage's (two record rows; a chain
+ *              counts 2 * years_per_chain records).
+ * Consequences
+ *   1. With n_resources == 0 or every resource_scale == 0, and no load curves in the library, both record rows are bitwise those of
+ *      relmc_hl1_seq_storage at (scale, shift, storages), under either pick; with n_storage == 0 and (1.0, 0.0) in addition they are
+ *      bitwise relmc_hl1_seq's.
+ *   2. With n_weather == 1, load curve X and no effective resource, the records are bitwise relmc_hl1_seq_storage's on the model loaded
+ *      with X.
+ *   3. When capacities, loads and outputs are all multiples of 2^-k of moderate size, so that every sum is exact, one resource with the
+ *      constant output p gives bitwise the records of relmc_hl1_seq_sweep's level (scale, shift - p, fleet 0).
+ *   4. Without storage, the sampled LOLE and EUE are non-increasing in every resource_scale[r] and non-decreasing in shift, chain by
+ *      chain: the fleet history and the weather years are the same. */
+#define RELMC_HL1_VAR_MAX_RESOURCES 8
+#define RELMC_HL1_VAR_MAX_WEATHER   256
+#define RELMC_HL1_VAR_TAG           0x60000000u   /* counter word 2 of a weather draw; 0x80000000, 0x40000000, 0x50000000, 0x20000000 are the other streams' */
+#define RELMC_HL1_VAR_PICK_RANDOM   0
+#define RELMC_HL1_VAR_PICK_CYCLE    1
+/* The weather library: n_weather in 1 .. RELMC_HL1_VAR_MAX_WEATHER, n_resources in 0 .. RELMC_HL1_VAR_MAX_RESOURCES, nhours >= 1.  It
+ * lives in a slot of its own: no other load call disturbs it, and it disturbs none.
+ *   output_mw  [n_weather][n_resources][nhours], finite and >= 0; may be NULL iff n_resources == 0
+ *   load_mw    optional [n_weather][nhours], finite: the load curve of each weather year
+ * RELMC_ERR_INVALID, with relmc_last_error naming the weather year, the resource and the hour of the first bad value, for a value out of
+ * these rules; RELMC_ERR_UNSUPPORTED for n_weather * max(n_resources, 1) * nhours >= 2^31 (the kernel indexes the library in 32 bits).
+ * A refused call changes nothing. */
+int32_t relmc_hl1_var_load(relmc_ctx* ctx, int32_t n_weather, int32_t n_resources, int32_t nhours,
+                           const double* output_mw, const double* load_mw);
+/* resource_scale: finite and >= 0, entries at or above n_resources must be 0; pick: RELMC_HL1_VAR_PICK_* */
+typedef struct { double resource_scale[RELMC_HL1_VAR_MAX_RESOURCES]; double scale, shift; int32_t pick, reserved; } relmc_hl1_var_opts;  /* 88 bytes, reserved = 0 */
+/* chains [first_chain, first_chain + n_chains), each years_per_chain consecutive years, of the fleet loaded by relmc_hl1_seq_load against
+ * the weather loaded by relmc_hl1_var_load (RELMC_ERR_NO_CASE before either call; RELMC_ERR_INVALID, with a message that gives both
+ * values, when their nhours differ).  RELMC_ERR_INVALID, with relmc_last_error naming the field, for: anything relmc_hl1_seq_storage
+ * refuses; a null opts; a non-finite or negative resource_scale; a non-zero resource_scale at or above n_resources; pick not 0 or 1;
+ * reserved != 0.  A refused call changes nothing; n_chains == 0 zeroes the outputs.
+ *   years_host, storage_years_host  optional [n_chains * years_per_chain], chain-major
+ *   weather_host                    optional [n_chains * years_per_chain], chain-major: the weather year of every chain year */
+int32_t relmc_hl1_var_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain,
+                          int32_t start, const relmc_hl1_var_opts* opts, int32_t n_storage, const relmc_hl1_storage* storage,
+                          relmc_hl1_storage_acc* acc, relmc_hl1_seq_year* years_host,
+                          relmc_hl1_storage_year* storage_years_host, int32_t* weather_host);
+/* Host only, touches no device: the weather year of chain year `year` (0-based) of chain `chain`, or -1 for year < 0,
+ * years_per_chain < 1, n_weather outside 1 .. RELMC_HL1_VAR_MAX_WEATHER or pick not 0 or 1. */
+int32_t relmc_hl1_var_weather_year(uint64_t seed, uint64_t chain, int32_t year, int32_t years_per_chain, int32_t n_weather,
+                                   int32_t pick);
+
 /* ---- HL1 sequential chronology with derated states: three-state Markov units (an extension beyond the reference) ---- */
 /* A large thermal unit that loses a feed pump or a mill runs at part load for days: the textbook third state (Billinton & Allan), with
  * its own capacity and transition rates.  The reference's units, and every other HL1 track here, are two-state.

@@ -599,6 +599,62 @@ function run_sequential_storage(eng::Engine, capacity::Vector{Float64}, mttf::Ve
             years=yrs, storage_years=sty)
 end
 
+"relmc_hl1_var_opts (include/relmc.h, 88 bytes): the options of relmc_hl1_var_seq; resource_scale finite and >= 0 (0 beyond the library's resources), pick = HL1_VAR_PICK[...], reserved = 0"
+struct Hl1VarOpts
+    resource_scale::NTuple{8,Cdouble}; scale::Cdouble; shift::Cdouble; pick::Int32; reserved::Int32
+end
+const HL1_VAR_MAX_RESOURCES = 8                                            # RELMC_HL1_VAR_MAX_RESOURCES
+const HL1_VAR_MAX_WEATHER = 256                                            # RELMC_HL1_VAR_MAX_WEATHER
+const HL1_VAR_PICK = Dict(:random => Int32(0), :cycle => Int32(1))         # RELMC_HL1_VAR_PICK_*
+
+# Layout of the options, kept apart from LAYOUT (tests/test_hl1_variable_host.py compares it with the C compiler's and with ctypes)
+const LAYOUT_HL1_VAR = [
+    ("relmc_hl1_var_opts", 88, [("resource_scale", 0), ("scale", 64), ("shift", 72), ("pick", 80), ("reserved", 84)]),
+]
+
+"""
+run_sequential_variable (an extension beyond the reference): run_sequential_mc's chronology, same arguments and same chains under one
+seed, with weather-driven resources and up to 8 energy storages.  output_mw[hour, resource, weather year] (column-major: the C ABI's
+[n_weather][n_resources][nhours]) holds the hourly output of every resource in every weather year, weather_load[hour, weather year]
+optionally each weather year's own load curve.  Every chain year draws a weather year (pick = :random or :cycle); a step's capacity is
+the fleet's plus resource_scale[r] * output, its load scale * base + shift; the storages charge from the surplus, the resources' output
+included.  Returns run_sequential_storage's fields and the weather year (0-based) of every simulated year.
+"""
+function run_sequential_variable(eng::Engine, capacity::Vector{Float64}, mttf::Vector{Float64}, mttr::Vector{Float64},
+                                 hourly_load::Vector{Float64}, output_mw::Array{Float64,3}, years::Integer;
+                                 weather_load::Union{Nothing,Matrix{Float64}}=nothing, storages::Vector{Hl1Storage}=Hl1Storage[],
+                                 resource_scale::Vector{Float64}=ones(size(output_mw, 2)), scale::Real=1.0, shift::Real=0.0,
+                                 pick::Symbol=:random, seed::Integer=1, chains::Integer=1, start::Symbol=:all_up)
+    (years >= 1 && chains >= 1 && years % chains == 0) || throw(ArgumentError("years must be a positive multiple of chains"))
+    nh, nres, nw = size(output_mw)
+    nh == length(hourly_load) || throw(ArgumentError("output_mw has $nh hours, the load curve $(length(hourly_load))"))
+    nres <= HL1_VAR_MAX_RESOURCES || throw(ArgumentError("at most $HL1_VAR_MAX_RESOURCES resources"))
+    1 <= nw <= HL1_VAR_MAX_WEATHER || throw(ArgumentError("1 to $HL1_VAR_MAX_WEATHER weather years"))
+    length(resource_scale) == nres || throw(ArgumentError("one resource_scale per resource"))
+    weather_load === nothing || size(weather_load) == (nh, nw) || throw(ArgumentError("weather_load must be [hours, weather years]"))
+    length(storages) <= HL1_MAX_STORAGE || throw(ArgumentError("at most $HL1_MAX_STORAGE storages"))
+    check(ccall((:relmc_hl1_seq_load, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}),
+                eng.h, length(capacity), capacity, mttf, mttr, length(hourly_load), hourly_load), eng.h, "relmc_hl1_seq_load")
+    check(ccall((:relmc_hl1_var_load, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}),
+                eng.h, nw, nres, nh, nres == 0 ? C_NULL : output_mw, weather_load === nothing ? C_NULL : weather_load), eng.h, "relmc_hl1_var_load")
+    opts = Ref(Hl1VarOpts(ntuple(r -> r <= nres ? resource_scale[r] : 0.0, 8), Float64(scale), Float64(shift), HL1_VAR_PICK[pick], Int32(0)))
+    acc = Hl1StorageAcc()
+    yrs = Vector{Hl1SeqYear}(undef, years); sty = Vector{Hl1StorageYear}(undef, years); wy = Vector{Int32}(undef, years)
+    check(ccall((:relmc_hl1_var_seq, LIB), Int32,
+                (Ptr{Cvoid}, UInt64, UInt64, Int64, Int32, Int32, Ref{Hl1VarOpts}, Int32, Ptr{Hl1Storage}, Ref{Hl1StorageAcc}, Ptr{Hl1SeqYear},
+                 Ptr{Hl1StorageYear}, Ptr{Int32}),
+                eng.h, seed, 0, chains, years ÷ chains, HL1_START[start], opts, length(storages),
+                isempty(storages) ? C_NULL : storages, acc, yrs, sty, wy), eng.h, "relmc_hl1_var_seq")
+    return (lole_hours_yr=acc.sum_lole / years, eue_mwh_yr=acc.sum_eue / years, lolf_occ_yr=acc.sum_lolf / years,
+            served_hours_yr=acc.sum_served / years, discharged_mwh_yr=acc.sum_discharged / years, charged_mwh_yr=acc.sum_charged / years,
+            years=yrs, storage_years=sty, year_weather=wy)
+end
+
+"The weather year (0-based) of chain year `year` (0-based) of chain `chain` (relmc_hl1_var_weather_year: host only, no engine needed)"
+weather_year(seed::Integer, chain::Integer, year::Integer, years_per_chain::Integer, n_weather::Integer; pick::Symbol=:random) =
+    ccall((:relmc_hl1_var_weather_year, LIB), Int32, (UInt64, UInt64, Int32, Int32, Int32, Int32), seed, chain, year, years_per_chain, n_weather,
+          HL1_VAR_PICK[pick])
+
 "relmc_hl1_ms_unit (include/relmc.h, 64 bytes): a three-state unit, UP / DERATED / DOWN: capacities in MW, per state the mean holding time in hours and the probability of the first-listed destination (from UP: DOWN, DERATED; from DERATED: UP, DOWN; from DOWN: UP, DERATED)"
 struct Hl1MsUnit
     capacity_mw::Cdouble; derated_mw::Cdouble; mean_h::NTuple{3,Cdouble}; first_p::NTuple{3,Cdouble}

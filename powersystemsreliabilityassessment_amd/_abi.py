@@ -156,6 +156,17 @@ class Hl1StorageAcc(C.Structure):         # relmc_hl1_storage_acc
                 ("sum_served2", C.c_double), ("sum_discharged2", C.c_double), ("sum_charged2", C.c_double)]
 
 
+HL1_VAR_MAX_RESOURCES = 8                 # RELMC_HL1_VAR_MAX_RESOURCES
+HL1_VAR_MAX_WEATHER = 256                 # RELMC_HL1_VAR_MAX_WEATHER
+HL1_VAR_TAG = 0x60000000                  # RELMC_HL1_VAR_TAG
+HL1_VAR_PICK_RANDOM, HL1_VAR_PICK_CYCLE = 0, 1     # RELMC_HL1_VAR_PICK_*
+
+
+class Hl1VarOpts(C.Structure):            # relmc_hl1_var_opts (88 bytes)
+    _fields_ = [("resource_scale", C.c_double * HL1_VAR_MAX_RESOURCES), ("scale", C.c_double), ("shift", C.c_double),
+                ("pick", C.c_int32), ("reserved", C.c_int32)]
+
+
 HL1_MS_BRANCH_TAG = 0x50000000            # RELMC_HL1_MS_BRANCH_TAG
 HL1_MS_MAX_HOURS = 1 << 30                # RELMC_HL1_MS_MAX_HOURS
 

@@ -703,7 +703,90 @@ int32_t relmc_hl1_area_sweep(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain
                              const uint32_t* withheld, const uint8_t* tie_scaled, relmc_hl1_seq_acc* acc,
                              relmc_hl1_seq_year* years_host);
 
-/* ---- HL1 planning model: maintenance, energy-limited units, LFU (generating_adequancy_comparative.jl:15-120, tail_risk.jl:12-91) ---- */
+/* ---- weather-year resources and storages in the areas of the multi-area chronology (an extension beyond the reference) ---- */
+/* What wind, solar and a battery in area B are worth to B and to its neighbours across a limited tie exists only on the multi-area
+ * chronology: subtracting a profile from an area's load by hand gives one weather year, no sampling and no storage.  A weather library
+ * of the areas holds n_weather years, each with the hourly output of up to 8 resources, every one placed in an area, and, optionally, a
+ * load curve of every area; up to 8 storages, each placed in an area, are given in the call.  Resources and storages never fail.
+ * Per step, every operation is one correctly rounded fp64 operation (no contraction, no FMA):
+ *   1. Chronology    relmc_hl1_area's, word for word: units are global component k < 128, ties component 128 + t, the same start rules.
+ *                    Under one seed, chain c sees exactly the unit and tie history of chain c of relmc_hl1_area.
+ *   2. Weather year  of chain year y: relmc_hl1_var_weather_year's function, verbatim, with the same tag RELMC_HL1_VAR_TAG.  A one-area
+ *                    run therefore sees relmc_hl1_var_seq's weather.
+ *   3. Load          L_a = load_scale[a] * base_a(w, h) + load_shift[a], the product and the sum each rounded; base_a(w, h) =
+ *                    load_mw[w][a][h] when the library has load curves, else relmc_hl1_area_load's load[a][h].
+ *   4. Capacity      cap_a = sum of area a's UP units in ascending order; then, for r ascending over the resources with
+ *                    resource_area[r] == a, cap_a = cap_a + resource_scale[r] * output_mw[w][r][h], the product and the sum each rounded.
+ *                    The margin is m_a = cap_a - L_a.
+ *   5. Transfers first.  ISOLATED: none.  INTERCONNECTED: relmc_hl1_area's transfer solve on these margins, unchanged (both flow rules,
+ *                    the 1e-4 thresholds, the 4096 guard, T from the UP ties), which leaves the post-transfer margins m'_a.
+ *   6. Storage last, and local.  In every area a, its storages in array order apply relmc_hl1_seq_storage's step rule, verbatim:
+ *                    m'_a < 0: need = -m'_a, the storages discharge while need is left; the area's deficit is what is left.
+ *                    m'_a > 0: surplus = m'_a, the storages charge from it.          m'_a == 0: nothing happens.
+ *                    A state of charge starts at soc0_mwh in every chain and is carried across steps and years.
+ *      THE POLICY: energy-limited resources are used after the ties.  A storage neither exports nor charges from imports beyond what
+ *                    step 5 left in its area; the transfer solve never sees a state of charge.  A pooled or export policy is not built.
+ *   7. Flags and records.  Area a has a loss hour iff a deficit > 0 is left after step 6; the system has one iff any area has, its
+ *                    deficit the sum in area order.  Loss hours, EUE and events of every row follow relmc_hl1_area's rules.  A second
+ *                    record of every row is a relmc_hl1_storage_year: served_hours counts the steps on which the area was short after
+ *                    step 5 and nothing is left after step 6 (the system: some area was short after step 5, none is after step 6);
+ *                    discharged_mwh / charged_mwh are the step sums of x / y over the area's storages in order (the system: the areas'
+ *                    step sums in area order).  A year's sums are taken in relmc_hl1_area's fixed order: lane partials, then the butterfly.
+ * Consequences
+ *   C1. No effective resource (none, or every scale 0), no curves in the library, no storage, load_scale 1 and load_shift 0: the loss
+ *       records are bitwise relmc_hl1_area(policy, flow)'s, with and without tie-outage data; with other scales and shifts they are
+ *       bitwise relmc_hl1_area's on the model loaded with the curves load_scale[a] * load_a[h] + load_shift[a].
+ *   C2. One area, no ties: both records of area 0 and of the system are bitwise relmc_hl1_var_seq's two records with the same fleet,
+ *       library, scales and storages at (scale, shift) = (load_scale[0], load_shift[0]), under both picks.
+ *   C3. ISOLATED: area a's two records are bitwise relmc_hl1_var_seq's on the pooled fleet with the other areas' capacities at 0, area
+ *       a's curve(s), the other areas' resources at scale 0 and only area a's storages, in order.  INTERCONNECTED with every tie
+ *       capacity 0 is bitwise ISOLATED.
+ *   C4. For every row and year, served_hours + lole equals the lole of the same call with n_storage == 0, exactly: storage comes after
+ *       the transfers and never feeds back into them.
+ *   C5. Storages that cannot act (discharge_mw == 0, or energy_mwh == 0, or soc0_mwh == 0 together with charge_mw == 0) give loss
+ *       records bitwise those of n_storage == 0 and served_hours == discharged_mwh == 0.  charged_mwh is 0 as well, except that a
+ *       storage with discharge_mw == 0 and room left still charges by the step rule (as in relmc_hl1_seq_storage) and never delivers.
+ *   C6. On multiples of 2^-k of moderate size, so that every sum is exact, one resource in area a with the constant output p gives
+ *       bitwise the records of the same call without it at load_shift[a] - p. */
+/* The weather library of the areas: n_areas in 1 .. RELMC_AREA_MAX, n_weather in 1 .. RELMC_HL1_VAR_MAX_WEATHER, n_resources in
+ * 0 .. RELMC_HL1_VAR_MAX_RESOURCES, nhours >= 1.  It lives in a slot of its own: no other load call disturbs it, and it disturbs none.
+ *   resource_area  [n_resources], 0-based, in 0 .. n_areas - 1; may be NULL iff n_resources == 0
+ *   output_mw      [n_weather][n_resources][nhours], finite and >= 0; may be NULL iff n_resources == 0
+ *   load_mw        optional [n_weather][n_areas][nhours], finite: the load curve of every area in every weather year
+ * RELMC_ERR_INVALID, with relmc_last_error naming the weather year, the resource or area, and the hour of the first bad value, for a value
+ * out of these rules; RELMC_ERR_UNSUPPORTED for more than RELMC_AREA_MAX areas and for n_weather * max(n_resources, n_areas, 1) * nhours
+ * >= 2^31 (the kernel indexes the library in 32 bits).  A refused call changes nothing. */
+int32_t relmc_hl1_area_var_load(relmc_ctx* ctx, int32_t n_areas, int32_t n_weather, int32_t n_resources, const int32_t* resource_area,
+                                int32_t nhours, const double* output_mw, const double* load_mw);
+/* resource_scale: finite and >= 0, 0 at or above n_resources; load_scale / load_shift: finite, 1 / 0 at or above n_areas; policy
+ * RELMC_HL1_AREA_*, flow RELMC_HL1_AREA_FLOW_* (read under INTERCONNECTED only, but always checked), pick RELMC_HL1_VAR_PICK_* */
+typedef struct {
+    double resource_scale[RELMC_HL1_VAR_MAX_RESOURCES];
+    double load_scale[RELMC_AREA_MAX], load_shift[RELMC_AREA_MAX];
+    int32_t policy, flow, pick, reserved;
+} relmc_hl1_area_var_opts;   /* 208 bytes, reserved = 0 */
+/* a storage of relmc_hl1_seq_storage (the same field rules) in the 0-based area `area` */
+typedef struct { relmc_hl1_storage s; int32_t area, reserved; } relmc_hl1_area_storage;   /* 56 bytes, reserved = 0 */
+/* chains [first_chain, first_chain + n_chains), each years_per_chain consecutive years, of the model of relmc_hl1_area_load, and of
+ * relmc_hl1_area_tie_outages' data when set and the policy is INTERCONNECTED (exactly as relmc_hl1_area), against the library of
+ * relmc_hl1_area_var_load.  RELMC_ERR_NO_CASE before either load call; RELMC_ERR_INVALID, with a message that gives both values, when
+ * n_areas or nhours of the two differ or a resource_area is out of range for the model.  RELMC_ERR_INVALID, naming the storage and the
+ * field, for: anything relmc_hl1_area refuses; a null opts; a scale or shift out of the rules above; policy, flow or pick not 0 or 1;
+ * reserved != 0; n_storage outside 0 .. RELMC_HL1_MAX_STORAGE (all areas together); a storage's area out of range; anything
+ * relmc_hl1_seq_storage refuses in a storage's fields.  A refused call changes nothing; n_chains == 0 zeroes the outputs.
+ *   storage             [n_storage]; the storages of one area act in this array's order
+ *   acc                 [n_areas + 1], row n_areas = the system
+ *   years_host          optional [n_chains * years_per_chain][n_areas + 1], chain-major
+ *   storage_years_host  optional [n_chains * years_per_chain][n_areas + 1], chain-major
+ *   weather_host        optional [n_chains * years_per_chain], chain-major: the weather year of every chain year
+ * The split and repeat guarantees are relmc_hl1_area's.  Long chain ranges go in launches of at most ~4M year records, a chain counting
+ * 2 * (n_areas + 1) * years_per_chain; relmc_last_kernel_ms covers every launch. */
+int32_t relmc_hl1_area_var(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain,
+                           int32_t start, const relmc_hl1_area_var_opts* opts, int32_t n_storage,
+                           const relmc_hl1_area_storage* storage, relmc_hl1_storage_acc* acc, relmc_hl1_seq_year* years_host,
+                           relmc_hl1_storage_year* storage_years_host, int32_t* weather_host);
+
+/* ---- HL1 planning model: maintenance, energy-limited units, LFU(generating_adequancy_comparative.jl:15-120, tail_risk.jl:12-91) ---- */
 /* Year y is the global index first_year + i; hour h is 0-based; every year starts with every ELU's energy at 0; years are independent.
  * Block b of hour h of year y: philox4x32_10(ctr = (y_lo, y_hi, 0x20000000 | h, b), key = (seed_lo, seed_hi)); word j = word j & 3 of
  * block j >> 2 (the 0x20000000 tag keeps these draws apart from the 0x40000000 / 0x80000000 chronologies and the non-sequential draws).

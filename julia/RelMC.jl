@@ -829,6 +829,72 @@ const LAYOUT_HL1_AREA_SWEEP = [
     ("relmc_hl1_area_level", 144, [("load_scale", 0), ("load_shift", 64), ("tie_scale", 128), ("fleet", 136), ("reserved", 140)]),
 ]
 
+"relmc_hl1_area_var_opts (include/relmc.h, 208 bytes): the options of relmc_hl1_area_var; resource_scale finite and >= 0 (0 beyond the library's resources), load_scale / load_shift per area (1 / 0 beyond the model's areas), policy = HL1_AREA_POLICY[...], flow = HL1_AREA_FLOW[...], pick = HL1_VAR_PICK[...], reserved = 0"
+struct Hl1AreaVarOpts
+    resource_scale::NTuple{8,Cdouble}; load_scale::NTuple{8,Cdouble}; load_shift::NTuple{8,Cdouble}; policy::Int32; flow::Int32; pick::Int32; reserved::Int32
+end
+"relmc_hl1_area_storage (include/relmc.h, 56 bytes): the storage `s` in the 0-based area `area`; reserved = 0"
+struct Hl1AreaStorage
+    s::Hl1Storage; area::Int32; reserved::Int32
+end
+
+# Layout of the two structs, kept apart from LAYOUT (tests/test_hl1_area_variable_host.py compares it with the C compiler's and with ctypes)
+const LAYOUT_HL1_AREA_VAR = [
+    ("relmc_hl1_area_var_opts", 208, [("resource_scale", 0), ("load_scale", 64), ("load_shift", 128), ("policy", 192), ("flow", 196), ("pick", 200), ("reserved", 204)]),
+    ("relmc_hl1_area_storage", 56, [("s", 0), ("area", 48), ("reserved", 52)]),
+]
+
+"""
+run_area_variable (an extension beyond the reference): the chronology of the model that run_fast_sequential_simulation loaded last on
+this engine (tie outages included), same chains under one seed, with weather-year resources and storages in the areas.
+output_mw[hour, resource, weather year] (column-major: the C ABI's [n_weather][n_resources][nhours]) holds the hourly output of every
+resource, resource_area[r] its 1-based area, weather_load[hour, area, weather year] optionally every area's load curve of every weather
+year; storages are (1-based area, Hl1Storage) pairs, those of one area acting in the order given.  Per step the areas help each other
+over the ties first; each area's storages then serve what is left of its deficit or charge from what is left of its surplus.  Returns
+per row (areas, then the system) LOLE, EUE, LOLF, served hours and MWh discharged / charged per year, the per-year records
+(years x (n_areas + 1) x 3, twice) and the weather year (0-based) of every simulated year.
+"""
+function run_area_variable(eng::Engine, n_areas::Integer, policy::Symbol, output_mw::Array{Float64,3}, resource_area::Vector{<:Integer},
+                           n_years::Integer; weather_load::Union{Nothing,Array{Float64,3}}=nothing,
+                           storages::Vector{<:Tuple{Integer,Hl1Storage}}=Tuple{Int,Hl1Storage}[],
+                           resource_scale::Vector{Float64}=ones(size(output_mw, 2)), load_scale::Vector{Float64}=ones(n_areas),
+                           load_shift::Vector{Float64}=zeros(n_areas), pick::Symbol=:random, flow::Symbol=:reference, seed::Integer=1,
+                           chains::Integer=1, start::Symbol=:all_up)
+    (n_years >= 1 && chains >= 1 && n_years % chains == 0) || throw(ArgumentError("n_years must be a positive multiple of chains"))
+    1 <= n_areas <= AREA_MAX || throw(ArgumentError("1..$AREA_MAX areas"))
+    nh, nres, nw = size(output_mw)
+    nres <= HL1_VAR_MAX_RESOURCES || throw(ArgumentError("at most $HL1_VAR_MAX_RESOURCES resources"))
+    1 <= nw <= HL1_VAR_MAX_WEATHER || throw(ArgumentError("1 to $HL1_VAR_MAX_WEATHER weather years"))
+    (length(resource_area) == nres && all(1 <= a <= n_areas for a in resource_area)) || throw(ArgumentError("one 1-based area per resource"))
+    length(resource_scale) == nres || throw(ArgumentError("one resource_scale per resource"))
+    (length(load_scale) == n_areas && length(load_shift) == n_areas) || throw(ArgumentError("one load scale and shift per area"))
+    weather_load === nothing || size(weather_load) == (nh, n_areas, nw) || throw(ArgumentError("weather_load must be [hours, areas, weather years]"))
+    length(storages) <= HL1_MAX_STORAGE || throw(ArgumentError("at most $HL1_MAX_STORAGE storages"))
+    all(1 <= s[1] <= n_areas for s in storages) || throw(ArgumentError("a storage's area must be one of 1..$n_areas"))
+    check(ccall((:relmc_hl1_area_var_load, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Int32}, Int32, Ptr{Cdouble}, Ptr{Cdouble}),
+                eng.h, n_areas, nw, nres, nres == 0 ? C_NULL : Int32.(resource_area .- 1), nh, nres == 0 ? C_NULL : output_mw,
+                weather_load === nothing ? C_NULL : weather_load), eng.h, "relmc_hl1_area_var_load")
+    opts = Ref(Hl1AreaVarOpts(ntuple(r -> r <= nres ? resource_scale[r] : 0.0, 8), ntuple(a -> a <= n_areas ? load_scale[a] : 1.0, 8),
+                              ntuple(a -> a <= n_areas ? load_shift[a] : 0.0, 8), HL1_AREA_POLICY[policy], HL1_AREA_FLOW[flow],
+                              HL1_VAR_PICK[pick], Int32(0)))
+    st = [Hl1AreaStorage(s[2], Int32(s[1] - 1), Int32(0)) for s in storages]
+    rows = n_areas + 1
+    raw = zeros(UInt8, 104 * rows)                                            # relmc_hl1_storage_acc[rows], contiguous
+    yrs = Vector{Hl1SeqYear}(undef, n_years * rows); sty = Vector{Hl1StorageYear}(undef, n_years * rows); wy = Vector{Int32}(undef, n_years)
+    check(ccall((:relmc_hl1_area_var, LIB), Int32,
+                (Ptr{Cvoid}, UInt64, UInt64, Int64, Int32, Int32, Ref{Hl1AreaVarOpts}, Int32, Ptr{Hl1AreaStorage}, Ptr{UInt8}, Ptr{Hl1SeqYear},
+                 Ptr{Hl1StorageYear}, Ptr{Int32}),
+                eng.h, seed, 0, chains, n_years ÷ chains, HL1_START[start], opts, length(st), isempty(st) ? C_NULL : st, raw, yrs, sty, wy),
+          eng.h, "relmc_hl1_area_var")
+    sums = reshape(reinterpret(Float64, raw), 13, rows)                       # rows 2 .. 4: sum_lole, sum_eue, sum_lolf; 8 .. 10: served, discharged, charged
+    Y = reshape(yrs, rows, n_years); S = reshape(sty, rows, n_years)
+    return (lole=sums[2, :] ./ n_years, eue=sums[3, :] ./ n_years, lolf=sums[4, :] ./ n_years,
+            served_hours=sums[8, :] ./ n_years, discharged_mwh=sums[9, :] ./ n_years, charged_mwh=sums[10, :] ./ n_years,
+            year_indices=[getfield(Y[r, t], f) for t in 1:n_years, r in 1:rows, f in (:lole, :eue, :lolf)],
+            year_storage=[getfield(S[r, t], f) for t in 1:n_years, r in 1:rows, f in (:served_hours, :discharged_mwh, :charged_mwh)],
+            year_weather=wy)
+end
+
 # Structs the HL1 planning wrappers pass (the planning calls reuse the sequential model's records; no struct of their own), checked
 # against the C compiler by tests/test_hl1_plan_host.py
 const LAYOUT_HL1_PLAN = [

@@ -204,6 +204,16 @@ class Hl1AreaLevel(C.Structure):                   # relmc_hl1_area_level (144 b
                 ("fleet", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Hl1AreaVarOpts(C.Structure):                 # relmc_hl1_area_var_opts (208 bytes)
+    _fields_ = [("resource_scale", C.c_double * HL1_VAR_MAX_RESOURCES), ("load_scale", C.c_double * AREA_MAX),
+                ("load_shift", C.c_double * AREA_MAX), ("policy", C.c_int32), ("flow", C.c_int32), ("pick", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class Hl1AreaStorage(C.Structure):                 # relmc_hl1_area_storage (56 bytes): `area` is 0-based
+    _fields_ = [("s", Hl1Storage), ("area", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SeqOpts(C.Structure):
     _fields_ = [
         ("cov_threshold", C.c_double), ("max_years", C.c_int32), ("batch_years", C.c_int32), ("seed", C.c_uint64),

@@ -25,6 +25,7 @@ EXPORTS = [
     "relmc_nsq_run", "relmc_hl1_load", "relmc_hl1_nsq", "relmc_hl1_seq_load", "relmc_hl1_seq", "relmc_hl1_seq_events", "relmc_hl1_seq_sweep",
     "relmc_hl1_seq_storage", "relmc_hl1_var_load", "relmc_hl1_var_seq", "relmc_hl1_var_weather_year", "relmc_hl1_ms_load", "relmc_hl1_ms_seq",
     "relmc_hl1_plan_load", "relmc_hl1_plan", "relmc_hl1_area_load", "relmc_hl1_area", "relmc_hl1_area_tie_outages", "relmc_hl1_area_sweep",
+    "relmc_hl1_area_var_load", "relmc_hl1_area_var",
     "relmc_comm_unique_id", "relmc_comm_init", "relmc_comm_allreduce_acc", "relmc_comm_destroy", "relmc_comm_set_host_allreduce", "relmc_comm_info",
     "relmc_db_reset", "relmc_nsq_db_batch", "relmc_db_accumulate", "relmc_db_size", "relmc_db_export", "relmc_db_import",
     "relmc_seq_load", "relmc_seq_mcsampling", "relmc_seq_mcsimulation", "relmc_seq_years", "relmc_retry_stats", "relmc_retry_overflow", "relmc_retry_dense_stats", "relmc_case_order",
@@ -178,6 +179,12 @@ def load():
     L.relmc_hl1_area_sweep.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.POINTER(_abi.Hl1AreaLevel), _abi.c_uint32_p, u8p, C.POINTER(_abi.Hl1SeqAcc), C.POINTER(_abi.Hl1SeqYear)]
     L.relmc_hl1_area_sweep.restype = C.c_int32
+    L.relmc_hl1_area_var_load.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, i32p, C.c_int32, dp, dp]
+    L.relmc_hl1_area_var_load.restype = C.c_int32
+    L.relmc_hl1_area_var.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(_abi.Hl1AreaVarOpts), C.c_int32,
+                                     C.POINTER(_abi.Hl1AreaStorage), C.POINTER(_abi.Hl1StorageAcc), C.POINTER(_abi.Hl1SeqYear),
+                                     C.POINTER(_abi.Hl1StorageYear), i32p]
+    L.relmc_hl1_area_var.restype = C.c_int32
     L.relmc_comm_unique_id.argtypes = [u8p]
     L.relmc_comm_unique_id.restype = C.c_int32
     L.relmc_comm_init.argtypes = [vp, C.c_int32, C.c_int32, u8p]

@@ -14,7 +14,7 @@
 //                        sequential chronology (relmc_hl1_seq), its loss events (relmc_hl1_seq_events, kernels in relmc_event_kernels.h), its
 //                        load sweep (relmc_hl1_seq_sweep, kernel in relmc_sweep_kernels.h) and
 //                        the record reduction and unit check of every HL1 chronology track
-//   relmc_hl1_host.h     (a header, included by the seven HL1 units around it) what their host code shares: the chunk rule, the loop over a
+//   relmc_hl1_host.h     (a header, included by the eight HL1 units around it) what their host code shares: the chunk rule, the loop over a
 //                        model's launches with the reduction of their year records (hl1_run_records), the argument and unit checks
 //   relmc_storage.hip    energy storage with a state of charge on that chronology (relmc_hl1_seq_storage, kernel in relmc_storage_kernels.h)
 //   relmc_variable.hip   weather-year wind and solar resources on that chronology, with those storages (relmc_hl1_var_load, relmc_hl1_var_seq,
@@ -23,6 +23,8 @@
 //   relmc_plan.hip       the HL1 planning model's Monte Carlo (relmc_hl1_plan)
 //   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area)
 //   relmc_area_sweep.hip the sweep of that chronology over load, tie and fleet levels (relmc_hl1_area_sweep, kernel in relmc_area_sweep_kernels.h)
+//   relmc_area_variable.hip weather-year resources and storages in the areas of that chronology (relmc_hl1_area_var_load, relmc_hl1_area_var,
+//                        kernel in relmc_area_variable_kernels.h)
 //   relmc_screen.hip     the zero-curtailment pre-screen (relmc_solver_opts.screen): certificate tables, pre-pass kernels, worklists
 //   relmc_importance.hip importance sampling for the non-sequential track: tilted sampler with likelihood ratios, weighted reductions (kernels in
 //                        relmc_is_kernels.h), the cross-entropy tuner and the weighted run loop
@@ -222,6 +224,14 @@ struct relmc_ctx {
         // relmc_hl1_area_sweep (relmc_area_sweep.hip): the levels' table of a call, per-level, per-row records
         DevBuf<relmc::AreaSweepTab> sweep_tab; Hl1Records sweep_rec;
     } hl1_area;
+    // weather library of relmc_hl1_area_var_load (relmc_hl1_area_var runs the areas of hl1_area against it): out[n_weather][n_res][nhours],
+    // each resource's area, the optional load curves load[n_weather][n_areas][nhours], records of both kinds of every row.  A slot of its
+    // own, apart from every other HL1 model
+    bool has_hl1_area_var = false;
+    struct Hl1AreaVar {
+        int n_areas = 0, n_weather = 0, n_res = 0, nhours = 0; bool has_load = false; std::vector<int32_t> res_area;
+        DevBuf<double> out, load; Hl1Records rec;
+    } hl1_area_var;
     // zero-curtailment pre-screen (relmc_screen.hip): certificate tables of the case (device pointers inside tab), grow-only work buffers of a pre-pass
     struct Screen {
         relmc::ScreenTab tab = {};

@@ -546,6 +546,70 @@ int32_t relmc_hl1_var_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, i
 int32_t relmc_hl1_var_weather_year(uint64_t seed, uint64_t chain, int32_t year, int32_t years_per_chain, int32_t n_weather,
                                    int32_t pick);
 
+/* ---- weather-dependent forced outage rates on that chronology: a stress library beside the weather library (an extension beyond the reference) ---- */
+/* Thermal units fail more often in the cold snap or heat wave that also drives the peak load.  A stress library goes with the weather
+ * library of relmc_hl1_var_load: for every weather year w, outage class c (at most RELMC_HL1_STRESS_MAX_CLASSES: gas, coal, nuclear ...)
+ * and hour h a failure-rate multiplier fail_mult[w][c][h], finite and >= 0.  Every unit k of the relmc_hl1_seq_load fleet has a class
+ * unit_class[k] in -1 .. n_classes - 1; a unit of class -1 ignores the weather.  A UP unit of class c fails with the hazard
+ * fail_mult[w(y)][c][h] / mttf_k in hour h of chain year y, w(y) being relmc_hl1_var_weather_year's.  Repairs are unchanged: -mttr * ln U.
+ * Cumulative table  per (w, c): G[0] = 0, G[j + 1] = G[j] + fail_mult[w][c][j], one rounded addition per hour, H + 1 values
+ *              (relmc_hl1_stress_cumulative).  Only G goes to the device, and the contract is stated on G alone: the hazard consumed within
+ *              hour j is the linear interpolation of G[j] .. G[j + 1].
+ * Failure time  a unit becomes UP at chain time T (or is UP at the start, T = 0).  The draw and the product are relmc_hl1_seq's:
+ *              E = -mttf * ln U rounded once, U the draw (seed, chain, k | 0x40000000, event).  Class -1: the next transition is T + E.
+ *              Otherwise (relmc_hl1_stress_failure_time), every operation a separate rounded fp64 operation, no contraction, with
+ *              H = nhours, Y = years_per_chain and G the row of (w(y), c):
+ *                0. if not T < Y * H (UP again at or after the chain's end): the result is max(T, Y * H + 1)
+ *                1. n0 = floor(T), y = n0 div H, j = n0 mod H in integers, frac = T - n0
+ *                2. a = G[j] + (G[j + 1] - G[j]) * frac;  rem = G[H] - a
+ *                3. while E > rem (strict): E = E - rem, y = y + 1; if y == Y the result is Y * H + 1 (the unit does not fail within
+ *                   the chain); else j = 0, a = 0, rem = G[H] of the new year's row
+ *                4. t = a + E;  j' = the smallest index in j .. H - 1 with G[j' + 1] >= t, H - 1 if rounding leaves none
+ *                5. d = G[j' + 1] - G[j'];  frac' = d > 0 ? (t - G[j']) / d : 1, clamped to [0, 1]
+ *                6. the result is max(T, (y * H + j') + frac')
+ * Everything else is relmc_hl1_var_seq's, word for word: DOWN on steps [ceil(T_odd), ceil(T_even)), the resources, the load rule, the
+ *              storages, the two record rows, the start rules, the launch chunk rule, the split and repeat guarantees.
+ *              RELMC_HL1_START_STATIONARY keeps the base q = mttr / (mttf + mttr) for draw 0: under a varying multiplier the process is
+ *              NOT stationary, and that start is then only a start closer to the long-run mix than all-UP.
+ * Consequences
+ *   1. With every unit in class -1, both record rows are bitwise relmc_hl1_var_seq's, under either pick and with any storages.
+ *   2. With years_per_chain == 1 and the all-UP start, a multiplier of 1.0 in every hour gives bitwise relmc_hl1_var_seq's records, and
+ *      a multiplier of exactly 2.0 in every hour for the units of one class gives bitwise the records of relmc_hl1_var_seq on the fleet
+ *      with those units' mttf halved (G, 2T and E / 2 are exact then; a draw that ends within rounding of the year's end apart).
+ *   3. With years_per_chain > 1 and multiplier 1.0 a unit's position within the year, not its chain time, enters the sum, so transition
+ *      times may differ from relmc_hl1_var_seq's in the last bit; the steps they take effect on differ only when a time lies within
+ *      rounding of an integer.  No bitwise guarantee is given; the tests hold the per-year integers equal on their chains.
+ *   4. A weather year whose multipliers are all 0 for a class is passed with E unchanged: a unit of that class cannot fail in it.
+ *   5. Under one seed, units of class -1 have exactly the history they have in relmc_hl1_var_seq. */
+#define RELMC_HL1_STRESS_MAX_CLASSES 8
+/* The stress library: n_weather in 1 .. RELMC_HL1_VAR_MAX_WEATHER, n_classes in 1 .. RELMC_HL1_STRESS_MAX_CLASSES, nhours >= 1, n_units in
+ * 1 .. 128.  It builds G and uploads it; it lives in a slot of its own: no other load call disturbs it, and it disturbs none.
+ *   fail_mult   [n_weather][n_classes][nhours], finite and >= 0
+ *   unit_class  [n_units], -1 .. n_classes - 1
+ * RELMC_ERR_INVALID, with relmc_last_error naming the weather year, the class and the hour of the first non-finite or negative
+ * multiplier, or the unit with a class out of range; RELMC_ERR_UNSUPPORTED for n_weather * n_classes * (nhours + 1) >= 2^31 (the kernel
+ * indexes the tables in 32 bits).  A refused call changes nothing. */
+int32_t relmc_hl1_stress_load(relmc_ctx* ctx, int32_t n_weather, int32_t n_classes, int32_t nhours, const double* fail_mult,
+                              int32_t n_units, const int32_t* unit_class);
+/* relmc_hl1_var_seq's argument list and outputs, with the failure rule above.  RELMC_ERR_NO_CASE before any of relmc_hl1_seq_load,
+ * relmc_hl1_var_load and relmc_hl1_stress_load; RELMC_ERR_INVALID, with both values in the message, when n_units differs from the
+ * fleet's or n_weather or nhours differ from relmc_hl1_var_load's; everything relmc_hl1_var_seq refuses is refused here too.  A refused
+ * call changes nothing; n_chains == 0 zeroes the outputs. */
+int32_t relmc_hl1_stress_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain,
+                             int32_t start, const relmc_hl1_var_opts* opts, int32_t n_storage, const relmc_hl1_storage* storage,
+                             relmc_hl1_storage_acc* acc, relmc_hl1_seq_year* years_host,
+                             relmc_hl1_storage_year* storage_years_host, int32_t* weather_host);
+/* Host only, touches no device: cum_out[0 .. nhours] = the cumulative table G of one row of multipliers.  RELMC_ERR_INVALID for
+ * nhours < 1, a null pointer or a multiplier that is not finite and >= 0. */
+int32_t relmc_hl1_stress_cumulative(int32_t nhours, const double* fail_mult_row, double* cum_out);
+/* Host only, touches no device: the failure time above for one draw, compiled from the text the kernel is compiled from.
+ *   t, e     the time the unit became UP (finite, >= 0) and the draw -mttf * ln U (>= 0)
+ *   weather  [years_per_chain]: the weather year of every chain year, each in 0 .. RELMC_HL1_VAR_MAX_WEATHER - 1
+ *   cum      [n_weather][nhours + 1]: the cumulative tables of ONE class, n_weather above every entry of `weather`
+ * NaN for an argument out of these rules. */
+double relmc_hl1_stress_failure_time(double t, double e, int32_t nhours, int32_t years_per_chain, const int32_t* weather,
+                                     const double* cum);
+
 /* ---- HL1 sequential chronology with derated states: three-state Markov units (an extension beyond the reference) ---- */
 /* A large thermal unit that loses a feed pump or a mill runs at part load for days: the textbook third state (Billinton & Allan), with
  * its own capacity and transition rates.  The reference's units, and every other HL1 track here, are two-state.

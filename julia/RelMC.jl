@@ -655,6 +655,68 @@ weather_year(seed::Integer, chain::Integer, year::Integer, years_per_chain::Inte
     ccall((:relmc_hl1_var_weather_year, LIB), Int32, (UInt64, UInt64, Int32, Int32, Int32, Int32), seed, chain, year, years_per_chain, n_weather,
           HL1_VAR_PICK[pick])
 
+const HL1_STRESS_MAX_CLASSES = 8                                           # RELMC_HL1_STRESS_MAX_CLASSES
+
+"""
+run_sequential_stress (an extension beyond the reference): run_sequential_variable's chronology, same arguments, in which a UP unit of
+outage class c fails with the hazard fail_mult / mttf of the hour.  fail_mult[hour, class, weather year] (column-major: the C ABI's
+[n_weather][n_classes][nhours]) is finite and >= 0; unit_class[unit] is 0-based, -1 for a unit that ignores the weather.  Repairs are
+unchanged.  With every unit in class -1 the records are run_sequential_variable's bit for bit.  Returns that function's fields.
+"""
+function run_sequential_stress(eng::Engine, capacity::Vector{Float64}, mttf::Vector{Float64}, mttr::Vector{Float64},
+                               hourly_load::Vector{Float64}, output_mw::Array{Float64,3}, fail_mult::Array{Float64,3},
+                               unit_class::Vector{Int32}, years::Integer;
+                               weather_load::Union{Nothing,Matrix{Float64}}=nothing, storages::Vector{Hl1Storage}=Hl1Storage[],
+                               resource_scale::Vector{Float64}=ones(size(output_mw, 2)), scale::Real=1.0, shift::Real=0.0,
+                               pick::Symbol=:random, seed::Integer=1, chains::Integer=1, start::Symbol=:all_up)
+    (years >= 1 && chains >= 1 && years % chains == 0) || throw(ArgumentError("years must be a positive multiple of chains"))
+    nh, nres, nw = size(output_mw)
+    nh == length(hourly_load) || throw(ArgumentError("output_mw has $nh hours, the load curve $(length(hourly_load))"))
+    nres <= HL1_VAR_MAX_RESOURCES || throw(ArgumentError("at most $HL1_VAR_MAX_RESOURCES resources"))
+    1 <= nw <= HL1_VAR_MAX_WEATHER || throw(ArgumentError("1 to $HL1_VAR_MAX_WEATHER weather years"))
+    length(resource_scale) == nres || throw(ArgumentError("one resource_scale per resource"))
+    weather_load === nothing || size(weather_load) == (nh, nw) || throw(ArgumentError("weather_load must be [hours, weather years]"))
+    length(storages) <= HL1_MAX_STORAGE || throw(ArgumentError("at most $HL1_MAX_STORAGE storages"))
+    ncls = size(fail_mult, 2)
+    (size(fail_mult, 1) == nh && size(fail_mult, 3) == nw) || throw(ArgumentError("fail_mult must be [hours, classes, weather years] of the weather library"))
+    1 <= ncls <= HL1_STRESS_MAX_CLASSES || throw(ArgumentError("1 to $HL1_STRESS_MAX_CLASSES outage classes"))
+    (length(unit_class) == length(capacity) && all(-1 <= c < ncls for c in unit_class)) || throw(ArgumentError("one 0-based class, or -1, per unit"))
+    check(ccall((:relmc_hl1_seq_load, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}),
+                eng.h, length(capacity), capacity, mttf, mttr, length(hourly_load), hourly_load), eng.h, "relmc_hl1_seq_load")
+    check(ccall((:relmc_hl1_var_load, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}),
+                eng.h, nw, nres, nh, nres == 0 ? C_NULL : output_mw, weather_load === nothing ? C_NULL : weather_load), eng.h, "relmc_hl1_var_load")
+    check(ccall((:relmc_hl1_stress_load, LIB), Int32, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cdouble}, Int32, Ptr{Int32}),
+                eng.h, nw, ncls, nh, fail_mult, length(unit_class), unit_class), eng.h, "relmc_hl1_stress_load")
+    opts = Ref(Hl1VarOpts(ntuple(r -> r <= nres ? resource_scale[r] : 0.0, 8), Float64(scale), Float64(shift), HL1_VAR_PICK[pick], Int32(0)))
+    acc = Hl1StorageAcc()
+    yrs = Vector{Hl1SeqYear}(undef, years); sty = Vector{Hl1StorageYear}(undef, years); wy = Vector{Int32}(undef, years)
+    check(ccall((:relmc_hl1_stress_seq, LIB), Int32,
+                (Ptr{Cvoid}, UInt64, UInt64, Int64, Int32, Int32, Ref{Hl1VarOpts}, Int32, Ptr{Hl1Storage}, Ref{Hl1StorageAcc}, Ptr{Hl1SeqYear},
+                 Ptr{Hl1StorageYear}, Ptr{Int32}),
+                eng.h, seed, 0, chains, years ÷ chains, HL1_START[start], opts, length(storages),
+                isempty(storages) ? C_NULL : storages, acc, yrs, sty, wy), eng.h, "relmc_hl1_stress_seq")
+    return (lole_hours_yr=acc.sum_lole / years, eue_mwh_yr=acc.sum_eue / years, lolf_occ_yr=acc.sum_lolf / years,
+            served_hours_yr=acc.sum_served / years, discharged_mwh_yr=acc.sum_discharged / years, charged_mwh_yr=acc.sum_charged / years,
+            years=yrs, storage_years=sty, year_weather=wy)
+end
+
+"G[1 .. nhours + 1], the cumulative table of one row of failure-rate multipliers (relmc_hl1_stress_cumulative: host only, no engine needed)"
+function stress_cumulative(fail_mult_row::Vector{Float64})
+    cum = Vector{Float64}(undef, length(fail_mult_row) + 1)
+    rc = ccall((:relmc_hl1_stress_cumulative, LIB), Int32, (Int32, Ptr{Cdouble}, Ptr{Cdouble}), length(fail_mult_row), fail_mult_row, cum)
+    rc == 0 || throw(ArgumentError("the multipliers must be finite and not negative"))
+    return cum
+end
+
+"""
+The chain time at which a unit of a stressed class fails that became UP at chain time `t` with the draw `e` = -mttf * ln U
+(relmc_hl1_stress_failure_time: host only, no engine needed).  weather[year] is the 0-based weather year of every chain year,
+cum[hour + 1, weather year] the cumulative tables of the unit's class.  years * nhours + 1: not within the chain.
+"""
+stress_failure_time(t::Real, e::Real, weather::Vector{Int32}, cum::Matrix{Float64}) =
+    ccall((:relmc_hl1_stress_failure_time, LIB), Cdouble, (Cdouble, Cdouble, Int32, Int32, Ptr{Int32}, Ptr{Cdouble}),
+          t, e, size(cum, 1) - 1, length(weather), weather, cum)
+
 "relmc_hl1_ms_unit (include/relmc.h, 64 bytes): a three-state unit, UP / DERATED / DOWN: capacities in MW, per state the mean holding time in hours and the probability of the first-listed destination (from UP: DOWN, DERATED; from DERATED: UP, DOWN; from DOWN: UP, DERATED)"
 struct Hl1MsUnit
     capacity_mw::Cdouble; derated_mw::Cdouble; mean_h::NTuple{3,Cdouble}; first_p::NTuple{3,Cdouble}

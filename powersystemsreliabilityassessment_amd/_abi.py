@@ -160,6 +160,7 @@ HL1_VAR_MAX_RESOURCES = 8                 # RELMC_HL1_VAR_MAX_RESOURCES
 HL1_VAR_MAX_WEATHER = 256                 # RELMC_HL1_VAR_MAX_WEATHER
 HL1_VAR_TAG = 0x60000000                  # RELMC_HL1_VAR_TAG
 HL1_VAR_PICK_RANDOM, HL1_VAR_PICK_CYCLE = 0, 1     # RELMC_HL1_VAR_PICK_*
+HL1_STRESS_MAX_CLASSES = 8                # RELMC_HL1_STRESS_MAX_CLASSES
 
 
 class Hl1VarOpts(C.Structure):            # relmc_hl1_var_opts (88 bytes)

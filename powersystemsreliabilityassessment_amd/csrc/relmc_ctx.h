@@ -14,11 +14,13 @@
 //                        sequential chronology (relmc_hl1_seq), its loss events (relmc_hl1_seq_events, kernels in relmc_event_kernels.h), its
 //                        load sweep (relmc_hl1_seq_sweep, kernel in relmc_sweep_kernels.h) and
 //                        the record reduction and unit check of every HL1 chronology track
-//   relmc_hl1_host.h     (a header, included by the eight HL1 units around it) what their host code shares: the chunk rule, the loop over a
+//   relmc_hl1_host.h     (a header, included by the nine HL1 units around it) what their host code shares: the chunk rule, the loop over a
 //                        model's launches with the reduction of their year records (hl1_run_records), the argument and unit checks
 //   relmc_storage.hip    energy storage with a state of charge on that chronology (relmc_hl1_seq_storage, kernel in relmc_storage_kernels.h)
 //   relmc_variable.hip   weather-year wind and solar resources on that chronology, with those storages (relmc_hl1_var_load, relmc_hl1_var_seq,
 //                        kernel in relmc_variable_kernels.h)
+//   relmc_stress.hip     weather-dependent forced outage rates on that chronology, with those resources and storages (relmc_hl1_stress_load,
+//                        relmc_hl1_stress_seq, kernel in relmc_stress_kernels.h)
 //   relmc_multistate.hip that chronology with three-state units (relmc_hl1_ms_load, relmc_hl1_ms_seq, kernel in relmc_multistate_kernels.h)
 //   relmc_plan.hip       the HL1 planning model's Monte Carlo (relmc_hl1_plan)
 //   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area)
@@ -206,6 +208,10 @@ struct relmc_ctx {
     // optional load curves load[n_weather][nhours], records of both rows.  A slot of its own, apart from every other HL1 model
     bool has_hl1_var = false;
     struct Hl1Var { int n_weather = 0, n_res = 0, nhours = 0; bool has_load = false; DevBuf<double> out, load; Hl1Records rec; } hl1_var;
+    // stress library of relmc_hl1_stress_load (relmc_hl1_stress_seq runs the fleet of hl1_seq against hl1_var's weather and it): the
+    // cumulative multiplier tables cum[n_weather][n_classes][nhours + 1], the class of every unit, records of both rows.  A slot of its own
+    bool has_hl1_stress = false;
+    struct Hl1Stress { int n_weather = 0, n_classes = 0, nhours = 0, n_units = 0; DevBuf<double> cum; DevBuf<int32_t> ucls; Hl1Records rec; } hl1_stress;
     // HL1 sequential chronology with three-state units (relmc_hl1_ms_load / relmc_hl1_ms_seq): its own fleet / load curve, apart from every
     // other HL1 model; records of both rows
     bool has_hl1_ms = false;

@@ -1,0 +1,175 @@
+// relmc_stress.hip — weather-dependent forced outage rates on the HL1 sequential chronology (relmc_hl1_stress_load, relmc_hl1_stress_seq,
+// relmc_hl1_stress_cumulative, relmc_hl1_stress_failure_time, contract in include/relmc.h): the fleet of relmc_hl1_seq_load against the
+// weather library of relmc_hl1_var_load, with a failure-rate multiplier per weather year, outage class and hour in a slot of its own.
+// A unit of its own, so that the code objects of relmc_seq.hip, relmc_storage.hip and relmc_variable.hip stay what they were.  The two
+// rows of year records are summed by relmc_hl1_reduce_kernel (hl1_reduce_queue, relmc_seq.hip), one row at a time.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "relmc_hl1_host.h"
+#include "relmc_stress_kernels.h"
+
+using namespace relmc_host;
+
+namespace {
+// G[0] = 0, G[j + 1] = G[j] + m[j]: one rounded addition per hour
+void cumulative(int32_t nhours, const double* m, double* G)
+{
+    G[0] = 0.0;
+    for (int32_t j = 0; j < nhours; ++j) G[j + 1] = G[j] + m[j];
+}
+}  // namespace
+
+extern "C" {
+
+int32_t relmc_hl1_stress_cumulative(int32_t nhours, const double* fail_mult_row, double* cum_out)
+{
+    if (nhours < 1 || !fail_mult_row || !cum_out) return RELMC_ERR_INVALID;
+    for (int32_t j = 0; j < nhours; ++j)
+        if (!std::isfinite(fail_mult_row[j]) || fail_mult_row[j] < 0.0) return RELMC_ERR_INVALID;
+    cumulative(nhours, fail_mult_row, cum_out);
+    return RELMC_OK;
+}
+
+double relmc_hl1_stress_failure_time(double t, double e, int32_t nhours, int32_t years_per_chain, const int32_t* weather, const double* cum)
+{
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (!(t >= 0.0) || !(e >= 0.0) || !std::isfinite(t) || nhours < 1 || years_per_chain < 1 || !weather || !cum) return nan;
+    for (int32_t y = 0; y < years_per_chain; ++y)
+        if (weather[y] < 0 || weather[y] >= RELMC_HL1_VAR_MAX_WEATHER) return nan;
+    return relmc::hl1_stress_failure_time(t, e, nhours, years_per_chain, [&](int y) { return cum + (size_t)weather[y] * ((size_t)nhours + 1); });
+}
+
+int32_t relmc_hl1_stress_load(relmc_ctx* ctx, int32_t n_weather, int32_t n_classes, int32_t nhours, const double* fail_mult, int32_t n_units,
+                              const int32_t* unit_class)
+{
+    const std::string who = "relmc_hl1_stress_load: ";
+    if (!ctx) return RELMC_ERR_INVALID;
+    if (n_weather < 1 || n_weather > RELMC_HL1_VAR_MAX_WEATHER)
+        return fail(ctx, RELMC_ERR_INVALID, who + "n_weather " + std::to_string(n_weather) + " not in 1.." + std::to_string(RELMC_HL1_VAR_MAX_WEATHER));
+    if (n_classes < 1 || n_classes > RELMC_HL1_STRESS_MAX_CLASSES)
+        return fail(ctx, RELMC_ERR_INVALID, who + "n_classes " + std::to_string(n_classes) + " not in 1.." + std::to_string(RELMC_HL1_STRESS_MAX_CLASSES));
+    if (nhours < 1) return fail(ctx, RELMC_ERR_INVALID, who + "nhours " + std::to_string(nhours) + " is not positive");
+    if (n_units < 1 || n_units > relmc::NCOMPMAX)
+        return fail(ctx, RELMC_ERR_INVALID, who + "n_units " + std::to_string(n_units) + " not in 1.." + std::to_string(relmc::NCOMPMAX));
+    if (!fail_mult || !unit_class) return fail(ctx, RELMC_ERR_INVALID, who + "fail_mult or unit_class is null");
+    // the kernel indexes the cumulative tables in 32 bits
+    if ((int64_t)n_weather * n_classes * ((int64_t)nhours + 1) >= ((int64_t)1 << 31))
+        return fail(ctx, RELMC_ERR_UNSUPPORTED, who + "n_weather * n_classes * (nhours + 1) is 2^31 or more");
+    const size_t H = (size_t)nhours, rows = (size_t)n_weather * (size_t)n_classes;
+    for (size_t i = 0; i < rows * H; ++i)
+        if (!std::isfinite(fail_mult[i]) || fail_mult[i] < 0.0) {
+            const std::string where = "multiplier of weather year " + std::to_string(i / H / (size_t)n_classes) + ", class " +
+                                      std::to_string(i / H % (size_t)n_classes) + ", hour " + std::to_string(i % H);
+            return fail(ctx, RELMC_ERR_INVALID, who + where + (std::isfinite(fail_mult[i]) ? " is negative" : " not finite"));
+        }
+    for (int32_t k = 0; k < n_units; ++k)
+        if (unit_class[k] < -1 || unit_class[k] >= n_classes)
+            return fail(ctx, RELMC_ERR_INVALID, who + "class " + std::to_string(unit_class[k]) + " of unit " + std::to_string(k) + " not in -1.." + std::to_string(n_classes - 1));
+    std::vector<double> G(rows * (H + 1));
+    for (size_t r = 0; r < rows; ++r) cumulative(nhours, fail_mult + r * H, G.data() + r * (H + 1));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto& X = ctx->hl1_stress;
+    ctx->has_hl1_stress = false;
+    HIP_TRY(ctx, X.cum.grow(G.size()));
+    HIP_TRY(ctx, hipMemcpy(X.cum.get(), G.data(), sizeof(double) * G.size(), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, X.ucls.grow((size_t)n_units));
+    HIP_TRY(ctx, hipMemcpy(X.ucls.get(), unit_class, sizeof(int32_t) * (size_t)n_units, hipMemcpyHostToDevice));
+    X.n_weather = n_weather; X.n_classes = n_classes; X.nhours = nhours; X.n_units = n_units;
+    ctx->has_hl1_stress = true;
+    return RELMC_OK;
+}
+
+int32_t relmc_hl1_stress_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain, int32_t start,
+                             const relmc_hl1_var_opts* opts, int32_t n_storage, const relmc_hl1_storage* storage,
+                             relmc_hl1_storage_acc* acc, relmc_hl1_seq_year* years_host, relmc_hl1_storage_year* storage_years_host,
+                             int32_t* weather_host)
+{
+    const std::string who = "relmc_hl1_stress_seq: ";
+    if (!ctx) return RELMC_ERR_INVALID;
+    if (!ctx->has_hl1_seq) return fail(ctx, RELMC_ERR_NO_CASE, who + "relmc_hl1_seq_load has not been called");
+    if (!ctx->has_hl1_var) return fail(ctx, RELMC_ERR_NO_CASE, who + "relmc_hl1_var_load has not been called");
+    if (!ctx->has_hl1_stress) return fail(ctx, RELMC_ERR_NO_CASE, who + "relmc_hl1_stress_load has not been called");
+    auto& S = ctx->hl1_seq;
+    auto& V = ctx->hl1_var;
+    auto& X = ctx->hl1_stress;
+    if (S.nhours != V.nhours)
+        return fail(ctx, RELMC_ERR_INVALID, who + "nhours of relmc_hl1_seq_load " + std::to_string(S.nhours) + " is not nhours of relmc_hl1_var_load " + std::to_string(V.nhours));
+    if (X.n_units != S.ngen)
+        return fail(ctx, RELMC_ERR_INVALID, who + "n_units of relmc_hl1_stress_load " + std::to_string(X.n_units) + " is not the fleet's " + std::to_string(S.ngen));
+    if (X.n_weather != V.n_weather)
+        return fail(ctx, RELMC_ERR_INVALID, who + "n_weather of relmc_hl1_stress_load " + std::to_string(X.n_weather) + " is not n_weather of relmc_hl1_var_load " + std::to_string(V.n_weather));
+    if (X.nhours != V.nhours)
+        return fail(ctx, RELMC_ERR_INVALID, who + "nhours of relmc_hl1_stress_load " + std::to_string(X.nhours) + " is not nhours of relmc_hl1_var_load " + std::to_string(V.nhours));
+    if (!hl1_chain_args_ok(acc, n_chains, years_per_chain, start)) return fail(ctx, RELMC_ERR_INVALID, who + "bad arguments");
+    if (!opts) return fail(ctx, RELMC_ERR_INVALID, who + "opts is null");
+    if (!std::isfinite(opts->scale) || !std::isfinite(opts->shift)) return fail(ctx, RELMC_ERR_INVALID, who + "scale / shift not finite");
+    relmc::Hl1StressArgs A; std::memset(&A, 0, sizeof(A));
+    for (int r = 0; r < RELMC_HL1_VAR_MAX_RESOURCES; ++r) {  // relmc_hl1_var_seq's checks, repeated
+        const double s = opts->resource_scale[r];
+        const std::string rs = who + "resource_scale " + std::to_string(r);
+        if (!std::isfinite(s)) return fail(ctx, RELMC_ERR_INVALID, rs + " not finite");
+        if (s < 0.0) return fail(ctx, RELMC_ERR_INVALID, rs + " is negative");
+        if (r >= V.n_res && s != 0.0) return fail(ctx, RELMC_ERR_INVALID, rs + " is not 0 with n_resources " + std::to_string(V.n_res));
+        A.rscale[r] = r < V.n_res ? s : 0.0;
+    }
+    if (opts->pick != RELMC_HL1_VAR_PICK_RANDOM && opts->pick != RELMC_HL1_VAR_PICK_CYCLE)
+        return fail(ctx, RELMC_ERR_INVALID, who + "pick " + std::to_string(opts->pick) + " not 0 or 1");
+    if (opts->reserved != 0) return fail(ctx, RELMC_ERR_INVALID, who + "reserved is not 0");
+    if (n_storage < 0 || n_storage > RELMC_HL1_MAX_STORAGE)
+        return fail(ctx, RELMC_ERR_INVALID, who + "n_storage " + std::to_string(n_storage) + " not in 0.." + std::to_string(RELMC_HL1_MAX_STORAGE));
+    if (n_storage > 0 && !storage) return fail(ctx, RELMC_ERR_INVALID, who + "n_storage > 0 without storage");
+    for (int i = 0; i < n_storage; ++i) {                    // relmc_hl1_seq_storage's field checks, repeated
+        const relmc_hl1_storage& v = storage[i];
+        const std::string st = who + "storage " + std::to_string(i) + ": ";
+        const struct { const char* name; double x; } fields[6] = {{"charge_mw", v.charge_mw}, {"discharge_mw", v.discharge_mw}, {"energy_mwh", v.energy_mwh},
+                                                                   {"eta_charge", v.eta_charge}, {"eta_discharge", v.eta_discharge}, {"soc0_mwh", v.soc0_mwh}};
+        for (const auto& f : fields)
+            if (!std::isfinite(f.x)) return fail(ctx, RELMC_ERR_INVALID, st + f.name + " not finite");
+        for (int q = 0; q < 3; ++q)
+            if (fields[q].x < 0.0) return fail(ctx, RELMC_ERR_INVALID, st + fields[q].name + " is negative");
+        for (int q = 3; q < 5; ++q)
+            if (!(fields[q].x > 0.0 && fields[q].x <= 1.0)) return fail(ctx, RELMC_ERR_INVALID, st + fields[q].name + " not in (0, 1]");
+        if (!(v.soc0_mwh >= 0.0 && v.soc0_mwh <= v.energy_mwh)) return fail(ctx, RELMC_ERR_INVALID, st + "soc0_mwh not in [0, energy_mwh]");
+        A.st[i] = v;
+    }
+    A.scale = opts->scale; A.shift = opts->shift; A.n_storage = n_storage;
+    A.n_res = V.n_res; A.n_weather = V.n_weather; A.pick = opts->pick;
+    A.out = V.out.get(); A.wload = V.has_load ? V.load.get() : nullptr;
+    A.cum = X.cum.get(); A.ucls = X.ucls.get(); A.n_classes = X.n_classes;
+    std::memset(acc, 0, sizeof(*acc));
+    if (n_chains == 0) return RELMC_OK;
+    if (weather_host)                                        // the device works out the same function (hl1_stress_weather)
+        for (int64_t c = 0; c < n_chains; ++c)
+            for (int32_t y = 0; y < years_per_chain; ++y)
+                weather_host[c * years_per_chain + y] = relmc_hl1_var_weather_year(seed, first_chain + (uint64_t)c, y, years_per_chain, V.n_weather, opts->pick);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    double sum[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int64_t per = hl1_chunk_items(n_chains, kHl1RecordBudget, (int64_t)years_per_chain * 2);             // a chain counts its records of both rows
+    const int rc = hl1_run_records(ctx, "relmc_hl1_stress_seq", X.rec, n_chains, per, years_per_chain, 2, sum,
+        [&](int64_t c0, int64_t nc, int64_t) {
+            hipLaunchKernelGGL(relmc::relmc_hl1_stress_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
+                               first_chain + (uint64_t)c0, nc, years_per_chain, start, A, X.rec.years.get());
+        },
+        [&](int64_t c0, int64_t, int64_t nrec) -> int {
+            if (years_host)
+                HIP_TRY(ctx, hipMemcpyAsync(years_host + c0 * years_per_chain, X.rec.years.get(), sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
+            if (storage_years_host)
+                HIP_TRY(ctx, hipMemcpyAsync(storage_years_host + c0 * years_per_chain, X.rec.years.get() + (size_t)nrec * 3, sizeof(double) * 3 * nrec,
+                                            hipMemcpyDeviceToHost, ctx->stream));
+            return RELMC_OK;
+        },
+        hl1_no_host_step);
+    if (rc) return rc;
+    acc->years = n_chains * years_per_chain;
+    acc->sum_lole = sum[0]; acc->sum_eue = sum[1]; acc->sum_lolf = sum[2]; acc->sum_lole2 = sum[3]; acc->sum_eue2 = sum[4]; acc->sum_lolf2 = sum[5];
+    acc->sum_served = sum[6]; acc->sum_discharged = sum[7]; acc->sum_charged = sum[8];
+    acc->sum_served2 = sum[9]; acc->sum_discharged2 = sum[10]; acc->sum_charged2 = sum[11];
+    return RELMC_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,360 @@
+// relmc_stress_kernels.h — weather-dependent forced outage rates on the HL1 sequential chronology (relmc_hl1_stress_seq, contract in
+// include/relmc.h): relmc_hl1_var_seq's walk of a chain's fleet history, in which a UP unit of outage class c fails with the hazard
+// fail_mult[w(y)][c][h] / mttf in hour h of chain year y.  The time of a failure is no longer T + E: the draw E = -mttf * ln U is spent
+// along the cumulative multiplier table G of the unit's class, year by year (hl1_stress_failure_time, compiled for the host and the
+// device from this one text).  An extension beyond the reference, whose units have constant rates.
+// The helpers of the resources, the storages and the year close repeat relmc_variable_kernels.h's under names of their own: that header
+// defines its kernel, so a second unit cannot include it, and relmc_variable.hip's code object stays what it was.
+#pragma once
+#include <utility>
+#include "../../include/relmc.h"
+#include "relmc_devfn.h"
+#include "relmc_hl1_chrono.h"
+
+namespace relmc {
+
+// The contract's failure time (include/relmc.h, "Failure time"): a unit of a stressed class became UP at chain time T >= 0 and draws the
+// hazard E > 0; -> the chain time at which it fails, or years * H + 1 when it does not fail within the chain.  row(y) is the cumulative
+// table G[0 .. H] of the unit's class in the weather year of chain year y (0 <= y < years).  Every fp64 operation is rounded on its own
+// (no contraction), so that the host, the device and the Python model of the tests give the same bits.
+template <class Row>
+__host__ __device__ inline double hl1_stress_failure_time(double T, double E, int H, int years, Row&& row)
+{
+#pragma clang fp contract(off)
+    const double never = (double)((int64_t)years * H + 1);
+    if (!(T < (double)((int64_t)years * H))) return T > never ? T : never;    // UP again at or after the chain's end: nothing to see
+    const int64_t n0 = (int64_t)T;                           // floor: T >= 0
+    int y = (int)(n0 / H), j = (int)(n0 - (int64_t)y * H);
+    const double* G = row(y);
+    const double frac = T - (double)n0;
+    const double slope = G[j + 1] - G[j];
+    const double part = slope * frac;
+    double a = G[j] + part;
+    double rem = G[H] - a;
+    while (E > rem) {                                        // the year's hazard does not use the draw up
+        E = E - rem;
+        if (++y == years) return never;
+        G = row(y);
+        j = 0; a = 0.0; rem = G[H];
+    }
+    const double t = a + E;
+    // The smallest j' in j .. H - 1 with G[j' + 1] >= t, H - 1 if there is none: at most ceil(log2 H) probes.  (A search that reads 15
+    // pivots a level, 4 levels of independent loads, finds the same j' and was measured slower: DESIGN.md 6.10.)
+    int lo = j, hi = H - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (G[mid + 1] >= t) hi = mid; else lo = mid + 1;
+    }
+    const double g0 = G[lo], d = G[lo + 1] - g0;
+    double f = 1.0;
+    if (d > 0.0) {
+        const double num = t - g0;
+        f = num / d;
+        f = f < 0.0 ? 0.0 : f > 1.0 ? 1.0 : f;
+    }
+    const double r = (double)((int64_t)y * H + lo) + f;
+    return r > T ? r : T;
+}
+
+// The storages, the load level, the resource scales and the weather library as Hl1VarArgs has them, then the stress library: the
+// cumulative tables and the fleet's classes.  Passed BY VALUE as a kernel argument: every read of the fields is a scalar load from the
+// kernel argument segment.
+struct Hl1StressArgs {
+    relmc_hl1_storage st[RELMC_HL1_MAX_STORAGE];
+    double rscale[RELMC_HL1_VAR_MAX_RESOURCES];
+    double scale, shift;
+    const double* out;                   // [n_weather][n_res][H], fewer than 2^31 values (relmc_hl1_var_load)
+    const double* wload;                 // [n_weather][H], or nullptr: the load curve of relmc_hl1_seq_load
+    const double* cum;                   // [n_weather][n_classes][H + 1], fewer than 2^31 values (relmc_hl1_stress_load)
+    const int32_t* ucls;                 // [ngen]: -1 or a class
+    int32_t n_storage, n_res, n_weather, pick, n_classes, reserved;
+};
+
+template <class F, int... I>
+DEVFI void hl1_stress_each_(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <class F>
+DEVFI void hl1_stress_each(F&& f) { hl1_stress_each_(f, std::make_integer_sequence<int, RELMC_HL1_MAX_STORAGE>{}); }
+
+// L = scale * base + shift with the product and the sum each rounded
+DEVFI double hl1_stress_load(double scale, double ld, double shift)
+{
+#pragma clang fp contract(off)
+    const double p = scale * ld;
+    return p + shift;
+}
+
+// cap + s * v with the product and the sum each rounded
+DEVFI double hl1_stress_add(double cap, double s, double v)
+{
+#pragma clang fp contract(off)
+    const double p = s * v;
+    return cap + p;
+}
+
+// hl1_var_weather, verbatim: the weather year of chain year y of `chain`
+DEVFI int hl1_stress_weather(uint64_t seed, uint64_t chain, int y, int years, int n_weather, int pick)
+{
+    if (pick == RELMC_HL1_VAR_PICK_CYCLE) return (int)((chain * (uint64_t)years + (uint64_t)y) % (uint64_t)n_weather);
+    uint32_t w[4];
+    philox4x32_10((uint32_t)chain, (uint32_t)(chain >> 32), RELMC_HL1_VAR_TAG, (uint32_t)y, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+    return (int)(((uint64_t)w[0] * (uint64_t)n_weather) >> 32);
+}
+
+DEVFI double hl1_stress_readlane(double v, int src)
+{
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
+}
+
+// bit i = storage i can discharge, bit 8 + i = it is not settled (hl1_var_bits)
+DEVFI uint32_t hl1_stress_bits(const relmc_hl1_storage& p, double s, int i)
+{
+    return ((s > 0.0 && p.discharge_mw > 0.0) ? 1u << i : 0u) | ((s < p.energy_mwh && p.charge_mw > 0.0) ? 256u << i : 0u);
+}
+
+// The contract's short step (hl1_var_discharge)
+DEVFI void hl1_stress_discharge(const Hl1StressArgs& A, int ns, int z, int lane, double& soc, uint32_t& bits, double& need, double& xs)
+{
+    hl1_stress_each([&](auto ic) {
+#pragma clang fp contract(off)
+        constexpr int i = decltype(ic)::value;
+        if (i < ns && need > 0.0 && ((bits >> i) & 1u)) {    // wave-uniform
+            const relmc_hl1_storage& p = A.st[i + z];
+            const double eta = p.eta_discharge, s = hl1_stress_readlane(soc, i);
+            const double avail = __builtin_fmin(p.discharge_mw, s * eta);
+            const double x = __builtin_fmin(avail, need);
+            const double t = __builtin_fmax(0.0, s - x / eta);
+            need = need - x;
+            xs = xs + x;
+            soc = lane == i ? t : soc;
+            bits = (bits & ~(0x101u << i)) | hl1_stress_bits(p, t, i);
+        }
+    });
+}
+
+// The contract's long step (hl1_var_charge)
+DEVFI void hl1_stress_charge(const Hl1StressArgs& A, int ns, int z, int lane, double& soc, uint32_t& bits, double surplus, double& ys)
+{
+    hl1_stress_each([&](auto ic) {
+#pragma clang fp contract(off)
+        constexpr int i = decltype(ic)::value;
+        if (i < ns && surplus > 0.0 && ((bits >> (8 + i)) & 1u)) {      // wave-uniform
+            const relmc_hl1_storage& p = A.st[i + z];
+            const double eta = p.eta_charge, cap = p.energy_mwh, s = hl1_stress_readlane(soc, i);
+            const double room = (cap - s) / eta;
+            const double y = __builtin_fmin(__builtin_fmin(p.charge_mw, room), surplus);
+            const double t = __builtin_fmin(cap, s + y * eta);
+            surplus = surplus - y;
+            ys = ys + y;
+            soc = lane == i ? t : soc;
+            bits = (bits & ~(0x101u << i)) | hl1_stress_bits(p, t, i);
+        }
+    });
+}
+
+// This lane's partials of the open year, and the year's close (hl1_var_close_year: the fixed-order butterfly over both records)
+struct Hl1StressPartials { uint32_t lole, lolf, served; double eue, dis, chg; };
+DEVFI void hl1_stress_close_year(Hl1StressPartials& a, double* __restrict__ out0, double* __restrict__ out1)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        a.lole += (uint32_t)__shfl_xor((int)a.lole, off); a.lolf += (uint32_t)__shfl_xor((int)a.lolf, off); a.served += (uint32_t)__shfl_xor((int)a.served, off);
+        a.eue += __shfl_xor(a.eue, off); a.dis += __shfl_xor(a.dis, off); a.chg += __shfl_xor(a.chg, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        out0[0] = (double)a.lole; out0[1] = a.eue; out0[2] = (double)a.lolf;
+        out1[0] = (double)a.served; out1[1] = a.dis; out1[2] = a.chg;
+    }
+    a.lole = a.lolf = a.served = 0u;
+    a.eue = a.dis = a.chg = 0.0;
+}
+
+// Chain c = blockIdx.x * 4 + wave.  The window loop, the group stages and the year close are a COPY of relmc_hl1_var_kernel's
+// (relmc_variable_kernels.h, which says what they do), on purpose: sharing the loop between kernels has cost the older kernels time
+// (DESIGN.md 6.12), and that kernel's code object must not change.  What is new is the transition of stage (1):
+//   class      lane l keeps the classes of its units l and l + 64 in registers (cls[s], -1: the unit ignores the weather)
+//   failure    a lane whose unit has just become UP and has a class runs hl1_stress_failure_time instead of the addition: a walk over the
+//              years the draw outlasts (bounded by `years`; the weather year of each from hl1_stress_weather), then a binary search of at
+//              most ceil(log2 H) probes over one row of G in global memory, which every chain reads and L2 keeps.  These lanes diverge
+//              from the others inside `while (__any(more))`; the loop's trip count is what it was, one trip per transition of the busiest lane
+//   never      a unit that does not fail again gets years * H + 1, beyond every window: its cursor waits for the rest of the chain
+// Records: year_out[row][chain of the launch][year][3], row 0 = (lole, eue, lolf), row 1 = (served_hours, discharged_mwh, charged_mwh).
+// amdgpu_waves_per_eu(4, 4): left alone the allocator takes 131 VGPRs, three waves per SIMD; asked for relmc_hl1_var_kernel's four it
+// finds 125 without scratch.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) relmc_hl1_stress_kernel(const Hl1SeqCase* __restrict__ S, const double* __restrict__ load, uint64_t seed,
+                                                               uint64_t first_chain, int64_t n_chains, int32_t years, int32_t start,
+                                                               const Hl1StressArgs A, double* __restrict__ year_out)
+{
+    constexpr int W = HL1_SEQ_WINDOW;
+    constexpr int NS = RELMC_HL1_MAX_STORAGE;
+    __shared__ uint32_t masks[4][4][W];                     // [wave][mask word][step of the window], bit k & 31 of word k >> 5 = unit k down
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t cl = (int64_t)blockIdx.x * 4 + wv;
+    if (cl >= n_chains) return;                              // wave-uniform
+    const uint64_t chain = first_chain + (uint64_t)cl;
+    const int ngen = S->ngen, H = S->nhours, nw = (ngen + 31) >> 5, nslot = ngen > 64 ? 2 : 1;
+    const int ns = A.n_storage < NS ? A.n_storage : NS;
+    const int nres = A.n_res < RELMC_HL1_VAR_MAX_RESOURCES ? A.n_res : RELMC_HL1_VAR_MAX_RESOURCES;
+    const double* __restrict__ const lcurve = A.wload ? A.wload : load;       // base(w, h) = lcurve[(w * H & lmask) + h]
+    const uint32_t lmask = A.wload ? ~0u : 0u;
+    const double* __restrict__ const rout = A.out;
+    const double* __restrict__ const cum = A.cum;
+    const uint32_t ncls = (uint32_t)A.n_classes, H1 = (uint32_t)H + 1u;
+    uint32_t (*const seg)[W] = masks[wv];
+    const int64_t nsteps = (int64_t)years * H;
+    double* const out0 = year_out + (size_t)cl * (size_t)years * 3;
+    double* const out1 = out0 + (size_t)n_chains * (size_t)years * 3;
+
+    bool down[2], mine[2];
+    double tn[2], mf[2], mr[2];
+    int ev[2], cls[2];
+    int64_t since[2];
+    // the failure time of a unit of class c that became UP at T with the draw E (c >= 0; G's row of (w, c) starts at (w * ncls + c) * (H + 1))
+    auto fail_at = [&](double T, double E, int c) {
+        return hl1_stress_failure_time(T, E, H, years, [&](int y) {
+            return cum + ((uint32_t)hl1_stress_weather(seed, chain, y, years, A.n_weather, A.pick) * ncls + (uint32_t)c) * H1;
+        });
+    };
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int k = lane + 64 * s;
+        mine[s] = k < ngen;
+        mf[s] = mine[s] ? S->mttf[k] : 1.0; mr[s] = mine[s] ? S->mttr[k] : 1.0;
+        cls[s] = mine[s] ? A.ucls[k] : -1;
+        down[s] = false; ev[s] = 0; since[s] = 1; tn[s] = 0.0;
+        if (mine[s]) {
+            if (start == RELMC_HL1_START_STATIONARY) { down[s] = hl1_seq_u(chain, k, 0, seed) < S->q[k]; ev[s] = 1; }
+            const double e = __dmul_rn(-(down[s] ? mr[s] : mf[s]), log(hl1_seq_u(chain, k, ev[s], seed)));    // T_1 = 0 + duration, or
+            tn[s] = (!down[s] && cls[s] >= 0) ? fail_at(0.0, e, cls[s]) : e;                                     // the failure time from 0
+            ++ev[s];
+        }
+    }
+
+    double soc = 0.0;                                        // storage i's state of charge (MWh) in lane i
+    uint32_t bits = 0u;                                      // hl1_stress_bits of every storage (wave-uniform)
+    hl1_stress_each([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        if (i < ns) { soc = lane == i ? A.st[i].soc0_mwh : soc; bits |= hl1_stress_bits(A.st[i], A.st[i].soc0_mwh, i); }
+    });
+    Hl1StressPartials a = {0u, 0u, 0u, 0.0, 0.0, 0.0};      // this lane's partials of the open year ycur
+    int ycur = 0, gy = 0, gh = 0;                            // gy / gh: chain year and hour of the current 64-step group's first step
+    int yw = -1;                                             // this lane's cached chain year, and
+    uint32_t wb = 0u;                                        // w * H of its weather year w (relmc_hl1_var_load: n_weather * n_res * H < 2^31)
+    bool prev = false;                                       // loss flag of the step before the group (none before step 1)
+    for (int64_t w0 = 1; w0 <= nsteps; w0 += W) {
+        const int64_t w1 = w0 + W;
+        const int wlen = nsteps - w0 + 1 < W ? (int)(nsteps - w0 + 1) : W;
+        for (int q = 0; q < nw; ++q)
+            for (int i = lane; i < W; i += 64) seg[q][i] = 0u;
+        hl1_seq_wave_sync();
+        // (1) down intervals [ceil(T_odd), ceil(T_even)) of the window
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {                        // unrolled: the cursors stay in registers
+            if (s >= nslot) break;
+            bool more = mine[s];
+            while (__any(more)) {
+                int fb = 0, fe = 0;
+                if (more) {
+                    const int64_t c = (int64_t)__builtin_ceil(tn[s]);             // the transition takes effect from step c on
+                    if (down[s]) {
+                        const int64_t a0 = since[s] > w0 ? since[s] : w0, b = c < w1 ? c : w1;
+                        if (b > a0) { fb = (int)(a0 - w0); fe = (int)(b - w0); }
+                    }
+                    if (c >= w1) more = false;                                    // the cursor waits for a later window
+                    else {
+                        down[s] = !down[s]; since[s] = c;
+                        const double l = log(hl1_seq_u(chain, lane + 64 * s, ev[s], seed));
+                        const double e = __dmul_rn(-(down[s] ? mr[s] : mf[s]), l);
+                        if (!down[s] && cls[s] >= 0) tn[s] = fail_at(tn[s], e, cls[s]);   // UP in a stressed class: the hazard along G
+                        else tn[s] = __dadd_rn(tn[s], e);                         // no FMA: the host model rounds the same way
+                        ++ev[s];
+                    }
+                }
+                for (uint64_t pend = __ballot(fe > fb); pend; pend &= pend - 1) {
+                    const int src = __builtin_ctzll(pend);
+                    const int sb = __builtin_amdgcn_readlane(fb, src), se = __builtin_amdgcn_readlane(fe, src), sk = src + 64 * s;
+                    uint32_t* const row = seg[sk >> 5];
+                    const uint32_t bit = 1u << (sk & 31);
+                    for (int h = sb + lane; h < se; h += 64) row[h] |= bit;       // se <= W: inside the window's row
+                }
+            }
+        }
+        hl1_seq_wave_sync();
+        // (2) one step per lane
+        for (int g = 0; g < wlen; g += 64) {
+            const int i = g + lane;                          // < W: g is a multiple of 64 below wlen <= W
+            const bool valid = i < wlen;
+            int h = gh + lane, y = gy;
+            while (h >= H) { h -= H; ++y; }
+            bool sh = false, lg = false;                     // short: cap < L, long: cap > L
+            double m = 0.0;                                  // the step's need (short) or surplus (long)
+            if (valid) {                                     // y < years, h < H: every read below is inside its table
+                if (y != yw) { yw = y; wb = (uint32_t)hl1_stress_weather(seed, chain, y, years, A.n_weather, A.pick) * (uint32_t)H; }
+                // the step's load and its first two outputs are read BEFORE the capacity sum, whose work hides their latency
+                const double ld = lcurve[(wb & lmask) + (uint32_t)h];
+                uint32_t oi = wb * (uint32_t)nres + (uint32_t)h;                  // out[(w * n_res + r) * H + h], r = 0
+                double o0 = 0.0, o1 = 0.0;
+                if (nres > 0) o0 = rout[oi];                                      // wave-uniform tests
+                if (nres > 1) o1 = rout[oi + (uint32_t)H];
+                double cap = 0.0;
+                for (int q = 0; q < nw; ++q) {
+                    const uint32_t up = ~seg[q][i];
+                    const int kn = ngen - 32 * q < 32 ? ngen - 32 * q : 32;
+                    for (int b = 0; b < kn; ++b) cap += ((up >> b) & 1u) ? S->cap[32 * q + b] : 0.0;   // ascending units; + 0.0 is exact
+                }
+                if (nres > 0) cap = hl1_stress_add(cap, A.rscale[0], o0);
+                if (nres > 1) cap = hl1_stress_add(cap, A.rscale[1], o1);
+                for (int r = 2; r < nres; r += 2) {                               // the others two at a time: one wait per pair
+                    const uint32_t oj = oi + (uint32_t)r * (uint32_t)H;
+                    const bool two = r + 1 < nres;
+                    const double a = rout[oj], b = two ? rout[oj + (uint32_t)H] : 0.0;
+                    cap = hl1_stress_add(cap, A.rscale[r], a);
+                    if (two) cap = hl1_stress_add(cap, A.rscale[r + 1], b);
+                }
+                const double L = hl1_stress_load(A.scale, ld, A.shift);
+                sh = cap < L; lg = cap > L;
+                m = sh ? L - cap : lg ? cap - L : 0.0;
+            }
+            const uint64_t ms = __builtin_amdgcn_ballot_w64(sh), ml = __builtin_amdgcn_ballot_w64(lg);
+            if (ms != 0 || (bits >> 8) != 0u) {              // wave-uniform; a quiet group (no short step, every storage settled) does nothing
+                double xy = 0.0;                             // the sum of x (short step) or of y (long step) of the lane's step
+                int z = 0;
+                __asm__ volatile("" : "+s"(z));
+                uint64_t rest = ~0ull;                       // the steps after the one just visited
+                for (;;) {
+                    const uint64_t todo = (((bits & 0xffu) ? ms : 0ull) | ((bits >> 8) ? ml : 0ull)) & rest;
+                    if (todo == 0) break;
+                    const int j = __builtin_ctzll(todo);
+                    rest = j == 63 ? 0ull : ~0ull << (j + 1);
+                    const double mj = hl1_stress_readlane(m, j);
+                    if ((ms >> j) & 1ull) {
+                        double need = mj, x = 0.0;
+                        hl1_stress_discharge(A, ns, z, lane, soc, bits, need, x);
+                        if (lane == j) { m = need; xy = x; }     // m: what is left of the need
+                    } else {
+                        double yj = 0.0;
+                        hl1_stress_charge(A, ns, z, lane, soc, bits, mj, yj);
+                        if (lane == j) xy = yj;
+                    }
+                }
+                const bool f = sh && m > 0.0;                // a loss step: need is left after the storages (m: the deficit)
+                const int fl = __shfl_up((int)f, 1);
+                const bool r = f && !(lane == 0 ? prev : fl != 0);
+                prev = __shfl((int)f, 63) != 0;
+                for (;;) {
+                    if (valid && y == ycur) {
+                        a.lole += f ? 1u : 0u; a.lolf += r ? 1u : 0u; a.served += (sh && !f) ? 1u : 0u;
+                        a.eue += f ? m : 0.0; a.dis += sh ? xy : 0.0; a.chg += sh ? 0.0 : xy;
+                    }
+                    if (!__any(valid && y > ycur)) break;
+                    hl1_stress_close_year(a, out0 + (size_t)ycur * 3, out1 + (size_t)ycur * 3);
+                    ++ycur;
+                }
+            } else prev = false;
+            gh += 64;
+            while (gh >= H) { gh -= H; ++gy; }
+        }
+        hl1_seq_wave_sync();
+    }
+    for (; ycur < years; ++ycur) hl1_stress_close_year(a, out0 + (size_t)ycur * 3, out1 + (size_t)ycur * 3);
+}
+}  // namespace relmc

@@ -1,7 +1,8 @@
 // relmc_area_variable.hip — weather-year resources and storages in the areas of the HL1 multi-area chronology (relmc_hl1_area_var_load,
 // relmc_hl1_area_var, contract in include/relmc.h): the areas, units and ties of relmc_hl1_area_load (relmc_area.hip), with
 // relmc_hl1_area_tie_outages' data when set, against a weather library in a slot of its own; the storages are given in the call.  A unit
-// of its own, so that the code objects of relmc_area.hip and relmc_variable.hip stay what they were.  The two records of every row,
+// of its own, so that the code objects of relmc_area.hip and relmc_variable.hip stay what they were; the resource-scale, pick and
+// per-storage checks, the weather_host fill and the accumulator fill are relmc_hl1_host.h's, shared with relmc_hl1_var_seq.  The two records of every row,
 // (lole, eue, lolf) and (served_hours, discharged_mwh, charged_mwh), are summed by relmc_hl1_reduce_kernel (hl1_reduce_queue,
 // relmc_seq.hip), one slice at a time.
 #include <algorithm>
@@ -92,15 +93,8 @@ int32_t relmc_hl1_area_var(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, 
     if (!hl1_chain_args_ok(acc, n_chains, years_per_chain, start)) return fail(ctx, RELMC_ERR_INVALID, who + "bad arguments");
     if (!opts) return fail(ctx, RELMC_ERR_INVALID, who + "opts is null");
     relmc::AreaVarArgs A; std::memset(&A, 0, sizeof(A));
-    for (int r = 0; r < RELMC_HL1_VAR_MAX_RESOURCES; ++r) {
-        const double s = opts->resource_scale[r];
-        const std::string rs = who + "resource_scale " + std::to_string(r);
-        if (!std::isfinite(s)) return fail(ctx, RELMC_ERR_INVALID, rs + " not finite");
-        if (s < 0.0) return fail(ctx, RELMC_ERR_INVALID, rs + " is negative");
-        if (r >= V.n_res && s != 0.0) return fail(ctx, RELMC_ERR_INVALID, rs + " is not 0 with n_resources " + std::to_string(V.n_res));
-        A.rscale[r] = r < V.n_res ? s : 0.0;
-        A.rarea[r] = r < V.n_res ? V.res_area[r] : 0;
-    }
+    if (const int rc = hl1_resource_scales(ctx, who, opts->resource_scale, V.n_res, A.rscale)) return rc;
+    for (int r = 0; r < V.n_res; ++r) A.rarea[r] = V.res_area[r];
     for (int a = 0; a < RELMC_AREA_MAX; ++a) {
         const double sc = opts->load_scale[a], sh = opts->load_shift[a];
         const std::string la = who + "load_scale / load_shift of area " + std::to_string(a);
@@ -112,27 +106,15 @@ int32_t relmc_hl1_area_var(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, 
         return fail(ctx, RELMC_ERR_INVALID, who + "policy " + std::to_string(opts->policy) + " not 0 or 1");
     if (opts->flow != RELMC_HL1_AREA_FLOW_REFERENCE && opts->flow != RELMC_HL1_AREA_FLOW_MAX_FLOW)
         return fail(ctx, RELMC_ERR_INVALID, who + "flow " + std::to_string(opts->flow) + " not 0 or 1");
-    if (opts->pick != RELMC_HL1_VAR_PICK_RANDOM && opts->pick != RELMC_HL1_VAR_PICK_CYCLE)
-        return fail(ctx, RELMC_ERR_INVALID, who + "pick " + std::to_string(opts->pick) + " not 0 or 1");
-    if (opts->reserved != 0) return fail(ctx, RELMC_ERR_INVALID, who + "reserved is not 0");
-    if (n_storage < 0 || n_storage > RELMC_HL1_MAX_STORAGE)
-        return fail(ctx, RELMC_ERR_INVALID, who + "n_storage " + std::to_string(n_storage) + " not in 0.." + std::to_string(RELMC_HL1_MAX_STORAGE));
-    if (n_storage > 0 && !storage) return fail(ctx, RELMC_ERR_INVALID, who + "n_storage > 0 without storage");
-    for (int i = 0; i < n_storage; ++i) {                    // relmc_hl1_seq_storage's field checks, repeated
+    if (const int rc = hl1_pick_check(ctx, who, opts->pick, opts->reserved)) return rc;
+    if (const int rc = hl1_storage_count_check(ctx, who, n_storage, storage)) return rc;
+    for (int i = 0; i < n_storage; ++i) {
         const relmc_hl1_storage& v = storage[i].s;
         const std::string st = who + "storage " + std::to_string(i) + ": ";
         if (storage[i].area < 0 || storage[i].area >= S.n_areas)
             return fail(ctx, RELMC_ERR_INVALID, st + "area " + std::to_string(storage[i].area) + " not in 0.." + std::to_string(S.n_areas - 1));
         if (storage[i].reserved != 0) return fail(ctx, RELMC_ERR_INVALID, st + "reserved is not 0");
-        const struct { const char* name; double x; } fields[6] = {{"charge_mw", v.charge_mw}, {"discharge_mw", v.discharge_mw}, {"energy_mwh", v.energy_mwh},
-                                                                   {"eta_charge", v.eta_charge}, {"eta_discharge", v.eta_discharge}, {"soc0_mwh", v.soc0_mwh}};
-        for (const auto& f : fields)
-            if (!std::isfinite(f.x)) return fail(ctx, RELMC_ERR_INVALID, st + f.name + " not finite");
-        for (int q = 0; q < 3; ++q)
-            if (fields[q].x < 0.0) return fail(ctx, RELMC_ERR_INVALID, st + fields[q].name + " is negative");
-        for (int q = 3; q < 5; ++q)
-            if (!(fields[q].x > 0.0 && fields[q].x <= 1.0)) return fail(ctx, RELMC_ERR_INVALID, st + fields[q].name + " not in (0, 1]");
-        if (!(v.soc0_mwh >= 0.0 && v.soc0_mwh <= v.energy_mwh)) return fail(ctx, RELMC_ERR_INVALID, st + "soc0_mwh not in [0, energy_mwh]");
+        if (const int rc = hl1_storage_check(ctx, st, v)) return rc;
         A.st[i] = v; A.sarea[i] = storage[i].area;
     }
     A.n_storage = n_storage; A.n_res = V.n_res; A.n_weather = V.n_weather; A.pick = opts->pick;
@@ -140,10 +122,7 @@ int32_t relmc_hl1_area_var(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, 
     const int rows = S.n_areas + 1, slices = 2 * rows;
     std::memset(acc, 0, sizeof(*acc) * rows);
     if (n_chains == 0) return RELMC_OK;
-    if (weather_host)                                        // the device works out the same function (area_var_weather)
-        for (int64_t c = 0; c < n_chains; ++c)
-            for (int32_t y = 0; y < years_per_chain; ++y)
-                weather_host[c * years_per_chain + y] = relmc_hl1_var_weather_year(seed, first_chain + (uint64_t)c, y, years_per_chain, V.n_weather, opts->pick);
+    hl1_weather_fill(weather_host, seed, first_chain, n_chains, years_per_chain, V.n_weather, opts->pick);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool inter = opts->policy == RELMC_HL1_AREA_INTERCONNECTED;
     const int nw = (S.ngen + 31) >> 5;
@@ -177,15 +156,7 @@ int32_t relmc_hl1_area_var(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, 
                     }
         });
     if (rc) return rc;
-    for (int r = 0; r < rows; ++r) {
-        const double* s0 = sum.data() + (size_t)r * 6;
-        const double* s1 = sum.data() + (size_t)(rows + r) * 6;
-        relmc_hl1_storage_acc& o = acc[r];
-        o.years = total;
-        o.sum_lole = s0[0]; o.sum_eue = s0[1]; o.sum_lolf = s0[2]; o.sum_lole2 = s0[3]; o.sum_eue2 = s0[4]; o.sum_lolf2 = s0[5];
-        o.sum_served = s1[0]; o.sum_discharged = s1[1]; o.sum_charged = s1[2];
-        o.sum_served2 = s1[3]; o.sum_discharged2 = s1[4]; o.sum_charged2 = s1[5];
-    }
+    for (int r = 0; r < rows; ++r) hl1_storage_acc_fill(acc + r, total, sum.data() + (size_t)r * 6, sum.data() + (size_t)(rows + r) * 6);
     return RELMC_OK;
 }
 

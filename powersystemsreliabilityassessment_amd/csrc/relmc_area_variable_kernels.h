@@ -2,13 +2,11 @@
 // contract in include/relmc.h): relmc_hl1_area_kernel's chronology and transfer solve, relmc_hl1_var_kernel's weather years and resource
 // outputs in each area's capacity, and relmc_hl1_seq_storage's step rule applied area by area AFTER the transfers.  An extension beyond
 // the reference, whose areas hold dispatchable units only.
-// The transfer-solve helpers repeat relmc_area_kernels.h's and the storage helpers relmc_variable_kernels.h's under names of their own:
-// those headers define their kernels, so a second unit cannot include them, and their code objects stay what they were.
+// The transfer solve (area_bfs, area_solve, area_tie_residual) is relmc_area_kernels.h's, whose kernel is a template and is not
+// instantiated here; the weather pick and the storage leaves are relmc_hl1_storage_devfn.h's.  The area-wise storage step is this unit's.
 #pragma once
-#include <utility>
-#include "../../include/relmc.h"
-#include "relmc_devfn.h"
-#include "relmc_hl1_chrono.h"
+#include "relmc_area_kernels.h"
+#include "relmc_hl1_storage_devfn.h"
 
 namespace relmc {
 
@@ -36,58 +34,17 @@ __host__ __device__ inline int area_var_lds_rows(int na, bool inter, bool stor)
     return (na + 1) + (stor ? 2 * (na + 1) + na : 0) + na + (inter ? na * na : 0);
 }
 
-// f(integral_constant<int, i>) for i = 0 .. RELMC_HL1_MAX_STORAGE - 1, written out at compile time (hl1_var_each's pattern)
-template <class F, int... I>
-DEVFI void area_var_each_(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <class F>
-DEVFI void area_var_each(F&& f) { area_var_each_(f, std::make_integer_sequence<int, RELMC_HL1_MAX_STORAGE>{}); }
-
-// L = scale * base + shift with the product and the sum each rounded
-DEVFI double area_var_load(double scale, double ld, double shift)
-{
-#pragma clang fp contract(off)
-    const double p = scale * ld;
-    return p + shift;
-}
-
-// cap + s * v with the product and the sum each rounded
-DEVFI double area_var_add(double cap, double s, double v)
-{
-#pragma clang fp contract(off)
-    const double p = s * v;
-    return cap + p;
-}
-
-// The weather year of chain year y of `chain` (hl1_var_weather's function, verbatim; relmc_hl1_var_weather_year is the host's copy)
-DEVFI int area_var_weather(uint64_t seed, uint64_t chain, int y, int years, int n_weather, int pick)
-{
-    if (pick == RELMC_HL1_VAR_PICK_CYCLE) return (int)((chain * (uint64_t)years + (uint64_t)y) % (uint64_t)n_weather);
-    uint32_t w[4];
-    philox4x32_10((uint32_t)chain, (uint32_t)(chain >> 32), RELMC_HL1_VAR_TAG, (uint32_t)y, (uint32_t)seed, (uint32_t)(seed >> 32), w);
-    return (int)(((uint64_t)w[0] * (uint64_t)n_weather) >> 32);
-}
-
-DEVFI double area_var_readlane(double v, int src)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
-}
 // a value every lane holds alike (an LDS read at a wave-uniform address), moved to scalar registers: the tests on it are scalar branches
 DEVFI double area_var_uniform(double v)
 {
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
-// hl1_var_bits: bit i = storage i can discharge (s > 0 and discharge_mw > 0), bit 8 + i = it is not settled (s < energy_mwh and
-// charge_mw > 0)
-DEVFI uint32_t area_var_bits(const relmc_hl1_storage& p, double s, int i)
-{
-    return ((s > 0.0 && p.discharge_mw > 0.0) ? 1u << i : 0u) | ((s < p.energy_mwh && p.charge_mw > 0.0) ? 256u << i : 0u);
-}
 // the areas (bit a) that hold a storage able to discharge (low half) / not settled (high half, << 16)
 DEVFI uint32_t area_var_can(const AreaVarArgs& A, int ns, uint32_t bits)
 {
     uint32_t can = 0u;
-    area_var_each([&](auto ic) {
+    hl1_storage_each([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         if (i < ns) can |= (((bits >> i) & 1u) | (((bits >> (8 + i)) & 1u) << 16)) << A.sarea[i];
     });
@@ -102,7 +59,7 @@ DEVFI uint32_t area_var_can(const AreaVarArgs& A, int ns, uint32_t bits)
 DEVFI void area_var_storage_step(const AreaVarArgs& A, int ns, int z, int lane, int j, double* __restrict__ mgw, double* __restrict__ xyw,
                                  double& soc, uint32_t& bits)
 {
-    area_var_each([&](auto ic) {
+    hl1_storage_each([&](auto ic) {
 #pragma clang fp contract(off)
         constexpr int i = decltype(ic)::value;
         if (i < ns && ((bits >> i) & 0x101u)) {              // wave-uniform
@@ -110,7 +67,7 @@ DEVFI void area_var_storage_step(const AreaVarArgs& A, int ns, int z, int lane, 
             const int at = (A.sarea[i + z] & (AREA_MAX - 1)) * 64 + j;
             const double m = area_var_uniform(mgw[at]);
             if (m < 0.0 && ((bits >> i) & 1u)) {
-                const double need = -m, eta = p.eta_discharge, s = area_var_readlane(soc, i);
+                const double need = -m, eta = p.eta_discharge, s = hl1_storage_readlane(soc, i);
                 const double avail = __builtin_fmin(p.discharge_mw, s * eta);
                 const double x = __builtin_fmin(avail, need);
                 const double t = __builtin_fmax(0.0, s - x / eta);
@@ -118,9 +75,9 @@ DEVFI void area_var_storage_step(const AreaVarArgs& A, int ns, int z, int lane, 
                 const double xs = area_var_uniform(xyw[at]) + x;
                 if (lane == j) { mgw[at] = -left; xyw[at] = xs; }
                 soc = lane == i ? t : soc;
-                bits = (bits & ~(0x101u << i)) | area_var_bits(p, t, i);
+                bits = (bits & ~(0x101u << i)) | hl1_storage_bits(p, t, i);
             } else if (m > 0.0 && ((bits >> (8 + i)) & 1u)) {
-                const double eta = p.eta_charge, cap = p.energy_mwh, s = area_var_readlane(soc, i);
+                const double eta = p.eta_charge, cap = p.energy_mwh, s = hl1_storage_readlane(soc, i);
                 const double room = (cap - s) / eta;
                 const double y = __builtin_fmin(__builtin_fmin(p.charge_mw, room), m);
                 const double t = __builtin_fmin(cap, s + y * eta);
@@ -128,84 +85,10 @@ DEVFI void area_var_storage_step(const AreaVarArgs& A, int ns, int z, int lane, 
                 const double ys = area_var_uniform(xyw[at]) + y;
                 if (lane == j) { mgw[at] = left; xyw[at] = ys; }
                 soc = lane == i ? t : soc;
-                bits = (bits & ~(0x101u << i)) | area_var_bits(p, t, i);
+                bits = (bits & ~(0x101u << i)) | hl1_storage_bits(p, t, i);
             }
         }
     });
-}
-
-// area_bfs, under a name of this unit
-DEVFI int area_var_bfs(const double* __restrict__ mg, const double* __restrict__ R, int n, int s, int t, uint32_t& parent)
-{
-    uint32_t queue = (uint32_t)s, marked = 1u << s;
-    int head = 0, tail = 1;
-    parent = 0u;
-    while (head < tail) {
-        const int u = (int)((queue >> (4 * head)) & 15u);
-        ++head;
-        if (t >= 0 ? u == t : mg[u * 64] < -1e-4) return u;
-        for (int v = 0; v < n; ++v)
-            if (!((marked >> v) & 1u) && R[(u * n + v) * 64] > 1e-4) {
-                parent = (parent & ~(15u << (4 * v))) | ((uint32_t)u << (4 * v));
-                marked |= 1u << v;
-                queue |= (uint32_t)v << (4 * tail);
-                ++tail;
-            }
-    }
-    return -1;
-}
-
-// area_solve, under a name of this unit: the INTERCONNECTED transfer solve of one lane on its margins mg[a * 64] in LDS, in place
-template <bool COPY = true>
-DEVFI void area_var_solve(double* __restrict__ mg, double* __restrict__ R, const double* __restrict__ tie, int n, int flow)
-{
-    if constexpr (COPY)
-        for (int e = 0; e < n * n; ++e) R[e * 64] = tie[e];
-    for (int it = 0; it < AREA_MAX_AUG; ++it) {
-        int s = -1, t = -1;
-        uint32_t parent = 0u;
-        if (flow == RELMC_HL1_AREA_FLOW_REFERENCE) {
-            for (int a = 0; a < n; ++a) {
-                const double m = mg[a * 64];
-                if (s < 0 && m > 1e-4) s = a;
-                if (t < 0 && m < -1e-4) t = a;
-            }
-            if (s < 0 || t < 0 || area_var_bfs(mg, R, n, s, t, parent) < 0) return;
-        } else {
-            for (int a = 0; a < n && t < 0; ++a)
-                if (mg[a * 64] > 1e-4) { s = a; t = area_var_bfs(mg, R, n, a, -1, parent); }
-            if (t < 0) return;
-        }
-        double f = mg[s * 64], d = -mg[t * 64];
-        f = d < f ? d : f;
-        for (int v = t; v != s;) {
-            const int p = (int)((parent >> (4 * v)) & 15u);
-            const double r = R[(p * n + v) * 64];
-            f = r < f ? r : f;
-            v = p;
-        }
-        mg[s * 64] -= f;
-        mg[t * 64] += f;
-        for (int v = t; v != s;) {
-            const int p = (int)((parent >> (4 * v)) & 15u);
-            R[(p * n + v) * 64] -= f;
-            R[(v * n + p) * 64] += f;
-            v = p;
-        }
-    }
-}
-
-// area_tie_residual, under a name of this unit
-DEVFI void area_var_tie_residual(double* __restrict__ R, const AreaTies* __restrict__ TL, int n, uint32_t down)
-{
-    for (int e = 0; e < n * n; ++e) R[e * 64] = 0.0;
-    const int nt = TL->n_ties;
-    for (int t = 0; t < nt; ++t)
-        if (!((down >> t) & 1u)) {
-            const int i = TL->from[t], j = TL->to[t];
-            R[(i * n + j) * 64] += TL->cap[t];
-            R[(j * n + i) * 64] += TL->cap[t];
-        }
 }
 
 // Row r of the wave's open year: the fixed-order butterflies of the lane partials (area_close_year's, over both records); lane 0 stores
@@ -304,10 +187,10 @@ __global__ void __launch_bounds__(64) relmc_hl1_area_var_kernel(const AreaCase* 
     }
 
     double soc = 0.0;                                        // storage i's state of charge (MWh) in lane i
-    uint32_t bits = 0u;                                      // area_var_bits of every storage (wave-uniform)
-    area_var_each([&](auto ic) {
+    uint32_t bits = 0u;                                      // hl1_storage_bits of every storage (wave-uniform)
+    hl1_storage_each([&](auto ic) {
         constexpr int i = decltype(ic)::value;
-        if (i < ns) { soc = lane == i ? V.st[i].soc0_mwh : soc; bits |= area_var_bits(V.st[i], V.st[i].soc0_mwh, i); }
+        if (i < ns) { soc = lane == i ? V.st[i].soc0_mwh : soc; bits |= hl1_storage_bits(V.st[i], V.st[i].soc0_mwh, i); }
     });
     int cL[AREA_MAX + 1], cF[AREA_MAX + 1], cS[AREA_MAX + 1];   // the wave's loss hours / events / served hours of the open year, per row (uniform)
 #pragma unroll
@@ -372,14 +255,14 @@ __global__ void __launch_bounds__(64) relmc_hl1_area_var_kernel(const AreaCase* 
             while (h >= H) { h -= H; ++y; }
             uint32_t sw = 0u, lw = 0u;                       // bit a: area a is short (m'_a < 0) / long (m'_a > 0) after the transfers
             if (valid) {                                     // y < years, h < H: every read below is inside its table
-                if (y != yw) { yw = y; wb = (uint32_t)area_var_weather(seed, chain, y, years, V.n_weather, V.pick) * (uint32_t)H; }
+                if (y != yw) { yw = y; wb = (uint32_t)hl1_var_weather(seed, chain, y, years, V.n_weather, V.pick) * (uint32_t)H; }
                 const uint32_t oi = wb * (uint32_t)nres + (uint32_t)h;            // out[(w * n_res + r) * H + h], r = 0
                 double o0 = 0.0, o1 = 0.0;
                 if (nres > 0) o0 = rout[oi];                                      // wave-uniform tests
                 if (nres > 1) o1 = rout[oi + (uint32_t)H];
                 {
                     uint32_t li = ((wb * (uint32_t)na) & lmask) + (uint32_t)h;    // lcurve[(w * na + a) * H + h], a = 0
-                    for (int a = 0; a < na; ++a, li += (uint32_t)H) mg[a * 64] = area_var_load(V.lscale[a], lcurve[li], V.lshift[a]);
+                    for (int a = 0; a < na; ++a, li += (uint32_t)H) mg[a * 64] = hl1_storage_load(V.lscale[a], lcurve[li], V.lshift[a]);
                 }
                 // area a's close-out: its resources r ascending, then m_a = cap_a - L_a in L_a's slot
                 const auto close_out = [&](int a, double cap) -> bool {
@@ -387,7 +270,7 @@ __global__ void __launch_bounds__(64) relmc_hl1_area_var_kernel(const AreaCase* 
                     for (int r = 0; r < RELMC_HL1_VAR_MAX_RESOURCES; ++r)
                         if (r < nres && V.rarea[r] == a) {                        // wave-uniform
                             const double o = r == 0 ? o0 : r == 1 ? o1 : rout[oi + (uint32_t)r * (uint32_t)H];
-                            cap = area_var_add(cap, V.rscale[r], o);
+                            cap = hl1_var_add(cap, V.rscale[r], o);
                         }
                     const double m = cap - mg[a * 64];
                     mg[a * 64] = m;
@@ -412,10 +295,10 @@ __global__ void __launch_bounds__(64) relmc_hl1_area_var_kernel(const AreaCase* 
                 if constexpr (TIES) {
                     if (inter && neg) {
                         const uint32_t tdown = seg[nw][i];
-                        if (tdown) { area_var_tie_residual(R, TL, na, tdown); area_var_solve<false>(mg, R, nullptr, na, flow); }
-                        else area_var_solve(mg, R, A->tie, na, flow);
+                        if (tdown) { area_tie_residual(R, TL, na, tdown); area_solve<false>(mg, R, nullptr, na, flow); }
+                        else area_solve(mg, R, A->tie, na, flow);
                     }
-                } else if (inter && neg) area_var_solve(mg, R, A->tie, na, flow);
+                } else if (inter && neg) area_solve(mg, R, A->tie, na, flow);
 #pragma unroll
                 for (int r = 0; r < AREA_MAX; ++r) {
                     if (r >= na) break;

@@ -1,5 +1,6 @@
 // relmc_hl1_host.h — host code the HL1 record models share: the unit and argument checks, the chunk rule, and the one loop that launches
-// a model chunk by chunk and sums its year records (hl1_run_records).  Host only.  `who` is the calling function's name, for the message.
+// a model chunk by chunk and sums its year records (hl1_run_records), and the checks and fills of the storage and weather-year tracks.
+// Host only.  `who` is the calling function's name, for the message.
 // The buffer pair of a model, Hl1Records, is in relmc_ctx.h: the context holds one per model by value.
 #pragma once
 #include <algorithm>
@@ -83,6 +84,80 @@ inline void hl1_rows_to_host(const std::vector<double>& stage, int n_levels, int
                 const double* s = stage.data() + ((size_t)(j * rows + r) * nrec + i) * 3;
                 o.lole = s[0]; o.eue = s[1]; o.lolf = s[2];
             }
+}
+
+// ---- what the storage and weather-year entry points check and fill alike: relmc_hl1_seq_storage, relmc_hl1_var_seq, relmc_hl1_stress_seq
+// and relmc_hl1_area_var.  Here `who` is the message prefix "<function>: ".  Each entry point calls these in the order of its contract.
+
+// n_storage in 0 .. RELMC_HL1_MAX_STORAGE, and an array to go with a positive count
+inline int hl1_storage_count_check(relmc_ctx* ctx, const std::string& who, int32_t n_storage, const void* storage)
+{
+    if (n_storage < 0 || n_storage > RELMC_HL1_MAX_STORAGE)
+        return fail(ctx, RELMC_ERR_INVALID, who + "n_storage " + std::to_string(n_storage) + " not in 0.." + std::to_string(RELMC_HL1_MAX_STORAGE));
+    if (n_storage > 0 && !storage) return fail(ctx, RELMC_ERR_INVALID, who + "n_storage > 0 without storage");
+    return RELMC_OK;
+}
+// The field rule of one storage (include/relmc.h): every field finite, the powers and the energy not negative, the efficiencies in
+// (0, 1], soc0_mwh in [0, energy_mwh].  st is the message prefix "<function>: storage <i>: ".
+inline int hl1_storage_check(relmc_ctx* ctx, const std::string& st, const relmc_hl1_storage& v)
+{
+    const struct { const char* name; double x; } fields[6] = {{"charge_mw", v.charge_mw}, {"discharge_mw", v.discharge_mw}, {"energy_mwh", v.energy_mwh},
+                                                               {"eta_charge", v.eta_charge}, {"eta_discharge", v.eta_discharge}, {"soc0_mwh", v.soc0_mwh}};
+    for (const auto& f : fields)
+        if (!std::isfinite(f.x)) return fail(ctx, RELMC_ERR_INVALID, st + f.name + " not finite");
+    for (int q = 0; q < 3; ++q)
+        if (fields[q].x < 0.0) return fail(ctx, RELMC_ERR_INVALID, st + fields[q].name + " is negative");
+    for (int q = 3; q < 5; ++q)
+        if (!(fields[q].x > 0.0 && fields[q].x <= 1.0)) return fail(ctx, RELMC_ERR_INVALID, st + fields[q].name + " not in (0, 1]");
+    if (!(v.soc0_mwh >= 0.0 && v.soc0_mwh <= v.energy_mwh)) return fail(ctx, RELMC_ERR_INVALID, st + "soc0_mwh not in [0, energy_mwh]");
+    return RELMC_OK;
+}
+// resource_scale[RELMC_HL1_VAR_MAX_RESOURCES] of the options against a library of n_res resources: finite, not negative, 0 beyond n_res;
+// fills rscale[] (0.0 beyond n_res)
+inline int hl1_resource_scales(relmc_ctx* ctx, const std::string& who, const double* resource_scale, int n_res, double* rscale)
+{
+    for (int r = 0; r < RELMC_HL1_VAR_MAX_RESOURCES; ++r) {
+        const double s = resource_scale[r];
+        const std::string rs = who + "resource_scale " + std::to_string(r);
+        if (!std::isfinite(s)) return fail(ctx, RELMC_ERR_INVALID, rs + " not finite");
+        if (s < 0.0) return fail(ctx, RELMC_ERR_INVALID, rs + " is negative");
+        if (r >= n_res && s != 0.0) return fail(ctx, RELMC_ERR_INVALID, rs + " is not 0 with n_resources " + std::to_string(n_res));
+        rscale[r] = r < n_res ? s : 0.0;
+    }
+    return RELMC_OK;
+}
+inline int hl1_pick_check(relmc_ctx* ctx, const std::string& who, int32_t pick, int32_t reserved)
+{
+    if (pick != RELMC_HL1_VAR_PICK_RANDOM && pick != RELMC_HL1_VAR_PICK_CYCLE)
+        return fail(ctx, RELMC_ERR_INVALID, who + "pick " + std::to_string(pick) + " not 0 or 1");
+    if (reserved != 0) return fail(ctx, RELMC_ERR_INVALID, who + "reserved is not 0");
+    return RELMC_OK;
+}
+// weather_host[chain of the call][year] (nullptr: not wanted): the function the device works out (hl1_var_weather); the arguments are in range
+inline void hl1_weather_fill(int32_t* weather_host, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain, int32_t n_weather, int32_t pick)
+{
+    if (!weather_host) return;
+    for (int64_t c = 0; c < n_chains; ++c)
+        for (int32_t y = 0; y < years_per_chain; ++y)
+            weather_host[c * years_per_chain + y] = relmc_hl1_var_weather_year(seed, first_chain + (uint64_t)c, y, years_per_chain, n_weather, pick);
+}
+// `copies` of the sequential storage-record models: the launch's two rows rec[row][nrec][3], the first record being record first_rec of the
+// call, to the host arrays that were asked for
+inline int hl1_two_row_copies(relmc_ctx* ctx, const double* rec, int64_t first_rec, int64_t nrec, relmc_hl1_seq_year* years_host,
+                              relmc_hl1_storage_year* storage_years_host)
+{
+    if (years_host) HIP_TRY(ctx, hipMemcpyAsync(years_host + first_rec, rec, sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
+    if (storage_years_host)
+        HIP_TRY(ctx, hipMemcpyAsync(storage_years_host + first_rec, rec + (size_t)nrec * 3, sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
+    return RELMC_OK;
+}
+// hl1_acc_fill's companion: s0 = the six sums of (lole, eue, lolf), s1 = those of (served_hours, discharged_mwh, charged_mwh)
+inline void hl1_storage_acc_fill(relmc_hl1_storage_acc* acc, int64_t years, const double* s0, const double* s1)
+{
+    acc->years = years;
+    acc->sum_lole = s0[0]; acc->sum_eue = s0[1]; acc->sum_lolf = s0[2]; acc->sum_lole2 = s0[3]; acc->sum_eue2 = s0[4]; acc->sum_lolf2 = s0[5];
+    acc->sum_served = s1[0]; acc->sum_discharged = s1[1]; acc->sum_charged = s1[2];
+    acc->sum_served2 = s1[3]; acc->sum_discharged2 = s1[4]; acc->sum_charged2 = s1[5];
 }
 
 }  // namespace relmc_host

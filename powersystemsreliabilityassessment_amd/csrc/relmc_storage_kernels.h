@@ -2,11 +2,10 @@
 // include/relmc.h): one walk of a chain's fleet history against the load L(h) = scale * load[h] + shift, with up to
 // RELMC_HL1_MAX_STORAGE storages that discharge into a shortfall and charge from surplus generation.  An extension beyond the reference
 // (its only energy-limited resource, the ELU of the planning model, drains and never recharges, on an hourly-sampling Monte Carlo).
+// The storage step, the wave-uniform bits and the year close are relmc_hl1_storage_devfn.h's, shared with the weather-year kernels.
 #pragma once
-#include <utility>
-#include "../../include/relmc.h"
-#include "relmc_devfn.h"
 #include "relmc_hl1_chrono.h"
+#include "relmc_hl1_storage_devfn.h"
 
 namespace relmc {
 
@@ -17,98 +16,6 @@ struct Hl1StorageArgs {
     double scale, shift;
     int32_t n_storage, pad;
 };
-
-// f(integral_constant<int, i>) for i = 0 .. RELMC_HL1_MAX_STORAGE - 1, written out at compile time (as hl1_sweep_levels): a storage's
-// state of charge is a register named by a constant, never a run-time index into a per-thread array (scratch)
-template <class F, int... I>
-DEVFI void hl1_storage_each_(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <class F>
-DEVFI void hl1_storage_each(F&& f) { hl1_storage_each_(f, std::make_integer_sequence<int, RELMC_HL1_MAX_STORAGE>{}); }
-
-// L(h) = scale * load + shift with the product and the sum each rounded (hl1_sweep_load's rule, stated to the compiler the same way)
-DEVFI double hl1_storage_load(double scale, double ld, double shift)
-{
-#pragma clang fp contract(off)
-    const double p = scale * ld;
-    return p + shift;
-}
-
-DEVFI double hl1_storage_readlane(double v, int src)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
-}
-
-// What storage i can still do at the state of charge s, as two wave-uniform bits: bit i = it can discharge (s > 0 and discharge_mw > 0),
-// bit 8 + i = it is not settled (s < energy_mwh and charge_mw > 0).  With the bit clear the contract's step leaves the storage, the
-// need / surplus and the sums as they are (avail or y is 0), so such a storage is passed over.
-DEVFI uint32_t hl1_storage_bits(const relmc_hl1_storage& p, double s, int i)
-{
-    return ((s > 0.0 && p.discharge_mw > 0.0) ? 1u << i : 0u) | ((s < p.energy_mwh && p.charge_mw > 0.0) ? 256u << i : 0u);
-}
-
-// The contract's short step.  soc: storage i's state of charge in lane i (read and written through the lane; one register pair instead
-// of eight); bits: hl1_storage_bits of every storage; z: a zero the compiler cannot see through, so that a storage's data is read from
-// the kernel argument segment here, where it is used, and is not 96 scalar registers live across the whole chain.
-// need -> what is left of it, xs = the sum of the x; every operation rounded once.
-DEVFI void hl1_storage_discharge(const Hl1StorageArgs& A, int ns, int z, int lane, double& soc, uint32_t& bits, double& need, double& xs)
-{
-    hl1_storage_each([&](auto ic) {
-#pragma clang fp contract(off)
-        constexpr int i = decltype(ic)::value;
-        if (i < ns && need > 0.0 && ((bits >> i) & 1u)) {    // wave-uniform
-            const relmc_hl1_storage& p = A.st[i + z];
-            const double eta = p.eta_discharge, s = hl1_storage_readlane(soc, i);
-            const double avail = __builtin_fmin(p.discharge_mw, s * eta);
-            const double x = __builtin_fmin(avail, need);
-            const double t = __builtin_fmax(0.0, s - x / eta);
-            need = need - x;
-            xs = xs + x;
-            soc = lane == i ? t : soc;
-            bits = (bits & ~(0x101u << i)) | hl1_storage_bits(p, t, i);
-        }
-    });
-}
-
-// The contract's long step: ys = the sum of the y
-DEVFI void hl1_storage_charge(const Hl1StorageArgs& A, int ns, int z, int lane, double& soc, uint32_t& bits, double surplus, double& ys)
-{
-    hl1_storage_each([&](auto ic) {
-#pragma clang fp contract(off)
-        constexpr int i = decltype(ic)::value;
-        if (i < ns && surplus > 0.0 && ((bits >> (8 + i)) & 1u)) {      // wave-uniform
-            const relmc_hl1_storage& p = A.st[i + z];
-            const double eta = p.eta_charge, cap = p.energy_mwh, s = hl1_storage_readlane(soc, i);
-            const double room = (cap - s) / eta;
-            const double y = __builtin_fmin(__builtin_fmin(p.charge_mw, room), surplus);
-            const double t = __builtin_fmin(cap, s + y * eta);
-            surplus = surplus - y;
-            ys = ys + y;
-            soc = lane == i ? t : soc;
-            bits = (bits & ~(0x101u << i)) | hl1_storage_bits(p, t, i);
-        }
-    });
-}
-
-// This lane's partials of the open year.  Loss hours, loss events and served hours are counts (exact in any order); the three energies are
-// fp64 sums over the lane's steps of the year in ascending order, as relmc_hl1_seq_kernel's EUE partial.
-struct Hl1StoragePartials { uint32_t lole, lolf, served; double eue, dis, chg; };
-
-// The wave's open year: relmc_hl1_seq_kernel's fixed-order butterfly (hl1_seq_close_year) over the lanes' partials of both records;
-// lane 0 stores (lole, eue, lolf) and (served_hours, discharged_mwh, charged_mwh); the partials restart at zero
-DEVFI void hl1_storage_close_year(Hl1StoragePartials& a, double* __restrict__ out0, double* __restrict__ out1)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a.lole += (uint32_t)__shfl_xor((int)a.lole, off); a.lolf += (uint32_t)__shfl_xor((int)a.lolf, off); a.served += (uint32_t)__shfl_xor((int)a.served, off);
-        a.eue += __shfl_xor(a.eue, off); a.dis += __shfl_xor(a.dis, off); a.chg += __shfl_xor(a.chg, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        out0[0] = (double)a.lole; out0[1] = a.eue; out0[2] = (double)a.lolf;
-        out1[0] = (double)a.served; out1[1] = a.dis; out1[2] = a.chg;
-    }
-    a.lole = a.lolf = a.served = 0u;
-    a.eue = a.dis = a.chg = 0.0;
-}
 
 // Chain c = blockIdx.x * 4 + wave; the chronology is relmc_hl1_seq_kernel's, word for word (lane l owns units l and l + 64, windows of
 // HL1_SEQ_WINDOW steps filled into the wave's LDS masks, one step per lane, no workgroup barrier).  The window loop below is a COPY of

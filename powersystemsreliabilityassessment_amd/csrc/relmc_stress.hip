@@ -1,7 +1,8 @@
 // relmc_stress.hip — weather-dependent forced outage rates on the HL1 sequential chronology (relmc_hl1_stress_load, relmc_hl1_stress_seq,
 // relmc_hl1_stress_cumulative, relmc_hl1_stress_failure_time, contract in include/relmc.h): the fleet of relmc_hl1_seq_load against the
 // weather library of relmc_hl1_var_load, with a failure-rate multiplier per weather year, outage class and hour in a slot of its own.
-// A unit of its own, so that the code objects of relmc_seq.hip, relmc_storage.hip and relmc_variable.hip stay what they were.  The two
+// A unit of its own, so that the code objects of relmc_seq.hip, relmc_storage.hip and relmc_variable.hip stay what they were; the option
+// and storage checks, the weather_host fill, the copies and the accumulator fill are relmc_hl1_host.h's, shared with those units.  The two
 // rows of year records are summed by relmc_hl1_reduce_kernel (hl1_reduce_queue, relmc_seq.hip), one row at a time.
 #include <algorithm>
 #include <cmath>
@@ -109,32 +110,13 @@ int32_t relmc_hl1_stress_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain
     if (!opts) return fail(ctx, RELMC_ERR_INVALID, who + "opts is null");
     if (!std::isfinite(opts->scale) || !std::isfinite(opts->shift)) return fail(ctx, RELMC_ERR_INVALID, who + "scale / shift not finite");
     relmc::Hl1StressArgs A; std::memset(&A, 0, sizeof(A));
-    for (int r = 0; r < RELMC_HL1_VAR_MAX_RESOURCES; ++r) {  // relmc_hl1_var_seq's checks, repeated
-        const double s = opts->resource_scale[r];
-        const std::string rs = who + "resource_scale " + std::to_string(r);
-        if (!std::isfinite(s)) return fail(ctx, RELMC_ERR_INVALID, rs + " not finite");
-        if (s < 0.0) return fail(ctx, RELMC_ERR_INVALID, rs + " is negative");
-        if (r >= V.n_res && s != 0.0) return fail(ctx, RELMC_ERR_INVALID, rs + " is not 0 with n_resources " + std::to_string(V.n_res));
-        A.rscale[r] = r < V.n_res ? s : 0.0;
-    }
-    if (opts->pick != RELMC_HL1_VAR_PICK_RANDOM && opts->pick != RELMC_HL1_VAR_PICK_CYCLE)
-        return fail(ctx, RELMC_ERR_INVALID, who + "pick " + std::to_string(opts->pick) + " not 0 or 1");
-    if (opts->reserved != 0) return fail(ctx, RELMC_ERR_INVALID, who + "reserved is not 0");
-    if (n_storage < 0 || n_storage > RELMC_HL1_MAX_STORAGE)
-        return fail(ctx, RELMC_ERR_INVALID, who + "n_storage " + std::to_string(n_storage) + " not in 0.." + std::to_string(RELMC_HL1_MAX_STORAGE));
-    if (n_storage > 0 && !storage) return fail(ctx, RELMC_ERR_INVALID, who + "n_storage > 0 without storage");
-    for (int i = 0; i < n_storage; ++i) {                    // relmc_hl1_seq_storage's field checks, repeated
+    if (const int rc = hl1_resource_scales(ctx, who, opts->resource_scale, V.n_res, A.rscale)) return rc;
+    if (const int rc = hl1_pick_check(ctx, who, opts->pick, opts->reserved)) return rc;
+    if (const int rc = hl1_storage_count_check(ctx, who, n_storage, storage)) return rc;
+    for (int i = 0; i < n_storage; ++i) {
         const relmc_hl1_storage& v = storage[i];
         const std::string st = who + "storage " + std::to_string(i) + ": ";
-        const struct { const char* name; double x; } fields[6] = {{"charge_mw", v.charge_mw}, {"discharge_mw", v.discharge_mw}, {"energy_mwh", v.energy_mwh},
-                                                                   {"eta_charge", v.eta_charge}, {"eta_discharge", v.eta_discharge}, {"soc0_mwh", v.soc0_mwh}};
-        for (const auto& f : fields)
-            if (!std::isfinite(f.x)) return fail(ctx, RELMC_ERR_INVALID, st + f.name + " not finite");
-        for (int q = 0; q < 3; ++q)
-            if (fields[q].x < 0.0) return fail(ctx, RELMC_ERR_INVALID, st + fields[q].name + " is negative");
-        for (int q = 3; q < 5; ++q)
-            if (!(fields[q].x > 0.0 && fields[q].x <= 1.0)) return fail(ctx, RELMC_ERR_INVALID, st + fields[q].name + " not in (0, 1]");
-        if (!(v.soc0_mwh >= 0.0 && v.soc0_mwh <= v.energy_mwh)) return fail(ctx, RELMC_ERR_INVALID, st + "soc0_mwh not in [0, energy_mwh]");
+        if (const int rc = hl1_storage_check(ctx, st, v)) return rc;
         A.st[i] = v;
     }
     A.scale = opts->scale; A.shift = opts->shift; A.n_storage = n_storage;
@@ -143,10 +125,7 @@ int32_t relmc_hl1_stress_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain
     A.cum = X.cum.get(); A.ucls = X.ucls.get(); A.n_classes = X.n_classes;
     std::memset(acc, 0, sizeof(*acc));
     if (n_chains == 0) return RELMC_OK;
-    if (weather_host)                                        // the device works out the same function (hl1_stress_weather)
-        for (int64_t c = 0; c < n_chains; ++c)
-            for (int32_t y = 0; y < years_per_chain; ++y)
-                weather_host[c * years_per_chain + y] = relmc_hl1_var_weather_year(seed, first_chain + (uint64_t)c, y, years_per_chain, V.n_weather, opts->pick);
+    hl1_weather_fill(weather_host, seed, first_chain, n_chains, years_per_chain, V.n_weather, opts->pick);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     double sum[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const int64_t per = hl1_chunk_items(n_chains, kHl1RecordBudget, (int64_t)years_per_chain * 2);             // a chain counts its records of both rows
@@ -155,20 +134,10 @@ int32_t relmc_hl1_stress_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain
             hipLaunchKernelGGL(relmc::relmc_hl1_stress_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
                                first_chain + (uint64_t)c0, nc, years_per_chain, start, A, X.rec.years.get());
         },
-        [&](int64_t c0, int64_t, int64_t nrec) -> int {
-            if (years_host)
-                HIP_TRY(ctx, hipMemcpyAsync(years_host + c0 * years_per_chain, X.rec.years.get(), sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
-            if (storage_years_host)
-                HIP_TRY(ctx, hipMemcpyAsync(storage_years_host + c0 * years_per_chain, X.rec.years.get() + (size_t)nrec * 3, sizeof(double) * 3 * nrec,
-                                            hipMemcpyDeviceToHost, ctx->stream));
-            return RELMC_OK;
-        },
+        [&](int64_t c0, int64_t, int64_t nrec) { return hl1_two_row_copies(ctx, X.rec.years.get(), c0 * years_per_chain, nrec, years_host, storage_years_host); },
         hl1_no_host_step);
     if (rc) return rc;
-    acc->years = n_chains * years_per_chain;
-    acc->sum_lole = sum[0]; acc->sum_eue = sum[1]; acc->sum_lolf = sum[2]; acc->sum_lole2 = sum[3]; acc->sum_eue2 = sum[4]; acc->sum_lolf2 = sum[5];
-    acc->sum_served = sum[6]; acc->sum_discharged = sum[7]; acc->sum_charged = sum[8];
-    acc->sum_served2 = sum[9]; acc->sum_discharged2 = sum[10]; acc->sum_charged2 = sum[11];
+    hl1_storage_acc_fill(acc, n_chains * years_per_chain, sum, sum + 6);
     return RELMC_OK;
 }
 

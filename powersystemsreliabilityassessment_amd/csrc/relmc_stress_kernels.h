@@ -3,13 +3,10 @@
 // fail_mult[w(y)][c][h] / mttf in hour h of chain year y.  The time of a failure is no longer T + E: the draw E = -mttf * ln U is spent
 // along the cumulative multiplier table G of the unit's class, year by year (hl1_stress_failure_time, compiled for the host and the
 // device from this one text).  An extension beyond the reference, whose units have constant rates.
-// The helpers of the resources, the storages and the year close repeat relmc_variable_kernels.h's under names of their own: that header
-// defines its kernel, so a second unit cannot include it, and relmc_variable.hip's code object stays what it was.
+// The helpers of the resources, the storages and the year close are relmc_hl1_storage_devfn.h's, shared with relmc_hl1_var_kernel.
 #pragma once
-#include <utility>
-#include "../../include/relmc.h"
-#include "relmc_devfn.h"
 #include "relmc_hl1_chrono.h"
+#include "relmc_hl1_storage_devfn.h"
 
 namespace relmc {
 
@@ -70,110 +67,12 @@ struct Hl1StressArgs {
     int32_t n_storage, n_res, n_weather, pick, n_classes, reserved;
 };
 
-template <class F, int... I>
-DEVFI void hl1_stress_each_(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <class F>
-DEVFI void hl1_stress_each(F&& f) { hl1_stress_each_(f, std::make_integer_sequence<int, RELMC_HL1_MAX_STORAGE>{}); }
-
-// L = scale * base + shift with the product and the sum each rounded
-DEVFI double hl1_stress_load(double scale, double ld, double shift)
-{
-#pragma clang fp contract(off)
-    const double p = scale * ld;
-    return p + shift;
-}
-
-// cap + s * v with the product and the sum each rounded
-DEVFI double hl1_stress_add(double cap, double s, double v)
-{
-#pragma clang fp contract(off)
-    const double p = s * v;
-    return cap + p;
-}
-
-// hl1_var_weather, verbatim: the weather year of chain year y of `chain`
-DEVFI int hl1_stress_weather(uint64_t seed, uint64_t chain, int y, int years, int n_weather, int pick)
-{
-    if (pick == RELMC_HL1_VAR_PICK_CYCLE) return (int)((chain * (uint64_t)years + (uint64_t)y) % (uint64_t)n_weather);
-    uint32_t w[4];
-    philox4x32_10((uint32_t)chain, (uint32_t)(chain >> 32), RELMC_HL1_VAR_TAG, (uint32_t)y, (uint32_t)seed, (uint32_t)(seed >> 32), w);
-    return (int)(((uint64_t)w[0] * (uint64_t)n_weather) >> 32);
-}
-
-DEVFI double hl1_stress_readlane(double v, int src)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
-}
-
-// bit i = storage i can discharge, bit 8 + i = it is not settled (hl1_var_bits)
-DEVFI uint32_t hl1_stress_bits(const relmc_hl1_storage& p, double s, int i)
-{
-    return ((s > 0.0 && p.discharge_mw > 0.0) ? 1u << i : 0u) | ((s < p.energy_mwh && p.charge_mw > 0.0) ? 256u << i : 0u);
-}
-
-// The contract's short step (hl1_var_discharge)
-DEVFI void hl1_stress_discharge(const Hl1StressArgs& A, int ns, int z, int lane, double& soc, uint32_t& bits, double& need, double& xs)
-{
-    hl1_stress_each([&](auto ic) {
-#pragma clang fp contract(off)
-        constexpr int i = decltype(ic)::value;
-        if (i < ns && need > 0.0 && ((bits >> i) & 1u)) {    // wave-uniform
-            const relmc_hl1_storage& p = A.st[i + z];
-            const double eta = p.eta_discharge, s = hl1_stress_readlane(soc, i);
-            const double avail = __builtin_fmin(p.discharge_mw, s * eta);
-            const double x = __builtin_fmin(avail, need);
-            const double t = __builtin_fmax(0.0, s - x / eta);
-            need = need - x;
-            xs = xs + x;
-            soc = lane == i ? t : soc;
-            bits = (bits & ~(0x101u << i)) | hl1_stress_bits(p, t, i);
-        }
-    });
-}
-
-// The contract's long step (hl1_var_charge)
-DEVFI void hl1_stress_charge(const Hl1StressArgs& A, int ns, int z, int lane, double& soc, uint32_t& bits, double surplus, double& ys)
-{
-    hl1_stress_each([&](auto ic) {
-#pragma clang fp contract(off)
-        constexpr int i = decltype(ic)::value;
-        if (i < ns && surplus > 0.0 && ((bits >> (8 + i)) & 1u)) {      // wave-uniform
-            const relmc_hl1_storage& p = A.st[i + z];
-            const double eta = p.eta_charge, cap = p.energy_mwh, s = hl1_stress_readlane(soc, i);
-            const double room = (cap - s) / eta;
-            const double y = __builtin_fmin(__builtin_fmin(p.charge_mw, room), surplus);
-            const double t = __builtin_fmin(cap, s + y * eta);
-            surplus = surplus - y;
-            ys = ys + y;
-            soc = lane == i ? t : soc;
-            bits = (bits & ~(0x101u << i)) | hl1_stress_bits(p, t, i);
-        }
-    });
-}
-
-// This lane's partials of the open year, and the year's close (hl1_var_close_year: the fixed-order butterfly over both records)
-struct Hl1StressPartials { uint32_t lole, lolf, served; double eue, dis, chg; };
-DEVFI void hl1_stress_close_year(Hl1StressPartials& a, double* __restrict__ out0, double* __restrict__ out1)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a.lole += (uint32_t)__shfl_xor((int)a.lole, off); a.lolf += (uint32_t)__shfl_xor((int)a.lolf, off); a.served += (uint32_t)__shfl_xor((int)a.served, off);
-        a.eue += __shfl_xor(a.eue, off); a.dis += __shfl_xor(a.dis, off); a.chg += __shfl_xor(a.chg, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        out0[0] = (double)a.lole; out0[1] = a.eue; out0[2] = (double)a.lolf;
-        out1[0] = (double)a.served; out1[1] = a.dis; out1[2] = a.chg;
-    }
-    a.lole = a.lolf = a.served = 0u;
-    a.eue = a.dis = a.chg = 0.0;
-}
-
 // Chain c = blockIdx.x * 4 + wave.  The window loop, the group stages and the year close are a COPY of relmc_hl1_var_kernel's
 // (relmc_variable_kernels.h, which says what they do), on purpose: sharing the loop between kernels has cost the older kernels time
 // (DESIGN.md 6.12), and that kernel's code object must not change.  What is new is the transition of stage (1):
 //   class      lane l keeps the classes of its units l and l + 64 in registers (cls[s], -1: the unit ignores the weather)
 //   failure    a lane whose unit has just become UP and has a class runs hl1_stress_failure_time instead of the addition: a walk over the
-//              years the draw outlasts (bounded by `years`; the weather year of each from hl1_stress_weather), then a binary search of at
+//              years the draw outlasts (bounded by `years`; the weather year of each from hl1_var_weather), then a binary search of at
 //              most ceil(log2 H) probes over one row of G in global memory, which every chain reads and L2 keeps.  These lanes diverge
 //              from the others inside `while (__any(more))`; the loop's trip count is what it was, one trip per transition of the busiest lane
 //   never      a unit that does not fail again gets years * H + 1, beyond every window: its cursor waits for the rest of the chain
@@ -211,7 +110,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     // the failure time of a unit of class c that became UP at T with the draw E (c >= 0; G's row of (w, c) starts at (w * ncls + c) * (H + 1))
     auto fail_at = [&](double T, double E, int c) {
         return hl1_stress_failure_time(T, E, H, years, [&](int y) {
-            return cum + ((uint32_t)hl1_stress_weather(seed, chain, y, years, A.n_weather, A.pick) * ncls + (uint32_t)c) * H1;
+            return cum + ((uint32_t)hl1_var_weather(seed, chain, y, years, A.n_weather, A.pick) * ncls + (uint32_t)c) * H1;
         });
     };
 #pragma unroll
@@ -230,12 +129,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     }
 
     double soc = 0.0;                                        // storage i's state of charge (MWh) in lane i
-    uint32_t bits = 0u;                                      // hl1_stress_bits of every storage (wave-uniform)
-    hl1_stress_each([&](auto ic) {
+    uint32_t bits = 0u;                                      // hl1_storage_bits of every storage (wave-uniform)
+    hl1_storage_each([&](auto ic) {
         constexpr int i = decltype(ic)::value;
-        if (i < ns) { soc = lane == i ? A.st[i].soc0_mwh : soc; bits |= hl1_stress_bits(A.st[i], A.st[i].soc0_mwh, i); }
+        if (i < ns) { soc = lane == i ? A.st[i].soc0_mwh : soc; bits |= hl1_storage_bits(A.st[i], A.st[i].soc0_mwh, i); }
     });
-    Hl1StressPartials a = {0u, 0u, 0u, 0.0, 0.0, 0.0};      // this lane's partials of the open year ycur
+    Hl1StoragePartials a = {0u, 0u, 0u, 0.0, 0.0, 0.0};      // this lane's partials of the open year ycur
     int ycur = 0, gy = 0, gh = 0;                            // gy / gh: chain year and hour of the current 64-step group's first step
     int yw = -1;                                             // this lane's cached chain year, and
     uint32_t wb = 0u;                                        // w * H of its weather year w (relmc_hl1_var_load: n_weather * n_res * H < 2^31)
@@ -288,7 +187,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
             bool sh = false, lg = false;                     // short: cap < L, long: cap > L
             double m = 0.0;                                  // the step's need (short) or surplus (long)
             if (valid) {                                     // y < years, h < H: every read below is inside its table
-                if (y != yw) { yw = y; wb = (uint32_t)hl1_stress_weather(seed, chain, y, years, A.n_weather, A.pick) * (uint32_t)H; }
+                if (y != yw) { yw = y; wb = (uint32_t)hl1_var_weather(seed, chain, y, years, A.n_weather, A.pick) * (uint32_t)H; }
                 // the step's load and its first two outputs are read BEFORE the capacity sum, whose work hides their latency
                 const double ld = lcurve[(wb & lmask) + (uint32_t)h];
                 uint32_t oi = wb * (uint32_t)nres + (uint32_t)h;                  // out[(w * n_res + r) * H + h], r = 0
@@ -301,16 +200,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                     const int kn = ngen - 32 * q < 32 ? ngen - 32 * q : 32;
                     for (int b = 0; b < kn; ++b) cap += ((up >> b) & 1u) ? S->cap[32 * q + b] : 0.0;   // ascending units; + 0.0 is exact
                 }
-                if (nres > 0) cap = hl1_stress_add(cap, A.rscale[0], o0);
-                if (nres > 1) cap = hl1_stress_add(cap, A.rscale[1], o1);
+                if (nres > 0) cap = hl1_var_add(cap, A.rscale[0], o0);
+                if (nres > 1) cap = hl1_var_add(cap, A.rscale[1], o1);
                 for (int r = 2; r < nres; r += 2) {                               // the others two at a time: one wait per pair
                     const uint32_t oj = oi + (uint32_t)r * (uint32_t)H;
                     const bool two = r + 1 < nres;
                     const double a = rout[oj], b = two ? rout[oj + (uint32_t)H] : 0.0;
-                    cap = hl1_stress_add(cap, A.rscale[r], a);
-                    if (two) cap = hl1_stress_add(cap, A.rscale[r + 1], b);
+                    cap = hl1_var_add(cap, A.rscale[r], a);
+                    if (two) cap = hl1_var_add(cap, A.rscale[r + 1], b);
                 }
-                const double L = hl1_stress_load(A.scale, ld, A.shift);
+                const double L = hl1_storage_load(A.scale, ld, A.shift);
                 sh = cap < L; lg = cap > L;
                 m = sh ? L - cap : lg ? cap - L : 0.0;
             }
@@ -325,14 +224,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                     if (todo == 0) break;
                     const int j = __builtin_ctzll(todo);
                     rest = j == 63 ? 0ull : ~0ull << (j + 1);
-                    const double mj = hl1_stress_readlane(m, j);
+                    const double mj = hl1_storage_readlane(m, j);
                     if ((ms >> j) & 1ull) {
                         double need = mj, x = 0.0;
-                        hl1_stress_discharge(A, ns, z, lane, soc, bits, need, x);
+                        hl1_storage_discharge(A, ns, z, lane, soc, bits, need, x);
                         if (lane == j) { m = need; xy = x; }     // m: what is left of the need
                     } else {
                         double yj = 0.0;
-                        hl1_stress_charge(A, ns, z, lane, soc, bits, mj, yj);
+                        hl1_storage_charge(A, ns, z, lane, soc, bits, mj, yj);
                         if (lane == j) xy = yj;
                     }
                 }
@@ -346,7 +245,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                         a.eue += f ? m : 0.0; a.dis += sh ? xy : 0.0; a.chg += sh ? 0.0 : xy;
                     }
                     if (!__any(valid && y > ycur)) break;
-                    hl1_stress_close_year(a, out0 + (size_t)ycur * 3, out1 + (size_t)ycur * 3);
+                    hl1_storage_close_year(a, out0 + (size_t)ycur * 3, out1 + (size_t)ycur * 3);
                     ++ycur;
                 }
             } else prev = false;
@@ -355,6 +254,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
         }
         hl1_seq_wave_sync();
     }
-    for (; ycur < years; ++ycur) hl1_stress_close_year(a, out0 + (size_t)ycur * 3, out1 + (size_t)ycur * 3);
+    for (; ycur < years; ++ycur) hl1_storage_close_year(a, out0 + (size_t)ycur * 3, out1 + (size_t)ycur * 3);
 }
 }  // namespace relmc

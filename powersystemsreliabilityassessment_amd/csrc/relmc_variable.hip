@@ -1,7 +1,8 @@
 // relmc_variable.hip — weather-year wind and solar resources on the HL1 sequential chronology, with storage (relmc_hl1_var_load,
 // relmc_hl1_var_seq, relmc_hl1_var_weather_year, contract in include/relmc.h): the fleet of relmc_hl1_seq_load (relmc_seq.hip) against a
 // weather library in a slot of its own, with the storages of relmc_hl1_seq_storage given in the call.  A unit of its own, so that the
-// code objects of relmc_seq.hip and relmc_storage.hip stay what they were.  The two rows of year records, (lole, eue, lolf) and
+// code objects of relmc_seq.hip and relmc_storage.hip stay what they were; the option and storage checks, the weather_host fill, the copies
+// and the accumulator fill are relmc_hl1_host.h's, the device leaves relmc_hl1_storage_devfn.h's, one copy for every track.  The two rows of year records, (lole, eue, lolf) and
 // (served_hours, discharged_mwh, charged_mwh), are summed by relmc_hl1_reduce_kernel (hl1_reduce_queue, relmc_seq.hip), one row at a time.
 #include <algorithm>
 #include <cmath>
@@ -28,7 +29,7 @@ uint32_t philox_word0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32
     }
     return c0;
 }
-// hl1_var_weather (relmc_variable_kernels.h) on the host; the arguments are in range
+// hl1_var_weather (relmc_hl1_storage_devfn.h) on the host; the arguments are in range
 int32_t weather_year(uint64_t seed, uint64_t chain, int32_t y, int32_t years, int32_t n_weather, int32_t pick)
 {
     if (pick == RELMC_HL1_VAR_PICK_CYCLE) return (int32_t)((chain * (uint64_t)years + (uint64_t)y) % (uint64_t)n_weather);
@@ -100,32 +101,13 @@ int32_t relmc_hl1_var_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, i
     if (!opts) return fail(ctx, RELMC_ERR_INVALID, who + "opts is null");
     if (!std::isfinite(opts->scale) || !std::isfinite(opts->shift)) return fail(ctx, RELMC_ERR_INVALID, who + "scale / shift not finite");
     Hl1VarArgs A; std::memset(&A, 0, sizeof(A));
-    for (int r = 0; r < RELMC_HL1_VAR_MAX_RESOURCES; ++r) {
-        const double s = opts->resource_scale[r];
-        const std::string rs = who + "resource_scale " + std::to_string(r);
-        if (!std::isfinite(s)) return fail(ctx, RELMC_ERR_INVALID, rs + " not finite");
-        if (s < 0.0) return fail(ctx, RELMC_ERR_INVALID, rs + " is negative");
-        if (r >= V.n_res && s != 0.0) return fail(ctx, RELMC_ERR_INVALID, rs + " is not 0 with n_resources " + std::to_string(V.n_res));
-        A.rscale[r] = r < V.n_res ? s : 0.0;
-    }
-    if (opts->pick != RELMC_HL1_VAR_PICK_RANDOM && opts->pick != RELMC_HL1_VAR_PICK_CYCLE)
-        return fail(ctx, RELMC_ERR_INVALID, who + "pick " + std::to_string(opts->pick) + " not 0 or 1");
-    if (opts->reserved != 0) return fail(ctx, RELMC_ERR_INVALID, who + "reserved is not 0");
-    if (n_storage < 0 || n_storage > RELMC_HL1_MAX_STORAGE)
-        return fail(ctx, RELMC_ERR_INVALID, who + "n_storage " + std::to_string(n_storage) + " not in 0.." + std::to_string(RELMC_HL1_MAX_STORAGE));
-    if (n_storage > 0 && !storage) return fail(ctx, RELMC_ERR_INVALID, who + "n_storage > 0 without storage");
-    for (int i = 0; i < n_storage; ++i) {                    // relmc_hl1_seq_storage's field checks, repeated
+    if (const int rc = hl1_resource_scales(ctx, who, opts->resource_scale, V.n_res, A.rscale)) return rc;
+    if (const int rc = hl1_pick_check(ctx, who, opts->pick, opts->reserved)) return rc;
+    if (const int rc = hl1_storage_count_check(ctx, who, n_storage, storage)) return rc;
+    for (int i = 0; i < n_storage; ++i) {
         const relmc_hl1_storage& v = storage[i];
         const std::string st = who + "storage " + std::to_string(i) + ": ";
-        const struct { const char* name; double x; } fields[6] = {{"charge_mw", v.charge_mw}, {"discharge_mw", v.discharge_mw}, {"energy_mwh", v.energy_mwh},
-                                                                   {"eta_charge", v.eta_charge}, {"eta_discharge", v.eta_discharge}, {"soc0_mwh", v.soc0_mwh}};
-        for (const auto& f : fields)
-            if (!std::isfinite(f.x)) return fail(ctx, RELMC_ERR_INVALID, st + f.name + " not finite");
-        for (int q = 0; q < 3; ++q)
-            if (fields[q].x < 0.0) return fail(ctx, RELMC_ERR_INVALID, st + fields[q].name + " is negative");
-        for (int q = 3; q < 5; ++q)
-            if (!(fields[q].x > 0.0 && fields[q].x <= 1.0)) return fail(ctx, RELMC_ERR_INVALID, st + fields[q].name + " not in (0, 1]");
-        if (!(v.soc0_mwh >= 0.0 && v.soc0_mwh <= v.energy_mwh)) return fail(ctx, RELMC_ERR_INVALID, st + "soc0_mwh not in [0, energy_mwh]");
+        if (const int rc = hl1_storage_check(ctx, st, v)) return rc;
         A.st[i] = v;
     }
     A.scale = opts->scale; A.shift = opts->shift; A.n_storage = n_storage;
@@ -133,10 +115,7 @@ int32_t relmc_hl1_var_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, i
     A.out = V.out.get(); A.wload = V.has_load ? V.load.get() : nullptr;
     std::memset(acc, 0, sizeof(*acc));
     if (n_chains == 0) return RELMC_OK;
-    if (weather_host)                                        // the device works out the same function (hl1_var_weather)
-        for (int64_t c = 0; c < n_chains; ++c)
-            for (int32_t y = 0; y < years_per_chain; ++y)
-                weather_host[c * years_per_chain + y] = weather_year(seed, first_chain + (uint64_t)c, y, years_per_chain, V.n_weather, opts->pick);
+    hl1_weather_fill(weather_host, seed, first_chain, n_chains, years_per_chain, V.n_weather, opts->pick);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     double sum[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const int64_t per = hl1_chunk_items(n_chains, kHl1RecordBudget, (int64_t)years_per_chain * 2);             // a chain counts its records of both rows
@@ -145,20 +124,10 @@ int32_t relmc_hl1_var_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, i
             hipLaunchKernelGGL(relmc_hl1_var_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
                                first_chain + (uint64_t)c0, nc, years_per_chain, start, A, V.rec.years.get());
         },
-        [&](int64_t c0, int64_t, int64_t nrec) -> int {
-            if (years_host)
-                HIP_TRY(ctx, hipMemcpyAsync(years_host + c0 * years_per_chain, V.rec.years.get(), sizeof(double) * 3 * nrec, hipMemcpyDeviceToHost, ctx->stream));
-            if (storage_years_host)
-                HIP_TRY(ctx, hipMemcpyAsync(storage_years_host + c0 * years_per_chain, V.rec.years.get() + (size_t)nrec * 3, sizeof(double) * 3 * nrec,
-                                            hipMemcpyDeviceToHost, ctx->stream));
-            return RELMC_OK;
-        },
+        [&](int64_t c0, int64_t, int64_t nrec) { return hl1_two_row_copies(ctx, V.rec.years.get(), c0 * years_per_chain, nrec, years_host, storage_years_host); },
         hl1_no_host_step);
     if (rc) return rc;
-    acc->years = n_chains * years_per_chain;
-    acc->sum_lole = sum[0]; acc->sum_eue = sum[1]; acc->sum_lolf = sum[2]; acc->sum_lole2 = sum[3]; acc->sum_eue2 = sum[4]; acc->sum_lolf2 = sum[5];
-    acc->sum_served = sum[6]; acc->sum_discharged = sum[7]; acc->sum_charged = sum[8];
-    acc->sum_served2 = sum[9]; acc->sum_discharged2 = sum[10]; acc->sum_charged2 = sum[11];
+    hl1_storage_acc_fill(acc, n_chains * years_per_chain, sum, sum + 6);
     return RELMC_OK;
 }
 

@@ -2,13 +2,10 @@
 // contract in include/relmc.h): one walk of a chain's fleet history in which every chain year draws a weather year w of the library of
 // relmc_hl1_var_load; the step's capacity is the fleet's plus resource_scale[r] * output[w][r][h], its load scale * base(w, h) + shift, and
 // the storages of relmc_hl1_seq_storage act on the two.  An extension beyond the reference, whose generation is all dispatchable.
-// The storage helpers below repeat relmc_storage_kernels.h's under names of their own: that header defines its kernel, so a second unit
-// cannot include it, and relmc_storage.hip's code object stays what it was.
+// The weather pick, the storage step and the year close are relmc_hl1_storage_devfn.h's, one copy for every kernel that uses them.
 #pragma once
-#include <utility>
-#include "../../include/relmc.h"
-#include "relmc_devfn.h"
 #include "relmc_hl1_chrono.h"
+#include "relmc_hl1_storage_devfn.h"
 
 namespace relmc {
 
@@ -22,109 +19,6 @@ struct Hl1VarArgs {
     const double* wload;                 // [n_weather][H], or nullptr: the load curve of relmc_hl1_seq_load
     int32_t n_storage, n_res, n_weather, pick;
 };
-
-// f(integral_constant<int, i>) for i = 0 .. RELMC_HL1_MAX_STORAGE - 1, written out at compile time (hl1_storage_each's pattern): a
-// storage's state of charge is a register named by a constant, never a run-time index into a per-thread array (scratch)
-template <class F, int... I>
-DEVFI void hl1_var_each_(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <class F>
-DEVFI void hl1_var_each(F&& f) { hl1_var_each_(f, std::make_integer_sequence<int, RELMC_HL1_MAX_STORAGE>{}); }
-
-// L = scale * base + shift with the product and the sum each rounded (hl1_storage_load's rule)
-DEVFI double hl1_var_load(double scale, double ld, double shift)
-{
-#pragma clang fp contract(off)
-    const double p = scale * ld;
-    return p + shift;
-}
-
-// cap + s * v with the product and the sum each rounded
-DEVFI double hl1_var_add(double cap, double s, double v)
-{
-#pragma clang fp contract(off)
-    const double p = s * v;
-    return cap + p;
-}
-
-// The weather year of chain year y of `chain` (the contract's two rules; relmc_hl1_var_weather_year is the host's copy)
-DEVFI int hl1_var_weather(uint64_t seed, uint64_t chain, int y, int years, int n_weather, int pick)
-{
-    if (pick == RELMC_HL1_VAR_PICK_CYCLE) return (int)((chain * (uint64_t)years + (uint64_t)y) % (uint64_t)n_weather);
-    uint32_t w[4];
-    philox4x32_10((uint32_t)chain, (uint32_t)(chain >> 32), RELMC_HL1_VAR_TAG, (uint32_t)y, (uint32_t)seed, (uint32_t)(seed >> 32), w);
-    return (int)(((uint64_t)w[0] * (uint64_t)n_weather) >> 32);
-}
-
-DEVFI double hl1_var_readlane(double v, int src)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
-}
-
-// hl1_storage_bits: bit i = storage i can discharge (s > 0 and discharge_mw > 0), bit 8 + i = it is not settled (s < energy_mwh and
-// charge_mw > 0)
-DEVFI uint32_t hl1_var_bits(const relmc_hl1_storage& p, double s, int i)
-{
-    return ((s > 0.0 && p.discharge_mw > 0.0) ? 1u << i : 0u) | ((s < p.energy_mwh && p.charge_mw > 0.0) ? 256u << i : 0u);
-}
-
-// The contract's short step (hl1_storage_discharge): soc holds storage i's state of charge in lane i, z is a zero the compiler cannot see
-// through, so that a storage's data is read where it is used.  need -> what is left of it, xs = the sum of the x
-DEVFI void hl1_var_discharge(const Hl1VarArgs& A, int ns, int z, int lane, double& soc, uint32_t& bits, double& need, double& xs)
-{
-    hl1_var_each([&](auto ic) {
-#pragma clang fp contract(off)
-        constexpr int i = decltype(ic)::value;
-        if (i < ns && need > 0.0 && ((bits >> i) & 1u)) {    // wave-uniform
-            const relmc_hl1_storage& p = A.st[i + z];
-            const double eta = p.eta_discharge, s = hl1_var_readlane(soc, i);
-            const double avail = __builtin_fmin(p.discharge_mw, s * eta);
-            const double x = __builtin_fmin(avail, need);
-            const double t = __builtin_fmax(0.0, s - x / eta);
-            need = need - x;
-            xs = xs + x;
-            soc = lane == i ? t : soc;
-            bits = (bits & ~(0x101u << i)) | hl1_var_bits(p, t, i);
-        }
-    });
-}
-
-// The contract's long step (hl1_storage_charge): ys = the sum of the y
-DEVFI void hl1_var_charge(const Hl1VarArgs& A, int ns, int z, int lane, double& soc, uint32_t& bits, double surplus, double& ys)
-{
-    hl1_var_each([&](auto ic) {
-#pragma clang fp contract(off)
-        constexpr int i = decltype(ic)::value;
-        if (i < ns && surplus > 0.0 && ((bits >> (8 + i)) & 1u)) {      // wave-uniform
-            const relmc_hl1_storage& p = A.st[i + z];
-            const double eta = p.eta_charge, cap = p.energy_mwh, s = hl1_var_readlane(soc, i);
-            const double room = (cap - s) / eta;
-            const double y = __builtin_fmin(__builtin_fmin(p.charge_mw, room), surplus);
-            const double t = __builtin_fmin(cap, s + y * eta);
-            surplus = surplus - y;
-            ys = ys + y;
-            soc = lane == i ? t : soc;
-            bits = (bits & ~(0x101u << i)) | hl1_var_bits(p, t, i);
-        }
-    });
-}
-
-// This lane's partials of the open year, and the year's close (Hl1StoragePartials, hl1_storage_close_year: the fixed-order butterfly over
-// both records; lane 0 stores (lole, eue, lolf) and (served_hours, discharged_mwh, charged_mwh); the partials restart at zero)
-struct Hl1VarPartials { uint32_t lole, lolf, served; double eue, dis, chg; };
-DEVFI void hl1_var_close_year(Hl1VarPartials& a, double* __restrict__ out0, double* __restrict__ out1)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a.lole += (uint32_t)__shfl_xor((int)a.lole, off); a.lolf += (uint32_t)__shfl_xor((int)a.lolf, off); a.served += (uint32_t)__shfl_xor((int)a.served, off);
-        a.eue += __shfl_xor(a.eue, off); a.dis += __shfl_xor(a.dis, off); a.chg += __shfl_xor(a.chg, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        out0[0] = (double)a.lole; out0[1] = a.eue; out0[2] = (double)a.lolf;
-        out1[0] = (double)a.served; out1[1] = a.dis; out1[2] = a.chg;
-    }
-    a.lole = a.lolf = a.served = 0u;
-    a.eue = a.dis = a.chg = 0.0;
-}
 
 // Chain c = blockIdx.x * 4 + wave.  The window loop and the group stages are a COPY of relmc_hl1_storage_kernel's (relmc_storage_kernels.h,
 // which says what the stages do), on purpose, as that kernel's is of relmc_hl1_seq_kernel's: sharing the loop between kernels cost the
@@ -177,12 +71,12 @@ __global__ void __launch_bounds__(256) relmc_hl1_var_kernel(const Hl1SeqCase* __
     }
 
     double soc = 0.0;                                        // storage i's state of charge (MWh) in lane i
-    uint32_t bits = 0u;                                      // hl1_var_bits of every storage (wave-uniform)
-    hl1_var_each([&](auto ic) {
+    uint32_t bits = 0u;                                      // hl1_storage_bits of every storage (wave-uniform)
+    hl1_storage_each([&](auto ic) {
         constexpr int i = decltype(ic)::value;
-        if (i < ns) { soc = lane == i ? A.st[i].soc0_mwh : soc; bits |= hl1_var_bits(A.st[i], A.st[i].soc0_mwh, i); }
+        if (i < ns) { soc = lane == i ? A.st[i].soc0_mwh : soc; bits |= hl1_storage_bits(A.st[i], A.st[i].soc0_mwh, i); }
     });
-    Hl1VarPartials a = {0u, 0u, 0u, 0.0, 0.0, 0.0};         // this lane's partials of the open year ycur
+    Hl1StoragePartials a = {0u, 0u, 0u, 0.0, 0.0, 0.0};         // this lane's partials of the open year ycur
     int ycur = 0, gy = 0, gh = 0;                            // gy / gh: chain year and hour of the current 64-step group's first step
     int yw = -1;                                             // this lane's cached chain year, and
     uint32_t wb = 0u;                                        // w * H of its weather year w (relmc_hl1_var_load: n_weather * n_res * H < 2^31)
@@ -255,7 +149,7 @@ __global__ void __launch_bounds__(256) relmc_hl1_var_kernel(const Hl1SeqCase* __
                     cap = hl1_var_add(cap, A.rscale[r], a);
                     if (two) cap = hl1_var_add(cap, A.rscale[r + 1], b);
                 }
-                const double L = hl1_var_load(A.scale, ld, A.shift);
+                const double L = hl1_storage_load(A.scale, ld, A.shift);
                 sh = cap < L; lg = cap > L;
                 m = sh ? L - cap : lg ? cap - L : 0.0;
             }
@@ -270,14 +164,14 @@ __global__ void __launch_bounds__(256) relmc_hl1_var_kernel(const Hl1SeqCase* __
                     if (todo == 0) break;
                     const int j = __builtin_ctzll(todo);
                     rest = j == 63 ? 0ull : ~0ull << (j + 1);
-                    const double mj = hl1_var_readlane(m, j);
+                    const double mj = hl1_storage_readlane(m, j);
                     if ((ms >> j) & 1ull) {
                         double need = mj, x = 0.0;
-                        hl1_var_discharge(A, ns, z, lane, soc, bits, need, x);
+                        hl1_storage_discharge(A, ns, z, lane, soc, bits, need, x);
                         if (lane == j) { m = need; xy = x; }     // m: what is left of the need
                     } else {
                         double yj = 0.0;
-                        hl1_var_charge(A, ns, z, lane, soc, bits, mj, yj);
+                        hl1_storage_charge(A, ns, z, lane, soc, bits, mj, yj);
                         if (lane == j) xy = yj;
                     }
                 }
@@ -291,7 +185,7 @@ __global__ void __launch_bounds__(256) relmc_hl1_var_kernel(const Hl1SeqCase* __
                         a.eue += f ? m : 0.0; a.dis += sh ? xy : 0.0; a.chg += sh ? 0.0 : xy;
                     }
                     if (!__any(valid && y > ycur)) break;
-                    hl1_var_close_year(a, out0 + (size_t)ycur * 3, out1 + (size_t)ycur * 3);
+                    hl1_storage_close_year(a, out0 + (size_t)ycur * 3, out1 + (size_t)ycur * 3);
                     ++ycur;
                 }
             } else prev = false;
@@ -300,6 +194,6 @@ __global__ void __launch_bounds__(256) relmc_hl1_var_kernel(const Hl1SeqCase* __
         }
         hl1_seq_wave_sync();
     }
-    for (; ycur < years; ++ycur) hl1_var_close_year(a, out0 + (size_t)ycur * 3, out1 + (size_t)ycur * 3);
+    for (; ycur < years; ++ycur) hl1_storage_close_year(a, out0 + (size_t)ycur * 3, out1 + (size_t)ycur * 3);
 }
 }  // namespace relmc

@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "relmc_hl1_host.h"
-#include "relmc_area_variable_kernels.h"
+#include "relmc_area_kernels.h"
 
 using namespace relmc_host;
 
@@ -129,7 +129,7 @@ int32_t relmc_hl1_area_var(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, 
     const bool ties = inter && S.tie_outages && S.tie_fail;       // the tie-outage kernel: one more mask row
     const size_t lds = sizeof(double) * 64 * relmc::area_var_lds_rows(S.n_areas, inter, n_storage > 0) +
                        sizeof(uint32_t) * (nw + (ties ? 1 : 0)) * relmc::HL1_SEQ_WINDOW;
-    const auto kernel = ties ? relmc::relmc_hl1_area_var_kernel<true> : relmc::relmc_hl1_area_var_kernel<false>;
+    const auto kernel = ties ? relmc::relmc_hl1_area_kernel<true, relmc::AreaVarArgs> : relmc::relmc_hl1_area_kernel<false, relmc::AreaVarArgs>;
     std::vector<double> stage, sum((size_t)slices * 6, 0.0);
     const int64_t total = n_chains * years_per_chain;
     const int64_t per = hl1_chunk_items(n_chains, kHl1RecordBudget, (int64_t)slices * years_per_chain);   // a chain counts its records of every slice

@@ -20,17 +20,17 @@
 //                        weather_host, the two-row copies, relmc_hl1_storage_acc)
 //   relmc_hl1_storage_devfn.h (a header, no kernel) the device leaves those four tracks share: the storage step, its bits, the year close,
 //                        the weather pick
-//   relmc_storage.hip    energy storage with a state of charge on that chronology (relmc_hl1_seq_storage, kernel in relmc_storage_kernels.h)
+//   relmc_storage.hip    energy storage with a state of charge on that chronology (relmc_hl1_seq_storage, kernel in relmc_hl1_storage_kernels.h)
 //   relmc_variable.hip   weather-year wind and solar resources on that chronology, with those storages (relmc_hl1_var_load, relmc_hl1_var_seq,
-//                        kernel in relmc_variable_kernels.h)
+//                        kernel in relmc_hl1_storage_kernels.h)
 //   relmc_stress.hip     weather-dependent forced outage rates on that chronology, with those resources and storages (relmc_hl1_stress_load,
-//                        relmc_hl1_stress_seq, kernel in relmc_stress_kernels.h)
+//                        relmc_hl1_stress_seq, kernel in relmc_hl1_storage_kernels.h)
 //   relmc_multistate.hip that chronology with three-state units (relmc_hl1_ms_load, relmc_hl1_ms_seq, kernel in relmc_multistate_kernels.h)
 //   relmc_plan.hip       the HL1 planning model's Monte Carlo (relmc_hl1_plan)
 //   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area)
 //   relmc_area_sweep.hip the sweep of that chronology over load, tie and fleet levels (relmc_hl1_area_sweep, kernel in relmc_area_sweep_kernels.h)
 //   relmc_area_variable.hip weather-year resources and storages in the areas of that chronology (relmc_hl1_area_var_load, relmc_hl1_area_var,
-//                        kernel in relmc_area_variable_kernels.h, transfer solve from relmc_area_kernels.h)
+//                        kernel in relmc_area_kernels.h, its own leaves in relmc_area_variable_devfn.h)
 //   relmc_screen.hip     the zero-curtailment pre-screen (relmc_solver_opts.screen): certificate tables, pre-pass kernels, worklists
 //   relmc_importance.hip importance sampling for the non-sequential track: tilted sampler with likelihood ratios, weighted reductions (kernels in
 //                        relmc_is_kernels.h), the cross-entropy tuner and the weighted run loop

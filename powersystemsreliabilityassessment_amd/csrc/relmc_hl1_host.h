@@ -1,9 +1,11 @@
 // relmc_hl1_host.h — host code the HL1 record models share: the unit and argument checks, the chunk rule, and the one loop that launches
-// a model chunk by chunk and sums its year records (hl1_run_records), and the checks and fills of the storage and weather-year tracks.
+// a model chunk by chunk and sums its year records (hl1_run_records), the checks and fills of the storage and weather-year tracks, and the
+// one body of relmc_hl1_var_seq and relmc_hl1_stress_seq (hl1_weather_seq).
 // Host only.  `who` is the calling function's name, for the message.
 // The buffer pair of a model, Hl1Records, is in relmc_ctx.h: the context holds one per model by value.
 #pragma once
 #include <algorithm>
+#include <cstring>
 
 #include "relmc_ctx.h"
 
@@ -158,6 +160,68 @@ inline void hl1_storage_acc_fill(relmc_hl1_storage_acc* acc, int64_t years, cons
     acc->sum_lole = s0[0]; acc->sum_eue = s0[1]; acc->sum_lolf = s0[2]; acc->sum_lole2 = s0[3]; acc->sum_eue2 = s0[4]; acc->sum_lolf2 = s0[5];
     acc->sum_served = s1[0]; acc->sum_discharged = s1[1]; acc->sum_charged = s1[2];
     acc->sum_served2 = s1[3]; acc->sum_discharged2 = s1[4]; acc->sum_charged2 = s1[5];
+}
+
+// The body of relmc_hl1_var_seq (STRESS false: Args is Hl1VarArgs, the records go to hl1_var.rec) and of relmc_hl1_stress_seq (STRESS
+// true: Hl1StressArgs, hl1_stress.rec), which adds the checks of its library against the fleet and the weather library and the fields of
+// Args that hold it.  `name` is the entry point's, `kernel` its instantiation of relmc_hl1_storage_track_kernel.
+template <bool STRESS, class Args, class Kernel>
+int hl1_weather_seq(relmc_ctx* ctx, const char* name, Kernel kernel, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain,
+                    int32_t start, const relmc_hl1_var_opts* opts, int32_t n_storage, const relmc_hl1_storage* storage, relmc_hl1_storage_acc* acc,
+                    relmc_hl1_seq_year* years_host, relmc_hl1_storage_year* storage_years_host, int32_t* weather_host)
+{
+    const std::string who = std::string(name) + ": ";
+    if (!ctx) return RELMC_ERR_INVALID;
+    if (!ctx->has_hl1_seq) return fail(ctx, RELMC_ERR_NO_CASE, who + "relmc_hl1_seq_load has not been called");
+    if (!ctx->has_hl1_var) return fail(ctx, RELMC_ERR_NO_CASE, who + "relmc_hl1_var_load has not been called");
+    if (STRESS && !ctx->has_hl1_stress) return fail(ctx, RELMC_ERR_NO_CASE, who + "relmc_hl1_stress_load has not been called");
+    auto& S = ctx->hl1_seq;
+    auto& V = ctx->hl1_var;
+    auto& X = ctx->hl1_stress;
+    if (S.nhours != V.nhours)
+        return fail(ctx, RELMC_ERR_INVALID, who + "nhours of relmc_hl1_seq_load " + std::to_string(S.nhours) + " is not nhours of relmc_hl1_var_load " + std::to_string(V.nhours));
+    if constexpr (STRESS) {
+        if (X.n_units != S.ngen)
+            return fail(ctx, RELMC_ERR_INVALID, who + "n_units of relmc_hl1_stress_load " + std::to_string(X.n_units) + " is not the fleet's " + std::to_string(S.ngen));
+        if (X.n_weather != V.n_weather)
+            return fail(ctx, RELMC_ERR_INVALID, who + "n_weather of relmc_hl1_stress_load " + std::to_string(X.n_weather) + " is not n_weather of relmc_hl1_var_load " + std::to_string(V.n_weather));
+        if (X.nhours != V.nhours)
+            return fail(ctx, RELMC_ERR_INVALID, who + "nhours of relmc_hl1_stress_load " + std::to_string(X.nhours) + " is not nhours of relmc_hl1_var_load " + std::to_string(V.nhours));
+    }
+    if (!hl1_chain_args_ok(acc, n_chains, years_per_chain, start)) return fail(ctx, RELMC_ERR_INVALID, who + "bad arguments");
+    if (!opts) return fail(ctx, RELMC_ERR_INVALID, who + "opts is null");
+    if (!std::isfinite(opts->scale) || !std::isfinite(opts->shift)) return fail(ctx, RELMC_ERR_INVALID, who + "scale / shift not finite");
+    Args A; std::memset(&A, 0, sizeof(A));
+    if (const int rc = hl1_resource_scales(ctx, who, opts->resource_scale, V.n_res, A.rscale)) return rc;
+    if (const int rc = hl1_pick_check(ctx, who, opts->pick, opts->reserved)) return rc;
+    if (const int rc = hl1_storage_count_check(ctx, who, n_storage, storage)) return rc;
+    for (int i = 0; i < n_storage; ++i) {
+        const relmc_hl1_storage& v = storage[i];
+        const std::string st = who + "storage " + std::to_string(i) + ": ";
+        if (const int rc = hl1_storage_check(ctx, st, v)) return rc;
+        A.st[i] = v;
+    }
+    A.scale = opts->scale; A.shift = opts->shift; A.n_storage = n_storage;
+    A.n_res = V.n_res; A.n_weather = V.n_weather; A.pick = opts->pick;
+    A.out = V.out.get(); A.wload = V.has_load ? V.load.get() : nullptr;
+    if constexpr (STRESS) { A.cum = X.cum.get(); A.ucls = X.ucls.get(); A.n_classes = X.n_classes; }
+    std::memset(acc, 0, sizeof(*acc));
+    if (n_chains == 0) return RELMC_OK;
+    hl1_weather_fill(weather_host, seed, first_chain, n_chains, years_per_chain, V.n_weather, opts->pick);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Hl1Records& R = STRESS ? X.rec : V.rec;
+    double sum[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int64_t per = hl1_chunk_items(n_chains, kHl1RecordBudget, (int64_t)years_per_chain * 2);             // a chain counts its records of both rows
+    const int rc = hl1_run_records(ctx, name, R, n_chains, per, years_per_chain, 2, sum,
+        [&](int64_t c0, int64_t nc, int64_t) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
+                               first_chain + (uint64_t)c0, nc, years_per_chain, start, A, R.years.get());
+        },
+        [&](int64_t c0, int64_t, int64_t nrec) { return hl1_two_row_copies(ctx, R.years.get(), c0 * years_per_chain, nrec, years_host, storage_years_host); },
+        hl1_no_host_step);
+    if (rc) return rc;
+    hl1_storage_acc_fill(acc, n_chains * years_per_chain, sum, sum + 6);
+    return RELMC_OK;
 }
 
 }  // namespace relmc_host

@@ -1,6 +1,6 @@
 // relmc_hl1_storage_devfn.h — device-only helpers of the storage and weather-year contracts (include/relmc.h), shared by
-// relmc_hl1_storage_kernel (relmc_storage_kernels.h), relmc_hl1_var_kernel (relmc_variable_kernels.h), relmc_hl1_stress_kernel
-// (relmc_stress_kernels.h) and relmc_hl1_area_var_kernel (relmc_area_variable_kernels.h).  Inline functions only, as relmc_hl1_chrono.h:
+// the three tracks of relmc_hl1_storage_track_kernel (relmc_hl1_storage_kernels.h) and the weather-year instantiations of relmc_hl1_area_kernel
+// (relmc_area_kernels.h).  Inline functions only, as relmc_hl1_chrono.h:
 // no kernel is defined here, so every unit may include it.  The functions are force-inlined leaves; every kernel that uses them compiles
 // to the instructions it had with a copy of its own.
 #pragma once

@@ -1,9 +1,16 @@
-// relmc_stress_kernels.h — weather-dependent forced outage rates on the HL1 sequential chronology (relmc_hl1_stress_seq, contract in
-// include/relmc.h): relmc_hl1_var_seq's walk of a chain's fleet history, in which a UP unit of outage class c fails with the hazard
-// fail_mult[w(y)][c][h] / mttf in hour h of chain year y.  The time of a failure is no longer T + E: the draw E = -mttf * ln U is spent
-// along the cumulative multiplier table G of the unit's class, year by year (hl1_stress_failure_time, compiled for the host and the
-// device from this one text).  An extension beyond the reference, whose units have constant rates.
-// The helpers of the resources, the storages and the year close are relmc_hl1_storage_devfn.h's, shared with relmc_hl1_var_kernel.
+// relmc_hl1_storage_kernels.h — the HL1 sequential chronology with energy storage, in its three tracks (contracts in include/relmc.h), as
+// one kernel template:
+//   storage  relmc_hl1_seq_storage: one walk of a chain's fleet history against the load L(h) = scale * load[h] + shift, with up to
+//            RELMC_HL1_MAX_STORAGE storages that discharge into a shortfall and charge from surplus generation
+//   weather  relmc_hl1_var_seq: every chain year draws a weather year w of the library of relmc_hl1_var_load; the step's capacity is the
+//            fleet's plus resource_scale[r] * output[w][r][h], its load scale * base(w, h) + shift
+//   stress   relmc_hl1_stress_seq: the weather track, in which a UP unit of outage class c fails with the hazard
+//            fail_mult[w(y)][c][h] / mttf in hour h of chain year y.  The time of a failure is no longer T + E: the draw E = -mttf * ln U is
+//            spent along the cumulative multiplier table G of the unit's class, year by year (hl1_stress_failure_time, compiled for the
+//            host and the device from this one text)
+// All three are extensions beyond the reference: its only energy-limited resource, the ELU of the planning model, drains and never
+// recharges, on an hourly-sampling Monte Carlo; its generation is all dispatchable; its units have constant rates.
+// The weather pick, the storage step, the wave-uniform bits and the year close are relmc_hl1_storage_devfn.h's.
 #pragma once
 #include "relmc_hl1_chrono.h"
 #include "relmc_hl1_storage_devfn.h"
@@ -53,23 +60,79 @@ __host__ __device__ inline double hl1_stress_failure_time(double T, double E, in
     return r > T ? r : T;
 }
 
-// The storages, the load level, the resource scales and the weather library as Hl1VarArgs has them, then the stress library: the
-// cumulative tables and the fleet's classes.  Passed BY VALUE as a kernel argument: every read of the fields is a scalar load from the
-// kernel argument segment.
-struct Hl1StressArgs {
+// A track's model, passed BY VALUE as a kernel argument (as Hl1SweepArgs): every read of a field is a scalar load from the kernel argument
+// segment, and the offsets of the fields are part of the code.  st[n_storage ..] and rscale[n_res ..] are zero and never read.
+struct Hl1StorageArgs {                  // the storages and the load level
+    relmc_hl1_storage st[RELMC_HL1_MAX_STORAGE];
+    double scale, shift;
+    int32_t n_storage, pad;
+};
+struct Hl1VarArgs {                      // and the resource scales and the weather library
     relmc_hl1_storage st[RELMC_HL1_MAX_STORAGE];
     double rscale[RELMC_HL1_VAR_MAX_RESOURCES];
     double scale, shift;
-    const double* out;                   // [n_weather][n_res][H], fewer than 2^31 values (relmc_hl1_var_load)
+    const double* out;                   // [n_weather][n_res][H], fewer than 2^31 values (relmc_hl1_var_load): the kernel indexes it in 32 bits
     const double* wload;                 // [n_weather][H], or nullptr: the load curve of relmc_hl1_seq_load
+    int32_t n_storage, n_res, n_weather, pick;
+};
+struct Hl1StressArgs {                   // and the stress library: the cumulative tables and the fleet's classes
+    relmc_hl1_storage st[RELMC_HL1_MAX_STORAGE];
+    double rscale[RELMC_HL1_VAR_MAX_RESOURCES];
+    double scale, shift;
+    const double* out;                   // as Hl1VarArgs
+    const double* wload;
     const double* cum;                   // [n_weather][n_classes][H + 1], fewer than 2^31 values (relmc_hl1_stress_load)
     const int32_t* ucls;                 // [ngen]: -1 or a class
     int32_t n_storage, n_res, n_weather, pick, n_classes, reserved;
 };
 
-// Chain c = blockIdx.x * 4 + wave.  The window loop, the group stages and the year close are a COPY of relmc_hl1_var_kernel's
-// (relmc_variable_kernels.h, which says what they do), on purpose: sharing the loop between kernels has cost the older kernels time
-// (DESIGN.md 6.12), and that kernel's code object must not change.  What is new is the transition of stage (1):
+enum Hl1Track : int { HL1_TRACK_STORAGE, HL1_TRACK_WEATHER, HL1_TRACK_STRESS };
+template <int TRACK> struct Hl1TrackArgs;
+template <> struct Hl1TrackArgs<HL1_TRACK_STORAGE> { using type = Hl1StorageArgs; };
+template <> struct Hl1TrackArgs<HL1_TRACK_WEATHER> { using type = Hl1VarArgs; };
+template <> struct Hl1TrackArgs<HL1_TRACK_STRESS> { using type = Hl1StressArgs; };
+
+// The kernel's setup reads a field that a track's struct lacks as nothing: no resources and no weather library, no classes
+DEVFI int hl1_track_nres(const Hl1StorageArgs&) { return 0; }
+DEVFI const double* hl1_track_wload(const Hl1StorageArgs&) { return nullptr; }
+DEVFI const double* hl1_track_out(const Hl1StorageArgs&) { return nullptr; }
+DEVFI int hl1_track_weather(const Hl1StorageArgs&, uint64_t, uint64_t, int, int) { return 0; }
+template <class Args> DEVFI int hl1_track_nres(const Args& A) { return A.n_res < RELMC_HL1_VAR_MAX_RESOURCES ? A.n_res : RELMC_HL1_VAR_MAX_RESOURCES; }
+template <class Args> DEVFI const double* hl1_track_wload(const Args& A) { return A.wload; }
+template <class Args> DEVFI const double* hl1_track_out(const Args& A) { return A.out; }
+template <class Args> DEVFI int hl1_track_weather(const Args& A, uint64_t seed, uint64_t chain, int y, int years) { return hl1_var_weather(seed, chain, y, years, A.n_weather, A.pick); }
+template <class Args> DEVFI const double* hl1_track_cum(const Args&) { return nullptr; }
+template <class Args> DEVFI uint32_t hl1_track_ncls(const Args&) { return 0u; }
+DEVFI const double* hl1_track_cum(const Hl1StressArgs& A) { return A.cum; }
+DEVFI uint32_t hl1_track_ncls(const Hl1StressArgs& A) { return (uint32_t)A.n_classes; }
+
+// Chain c = blockIdx.x * 4 + wave; the chronology is relmc_hl1_seq_kernel's, word for word (lane l owns units l and l + 64, windows of
+// HL1_SEQ_WINDOW steps filled into the wave's LDS masks, one step per lane, no workgroup barrier).  The window loop is written out here and
+// not shared with relmc_hl1_seq_kernel (relmc_seq_kernels.h), as relmc_hl1_sweep_kernel's is: sharing that loop between kernels cost the
+// sequential kernel 1.6-3 % twice.  The three tracks are instantiations of this one text, each with the instructions it had as a kernel of
+// its own; what a track adds is under `if constexpr`, and the setup values a track has no use for are dead.
+//
+// Storage i's state of charge lives in lane i of one register for the whole chain; what each storage can still do is kept beside it as
+// wave-uniform bits (hl1_storage_bits).  Per 64-step group:
+//   parallel   each lane forms cap and L of its step, the flags short (cap < L) and long (cap > L), and m = L - cap or cap - L
+//   quiet      no lane is short and every storage is settled (full, or unable to charge): the group changes no state and has no loss;
+//              nothing further is done (nearly every group).  A skipped group would add only + 0.0 to the year partials, so the
+//              years are closed when a later year shows up in a group that is not quiet, or at the end of the chain
+//   serial     the steps on which a storage can act are visited in step order by a wave-uniform loop: the short steps while some
+//              storage can discharge (s > 0 and discharge_mw > 0), the long steps while some storage is not settled (both read off
+//              the bits).  A step left out is one on which the contract's loop changes nothing: avail or y is 0 for every storage.
+//              m of the step is read from its lane, the storages are taken in ascending order, and what is left of the need and
+//              the step's sum of x (or of y) go back to the lane
+//   year       loss flag, rising edge (the neighbouring lane's flag, lane 63's carried over) and the lane partials of the open year as in
+//              relmc_hl1_seq_kernel: the EUE of a year is summed in its order (the counts are kept as integers, exact in any order)
+// The weather and stress tracks add to the parallel stage, one step per lane:
+//   weather    a 64-step group may span several years when H < 64, so the weather year belongs to the lane's chain year y.  Each lane
+//              keeps (yw, w * H) and works the pick out only when its y changes: once per lane and year, never per step
+//   load       base(w, h) from the library's [w][h] curves or the sequential model's [h]: pointer and row mask chosen once per kernel
+//   resources  cap = cap + rscale[r] * out[(w * n_res + r) * H + h] for r ascending, lanes on consecutive h (a lane past a year edge reads
+//              another row), in 32-bit indices; the scales are scalar loads from the argument segment under wave-uniform tests; the first two
+//              outputs and the load are read ahead of the capacity sum, the others in pairs
+// The stress track adds to the transition of stage (1):
 //   class      lane l keeps the classes of its units l and l + 64 in registers (cls[s], -1: the unit ignores the weather)
 //   failure    a lane whose unit has just become UP and has a class runs hl1_stress_failure_time instead of the addition: a walk over the
 //              years the draw outlasts (bounded by `years`; the weather year of each from hl1_var_weather), then a binary search of at
@@ -77,12 +140,14 @@ struct Hl1StressArgs {
 //              from the others inside `while (__any(more))`; the loop's trip count is what it was, one trip per transition of the busiest lane
 //   never      a unit that does not fail again gets years * H + 1, beyond every window: its cursor waits for the rest of the chain
 // Records: year_out[row][chain of the launch][year][3], row 0 = (lole, eue, lolf), row 1 = (served_hours, discharged_mwh, charged_mwh).
-// amdgpu_waves_per_eu(4, 4): left alone the allocator takes 131 VGPRs, three waves per SIMD; asked for relmc_hl1_var_kernel's four it
-// finds 125 without scratch.
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) relmc_hl1_stress_kernel(const Hl1SeqCase* __restrict__ S, const double* __restrict__ load, uint64_t seed,
-                                                               uint64_t first_chain, int64_t n_chains, int32_t years, int32_t start,
-                                                               const Hl1StressArgs A, double* __restrict__ year_out)
+// amdgpu_waves_per_eu: the stress track asks for (4, 4).  Left alone the allocator takes 131 VGPRs there, three waves per SIMD; asked for
+// the weather track's four it finds 125 without scratch.  (1, 8) is what a kernel without the attribute gets.
+template <int TRACK>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TRACK == HL1_TRACK_STRESS ? 4 : 1, TRACK == HL1_TRACK_STRESS ? 4 : 8)))
+relmc_hl1_storage_track_kernel(const Hl1SeqCase* __restrict__ S, const double* __restrict__ load, uint64_t seed, uint64_t first_chain, int64_t n_chains,
+                               int32_t years, int32_t start, const typename Hl1TrackArgs<TRACK>::type A, double* __restrict__ year_out)
 {
+    constexpr bool WEATHER = TRACK != HL1_TRACK_STORAGE, STRESS = TRACK == HL1_TRACK_STRESS;
     constexpr int W = HL1_SEQ_WINDOW;
     constexpr int NS = RELMC_HL1_MAX_STORAGE;
     __shared__ uint32_t masks[4][4][W];                     // [wave][mask word][step of the window], bit k & 31 of word k >> 5 = unit k down
@@ -92,12 +157,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     const uint64_t chain = first_chain + (uint64_t)cl;
     const int ngen = S->ngen, H = S->nhours, nw = (ngen + 31) >> 5, nslot = ngen > 64 ? 2 : 1;
     const int ns = A.n_storage < NS ? A.n_storage : NS;
-    const int nres = A.n_res < RELMC_HL1_VAR_MAX_RESOURCES ? A.n_res : RELMC_HL1_VAR_MAX_RESOURCES;
-    const double* __restrict__ const lcurve = A.wload ? A.wload : load;       // base(w, h) = lcurve[(w * H & lmask) + h]
-    const uint32_t lmask = A.wload ? ~0u : 0u;
-    const double* __restrict__ const rout = A.out;
-    const double* __restrict__ const cum = A.cum;
-    const uint32_t ncls = (uint32_t)A.n_classes, H1 = (uint32_t)H + 1u;
+    const int nres = hl1_track_nres(A);
+    const double* __restrict__ const lcurve = hl1_track_wload(A) ? hl1_track_wload(A) : load;    // base(w, h) = lcurve[(w * H & lmask) + h]
+    const uint32_t lmask = hl1_track_wload(A) ? ~0u : 0u;
+    const double* __restrict__ const rout = hl1_track_out(A);
+    const double* __restrict__ const cum = hl1_track_cum(A);
+    const uint32_t ncls = hl1_track_ncls(A), H1 = (uint32_t)H + 1u;
     uint32_t (*const seg)[W] = masks[wv];
     const int64_t nsteps = (int64_t)years * H;
     double* const out0 = year_out + (size_t)cl * (size_t)years * 3;
@@ -110,7 +175,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     // the failure time of a unit of class c that became UP at T with the draw E (c >= 0; G's row of (w, c) starts at (w * ncls + c) * (H + 1))
     auto fail_at = [&](double T, double E, int c) {
         return hl1_stress_failure_time(T, E, H, years, [&](int y) {
-            return cum + ((uint32_t)hl1_var_weather(seed, chain, y, years, A.n_weather, A.pick) * ncls + (uint32_t)c) * H1;
+            return cum + ((uint32_t)hl1_track_weather(A, seed, chain, y, years) * ncls + (uint32_t)c) * H1;
         });
     };
 #pragma unroll
@@ -118,12 +183,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
         const int k = lane + 64 * s;
         mine[s] = k < ngen;
         mf[s] = mine[s] ? S->mttf[k] : 1.0; mr[s] = mine[s] ? S->mttr[k] : 1.0;
-        cls[s] = mine[s] ? A.ucls[k] : -1;
+        if constexpr (STRESS) cls[s] = mine[s] ? A.ucls[k] : -1;
+        else cls[s] = -1;
         down[s] = false; ev[s] = 0; since[s] = 1; tn[s] = 0.0;
         if (mine[s]) {
             if (start == RELMC_HL1_START_STATIONARY) { down[s] = hl1_seq_u(chain, k, 0, seed) < S->q[k]; ev[s] = 1; }
             const double e = __dmul_rn(-(down[s] ? mr[s] : mf[s]), log(hl1_seq_u(chain, k, ev[s], seed)));    // T_1 = 0 + duration, or
-            tn[s] = (!down[s] && cls[s] >= 0) ? fail_at(0.0, e, cls[s]) : e;                                     // the failure time from 0
+            tn[s] = (STRESS && !down[s] && cls[s] >= 0) ? fail_at(0.0, e, cls[s]) : e;                           // the failure time from 0
             ++ev[s];
         }
     }
@@ -134,7 +200,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
         constexpr int i = decltype(ic)::value;
         if (i < ns) { soc = lane == i ? A.st[i].soc0_mwh : soc; bits |= hl1_storage_bits(A.st[i], A.st[i].soc0_mwh, i); }
     });
-    Hl1StoragePartials a = {0u, 0u, 0u, 0.0, 0.0, 0.0};      // this lane's partials of the open year ycur
+    Hl1StoragePartials a = {0u, 0u, 0u, 0.0, 0.0, 0.0};     // this lane's partials of the open year ycur
     int ycur = 0, gy = 0, gh = 0;                            // gy / gh: chain year and hour of the current 64-step group's first step
     int yw = -1;                                             // this lane's cached chain year, and
     uint32_t wb = 0u;                                        // w * H of its weather year w (relmc_hl1_var_load: n_weather * n_res * H < 2^31)
@@ -163,7 +229,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                         down[s] = !down[s]; since[s] = c;
                         const double l = log(hl1_seq_u(chain, lane + 64 * s, ev[s], seed));
                         const double e = __dmul_rn(-(down[s] ? mr[s] : mf[s]), l);
-                        if (!down[s] && cls[s] >= 0) tn[s] = fail_at(tn[s], e, cls[s]);   // UP in a stressed class: the hazard along G
+                        if (STRESS && !down[s] && cls[s] >= 0) tn[s] = fail_at(tn[s], e, cls[s]);   // UP in a stressed class: the hazard along G
                         else tn[s] = __dadd_rn(tn[s], e);                         // no FMA: the host model rounds the same way
                         ++ev[s];
                     }
@@ -187,29 +253,35 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
             bool sh = false, lg = false;                     // short: cap < L, long: cap > L
             double m = 0.0;                                  // the step's need (short) or surplus (long)
             if (valid) {                                     // y < years, h < H: every read below is inside its table
-                if (y != yw) { yw = y; wb = (uint32_t)hl1_var_weather(seed, chain, y, years, A.n_weather, A.pick) * (uint32_t)H; }
-                // the step's load and its first two outputs are read BEFORE the capacity sum, whose work hides their latency
-                const double ld = lcurve[(wb & lmask) + (uint32_t)h];
-                uint32_t oi = wb * (uint32_t)nres + (uint32_t)h;                  // out[(w * n_res + r) * H + h], r = 0
-                double o0 = 0.0, o1 = 0.0;
-                if (nres > 0) o0 = rout[oi];                                      // wave-uniform tests
-                if (nres > 1) o1 = rout[oi + (uint32_t)H];
+                double ld = 0.0, o0 = 0.0, o1 = 0.0;
+                uint32_t oi = 0u;
+                if constexpr (WEATHER) {
+                    if (y != yw) { yw = y; wb = (uint32_t)hl1_track_weather(A, seed, chain, y, years) * (uint32_t)H; }
+                    // the step's load and its first two outputs are read BEFORE the capacity sum, whose work hides their latency
+                    ld = lcurve[(wb & lmask) + (uint32_t)h];
+                    oi = wb * (uint32_t)nres + (uint32_t)h;                       // out[(w * n_res + r) * H + h], r = 0
+                    if (nres > 0) o0 = rout[oi];                                  // wave-uniform tests
+                    if (nres > 1) o1 = rout[oi + (uint32_t)H];
+                }
                 double cap = 0.0;
                 for (int q = 0; q < nw; ++q) {
                     const uint32_t up = ~seg[q][i];
                     const int kn = ngen - 32 * q < 32 ? ngen - 32 * q : 32;
                     for (int b = 0; b < kn; ++b) cap += ((up >> b) & 1u) ? S->cap[32 * q + b] : 0.0;   // ascending units; + 0.0 is exact
                 }
-                if (nres > 0) cap = hl1_var_add(cap, A.rscale[0], o0);
-                if (nres > 1) cap = hl1_var_add(cap, A.rscale[1], o1);
-                for (int r = 2; r < nres; r += 2) {                               // the others two at a time: one wait per pair
-                    const uint32_t oj = oi + (uint32_t)r * (uint32_t)H;
-                    const bool two = r + 1 < nres;
-                    const double a = rout[oj], b = two ? rout[oj + (uint32_t)H] : 0.0;
-                    cap = hl1_var_add(cap, A.rscale[r], a);
-                    if (two) cap = hl1_var_add(cap, A.rscale[r + 1], b);
-                }
-                const double L = hl1_storage_load(A.scale, ld, A.shift);
+                double L;
+                if constexpr (WEATHER) {
+                    if (nres > 0) cap = hl1_var_add(cap, A.rscale[0], o0);
+                    if (nres > 1) cap = hl1_var_add(cap, A.rscale[1], o1);
+                    for (int r = 2; r < nres; r += 2) {                           // the others two at a time: one wait per pair
+                        const uint32_t oj = oi + (uint32_t)r * (uint32_t)H;
+                        const bool two = r + 1 < nres;
+                        const double a = rout[oj], b = two ? rout[oj + (uint32_t)H] : 0.0;
+                        cap = hl1_var_add(cap, A.rscale[r], a);
+                        if (two) cap = hl1_var_add(cap, A.rscale[r + 1], b);
+                    }
+                    L = hl1_storage_load(A.scale, ld, A.shift);
+                } else L = hl1_storage_load(A.scale, load[h], A.shift);
                 sh = cap < L; lg = cap > L;
                 m = sh ? L - cap : lg ? cap - L : 0.0;
             }

@@ -1,7 +1,7 @@
 // relmc_storage.hip — energy storage with a state of charge on the HL1 sequential chronology (relmc_hl1_seq_storage, contract in
 // include/relmc.h): the model of relmc_hl1_seq_load (relmc_seq.hip) at one load level, with up to RELMC_HL1_MAX_STORAGE storages given in
 // the call.  A unit of its own, so that relmc_seq.hip's code object stays what it was.  The storage checks and the accumulator fill are
-// relmc_hl1_host.h's, the storage step on the device relmc_hl1_storage_devfn.h's, both shared with the weather-year tracks.  The two rows of year records, (lole, eue, lolf)
+// relmc_hl1_host.h's, the kernel the storage track of relmc_hl1_storage_kernels.h.  The two rows of year records, (lole, eue, lolf)
 // and (served_hours, discharged_mwh, charged_mwh), are summed by relmc_hl1_reduce_kernel (hl1_reduce_queue, relmc_seq.hip), one row at a time.
 #include <algorithm>
 #include <cmath>
@@ -10,7 +10,7 @@
 #include <vector>
 
 #include "relmc_hl1_host.h"
-#include "relmc_storage_kernels.h"
+#include "relmc_hl1_storage_kernels.h"
 
 using namespace relmc_host;
 
@@ -47,7 +47,7 @@ int32_t relmc_hl1_seq_storage(relmc_ctx* ctx, uint64_t seed, uint64_t first_chai
     const int64_t per = hl1_chunk_items(n_chains, kHl1RecordBudget, (int64_t)years_per_chain * 2);             // a chain counts its records of both rows
     const int rc = hl1_run_records(ctx, "relmc_hl1_seq_storage", X, n_chains, per, years_per_chain, 2, sum,
         [&](int64_t c0, int64_t nc, int64_t) {
-            hipLaunchKernelGGL(relmc_hl1_storage_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
+            hipLaunchKernelGGL(relmc_hl1_storage_track_kernel<HL1_TRACK_STORAGE>, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
                                first_chain + (uint64_t)c0, nc, years_per_chain, start, A, X.years.get());
         },
         [&](int64_t c0, int64_t, int64_t nrec) { return hl1_two_row_copies(ctx, X.years.get(), c0 * years_per_chain, nrec, years_host, storage_years_host); },

@@ -1,8 +1,8 @@
 // relmc_variable.hip — weather-year wind and solar resources on the HL1 sequential chronology, with storage (relmc_hl1_var_load,
 // relmc_hl1_var_seq, relmc_hl1_var_weather_year, contract in include/relmc.h): the fleet of relmc_hl1_seq_load (relmc_seq.hip) against a
 // weather library in a slot of its own, with the storages of relmc_hl1_seq_storage given in the call.  A unit of its own, so that the
-// code objects of relmc_seq.hip and relmc_storage.hip stay what they were; the option and storage checks, the weather_host fill, the copies
-// and the accumulator fill are relmc_hl1_host.h's, the device leaves relmc_hl1_storage_devfn.h's, one copy for every track.  The two rows of year records, (lole, eue, lolf) and
+// code objects of relmc_seq.hip and relmc_storage.hip stay what they were; the kernel is the weather track of relmc_hl1_storage_kernels.h, the
+// body of relmc_hl1_var_seq relmc_hl1_host.h's hl1_weather_seq, which relmc_hl1_stress_seq shares.  The two rows of year records, (lole, eue, lolf) and
 // (served_hours, discharged_mwh, charged_mwh), are summed by relmc_hl1_reduce_kernel (hl1_reduce_queue, relmc_seq.hip), one row at a time.
 #include <algorithm>
 #include <cmath>
@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "relmc_hl1_host.h"
-#include "relmc_variable_kernels.h"
+#include "relmc_hl1_storage_kernels.h"
 
 using namespace relmc_host;
 
@@ -89,46 +89,8 @@ int32_t relmc_hl1_var_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, i
                           relmc_hl1_storage_acc* acc, relmc_hl1_seq_year* years_host, relmc_hl1_storage_year* storage_years_host,
                           int32_t* weather_host)
 {
-    const std::string who = "relmc_hl1_var_seq: ";
-    if (!ctx) return RELMC_ERR_INVALID;
-    if (!ctx->has_hl1_seq) return fail(ctx, RELMC_ERR_NO_CASE, who + "relmc_hl1_seq_load has not been called");
-    if (!ctx->has_hl1_var) return fail(ctx, RELMC_ERR_NO_CASE, who + "relmc_hl1_var_load has not been called");
-    auto& S = ctx->hl1_seq;
-    auto& V = ctx->hl1_var;
-    if (S.nhours != V.nhours)
-        return fail(ctx, RELMC_ERR_INVALID, who + "nhours of relmc_hl1_seq_load " + std::to_string(S.nhours) + " is not nhours of relmc_hl1_var_load " + std::to_string(V.nhours));
-    if (!hl1_chain_args_ok(acc, n_chains, years_per_chain, start)) return fail(ctx, RELMC_ERR_INVALID, who + "bad arguments");
-    if (!opts) return fail(ctx, RELMC_ERR_INVALID, who + "opts is null");
-    if (!std::isfinite(opts->scale) || !std::isfinite(opts->shift)) return fail(ctx, RELMC_ERR_INVALID, who + "scale / shift not finite");
-    Hl1VarArgs A; std::memset(&A, 0, sizeof(A));
-    if (const int rc = hl1_resource_scales(ctx, who, opts->resource_scale, V.n_res, A.rscale)) return rc;
-    if (const int rc = hl1_pick_check(ctx, who, opts->pick, opts->reserved)) return rc;
-    if (const int rc = hl1_storage_count_check(ctx, who, n_storage, storage)) return rc;
-    for (int i = 0; i < n_storage; ++i) {
-        const relmc_hl1_storage& v = storage[i];
-        const std::string st = who + "storage " + std::to_string(i) + ": ";
-        if (const int rc = hl1_storage_check(ctx, st, v)) return rc;
-        A.st[i] = v;
-    }
-    A.scale = opts->scale; A.shift = opts->shift; A.n_storage = n_storage;
-    A.n_res = V.n_res; A.n_weather = V.n_weather; A.pick = opts->pick;
-    A.out = V.out.get(); A.wload = V.has_load ? V.load.get() : nullptr;
-    std::memset(acc, 0, sizeof(*acc));
-    if (n_chains == 0) return RELMC_OK;
-    hl1_weather_fill(weather_host, seed, first_chain, n_chains, years_per_chain, V.n_weather, opts->pick);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    double sum[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    const int64_t per = hl1_chunk_items(n_chains, kHl1RecordBudget, (int64_t)years_per_chain * 2);             // a chain counts its records of both rows
-    const int rc = hl1_run_records(ctx, "relmc_hl1_var_seq", V.rec, n_chains, per, years_per_chain, 2, sum,
-        [&](int64_t c0, int64_t nc, int64_t) {
-            hipLaunchKernelGGL(relmc_hl1_var_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, ctx->stream, S.dcase.get(), S.load.get(), seed,
-                               first_chain + (uint64_t)c0, nc, years_per_chain, start, A, V.rec.years.get());
-        },
-        [&](int64_t c0, int64_t, int64_t nrec) { return hl1_two_row_copies(ctx, V.rec.years.get(), c0 * years_per_chain, nrec, years_host, storage_years_host); },
-        hl1_no_host_step);
-    if (rc) return rc;
-    hl1_storage_acc_fill(acc, n_chains * years_per_chain, sum, sum + 6);
-    return RELMC_OK;
+    return hl1_weather_seq<false, Hl1VarArgs>(ctx, "relmc_hl1_var_seq", relmc_hl1_storage_track_kernel<HL1_TRACK_WEATHER>, seed, first_chain, n_chains, years_per_chain,
+                                              start, opts, n_storage, storage, acc, years_host, storage_years_host, weather_host);
 }
 
 }  // extern "C"

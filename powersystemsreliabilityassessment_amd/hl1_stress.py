@@ -14,7 +14,6 @@ the same hours; repairs are unchanged (relmc_hl1_stress_load, relmc_hl1_stress_s
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import time
 from dataclasses import dataclass, field
@@ -140,30 +139,10 @@ def run_sequential_stress(gens, load: hl1.LoadModel, weather, stress, years: int
     hl1._seq_model_load(eng, gens, load)
     hl1_variable._weather_load(eng, w)
     _stress_load(eng, s)
-    opts = _abi.Hl1VarOpts()
-    for r, v in enumerate(rs):
-        opts.resource_scale[r] = v
-    opts.scale, opts.shift, opts.pick, opts.reserved = scale, shift, hl1_variable._PICK[pick], 0
-    arr = (_abi.Hl1Storage * max(len(st), 1))(*[_abi.Hl1Storage(float(x.charge_mw), float(x.discharge_mw), float(x.energy_mwh),
-                                                                 float(x.eta_charge), float(x.eta_discharge), x.soc0) for x in st])
-    acc = _abi.Hl1StorageAcc()
-    yr, sy, wy = np.zeros((years, 3)), np.zeros((years, 3)), np.zeros(years, dtype=np.int32)
-    eng._check(eng.L.relmc_hl1_stress_seq(eng._h, int(seed), 0, chains, years // chains, hl1._SEQ_START[start], C.byref(opts), len(st),
-                                          arr if st else None, C.byref(acc), yr.ctypes.data_as(C.POINTER(_abi.Hl1SeqYear)),
-                                          sy.ctypes.data_as(C.POINTER(_abi.Hl1StorageYear)), wy.ctypes.data_as(_abi.c_int32_p)), "relmc_hl1_stress_seq")
-    k = np.arange(10, years + 1, 10)
-    history = np.cumsum(yr[:, 0])[k - 1] / k if k.size else np.zeros(0)
-    lole, eue, lolf = acc.sum_lole / years, acc.sum_eue / years, acc.sum_lolf / years
-    energy = (w.output_mw.sum(axis=2) * np.asarray(rs)[None, :]).sum(axis=1) if w.n_resources else np.zeros(w.n_weather)
-    method = "Sequential MC + stress" + (" + storage" if st else "")
-    return StressReliabilityResult(method, lole, eue, time.time() - t0, history,
-                                   lolf_occ_yr=lolf, lold_hours=lole / lolf if lolf > 0 else float("nan"),
-                                   year_lole=yr[:, 0].copy(), year_eue=yr[:, 1].copy(), year_lolf=yr[:, 2].copy(),
-                                   served_hours_yr=acc.sum_served / years, discharged_mwh_yr=acc.sum_discharged / years,
-                                   charged_mwh_yr=acc.sum_charged / years, year_served=sy[:, 0].copy(), year_discharged=sy[:, 1].copy(),
-                                   year_charged=sy[:, 2].copy(), storages=st, scale=scale, shift=shift,
-                                   year_weather=wy, offered_mwh_yr=float(energy[wy].mean()), resource_scale=rs, pick=pick,
-                                   unit_class=s.unit_class.copy(), mean_multiplier=s.fail_mult.mean(axis=2)[wy].mean(axis=0))
+    r = hl1_variable._run_weather_track(eng, "relmc_hl1_stress_seq", StressReliabilityResult, "Sequential MC + stress" + (" + storage" if st else ""), t0, w,
+                                        years, chains, start, seed, rs, scale, shift, pick, st, unit_class=s.unit_class.copy())
+    r.mean_multiplier = s.fail_mult.mean(axis=2)[r.year_weather].mean(axis=0)
+    return r
 
 
 def _hourly_copt(cap, qdown, net, step_size: float) -> tuple:

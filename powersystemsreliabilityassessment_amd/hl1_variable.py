@@ -119,6 +119,34 @@ def _weather_load(eng, w: WeatherYears) -> None:
         eng._hl1_var_loaded = key
 
 
+def _run_weather_track(eng, entry: str, result, method: str, t0: float, w: WeatherYears, years: int, chains: int, start: str, seed: int,
+                       rs: tuple, scale: float, shift: float, pick: str, st: tuple, **more):
+    """The call of `entry` (relmc_hl1_var_seq, or relmc_hl1_stress_seq, which has its signature) on the models already loaded, and its
+    outputs as a `result` (VariableReliabilityResult or a subclass; `more`: the subclass's own fields).  The arguments are checked."""
+    opts = _abi.Hl1VarOpts()
+    for r, v in enumerate(rs):
+        opts.resource_scale[r] = v
+    opts.scale, opts.shift, opts.pick, opts.reserved = scale, shift, _PICK[pick], 0
+    arr = (_abi.Hl1Storage * max(len(st), 1))(*[_abi.Hl1Storage(float(s.charge_mw), float(s.discharge_mw), float(s.energy_mwh),
+                                                                 float(s.eta_charge), float(s.eta_discharge), s.soc0) for s in st])
+    acc = _abi.Hl1StorageAcc()
+    yr, sy, wy = np.zeros((years, 3)), np.zeros((years, 3)), np.zeros(years, dtype=np.int32)
+    eng._check(getattr(eng.L, entry)(eng._h, int(seed), 0, chains, years // chains, hl1._SEQ_START[start], C.byref(opts), len(st),
+                                     arr if st else None, C.byref(acc), yr.ctypes.data_as(C.POINTER(_abi.Hl1SeqYear)),
+                                     sy.ctypes.data_as(C.POINTER(_abi.Hl1StorageYear)), wy.ctypes.data_as(_abi.c_int32_p)), entry)
+    k = np.arange(10, years + 1, 10)
+    history = np.cumsum(yr[:, 0])[k - 1] / k if k.size else np.zeros(0)
+    lole, eue, lolf = acc.sum_lole / years, acc.sum_eue / years, acc.sum_lolf / years
+    energy = (w.output_mw.sum(axis=2) * np.asarray(rs)[None, :]).sum(axis=1) if w.n_resources else np.zeros(w.n_weather)
+    return result(method, lole, eue, time.time() - t0, history,
+                  lolf_occ_yr=lolf, lold_hours=lole / lolf if lolf > 0 else float("nan"),
+                  year_lole=yr[:, 0].copy(), year_eue=yr[:, 1].copy(), year_lolf=yr[:, 2].copy(),
+                  served_hours_yr=acc.sum_served / years, discharged_mwh_yr=acc.sum_discharged / years,
+                  charged_mwh_yr=acc.sum_charged / years, year_served=sy[:, 0].copy(), year_discharged=sy[:, 1].copy(),
+                  year_charged=sy[:, 2].copy(), storages=st, scale=scale, shift=shift,
+                  year_weather=wy, offered_mwh_yr=float(energy[wy].mean()), resource_scale=rs, pick=pick, **more)
+
+
 def run_sequential_variable(gens, load: hl1.LoadModel, weather, years: int, *, storages=(), resource_scale=None, scale: float = 1.0,
                             shift: float = 0.0, pick: str = "random", seed: int = 1, chains: int = 1, start: str = "all_up",
                             engine=None) -> VariableReliabilityResult:
@@ -141,30 +169,8 @@ def run_sequential_variable(gens, load: hl1.LoadModel, weather, years: int, *, s
     t0 = time.time()
     hl1._seq_model_load(eng, gens, load)
     _weather_load(eng, w)
-    opts = _abi.Hl1VarOpts()
-    for r, v in enumerate(rs):
-        opts.resource_scale[r] = v
-    opts.scale, opts.shift, opts.pick, opts.reserved = scale, shift, _PICK[pick], 0
-    arr = (_abi.Hl1Storage * max(len(st), 1))(*[_abi.Hl1Storage(float(s.charge_mw), float(s.discharge_mw), float(s.energy_mwh),
-                                                                 float(s.eta_charge), float(s.eta_discharge), s.soc0) for s in st])
-    acc = _abi.Hl1StorageAcc()
-    yr, sy, wy = np.zeros((years, 3)), np.zeros((years, 3)), np.zeros(years, dtype=np.int32)
-    eng._check(eng.L.relmc_hl1_var_seq(eng._h, int(seed), 0, chains, years // chains, hl1._SEQ_START[start], C.byref(opts), len(st),
-                                       arr if st else None, C.byref(acc), yr.ctypes.data_as(C.POINTER(_abi.Hl1SeqYear)),
-                                       sy.ctypes.data_as(C.POINTER(_abi.Hl1StorageYear)), wy.ctypes.data_as(_abi.c_int32_p)), "relmc_hl1_var_seq")
-    k = np.arange(10, years + 1, 10)
-    history = np.cumsum(yr[:, 0])[k - 1] / k if k.size else np.zeros(0)
-    lole, eue, lolf = acc.sum_lole / years, acc.sum_eue / years, acc.sum_lolf / years
-    energy = (w.output_mw.sum(axis=2) * np.asarray(rs)[None, :]).sum(axis=1) if w.n_resources else np.zeros(w.n_weather)
-    offered = float(energy[wy].mean())
     method = "Sequential MC + resources" + (" + storage" if st else "") if any(v > 0.0 for v in rs) else "Sequential MC" + (" + storage" if st else "")
-    return VariableReliabilityResult(method, lole, eue, time.time() - t0, history,
-                                     lolf_occ_yr=lolf, lold_hours=lole / lolf if lolf > 0 else float("nan"),
-                                     year_lole=yr[:, 0].copy(), year_eue=yr[:, 1].copy(), year_lolf=yr[:, 2].copy(),
-                                     served_hours_yr=acc.sum_served / years, discharged_mwh_yr=acc.sum_discharged / years,
-                                     charged_mwh_yr=acc.sum_charged / years, year_served=sy[:, 0].copy(), year_discharged=sy[:, 1].copy(),
-                                     year_charged=sy[:, 2].copy(), storages=st, scale=scale, shift=shift,
-                                     year_weather=wy, offered_mwh_yr=offered, resource_scale=rs, pick=pick)
+    return _run_weather_track(eng, "relmc_hl1_var_seq", VariableReliabilityResult, method, t0, w, years, chains, start, seed, rs, scale, shift, pick, st)
 
 
 def run_analytical_variable(gens, weather, load: hl1.LoadModel, resource_scale=None, step_size: float = 1.0) -> hl1.ReliabilityResult:

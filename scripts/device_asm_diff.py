@@ -11,9 +11,16 @@ CSRC = os.path.join(ROOT, "powersystemsreliabilityassessment_amd", "csrc")
 unit = sys.argv[1] if len(sys.argv) > 1 else "relmc_core.hip"
 rev = sys.argv[2] if len(sys.argv) > 2 else "HEAD"
 AREA_ARGS = "PKNS_8AreaCaseEPKNS_8AreaTiesEPKdmmiiiilPd"
-RENAMED = {"_ZN5relmc21relmc_hl1_area_kernelEPKNS_8AreaCaseEPKdmmiiiilPd": "_ZN5relmc21relmc_hl1_area_kernelILb0EEEv" + AREA_ARGS,
-           "_ZN5relmc25relmc_hl1_area_tie_kernelE" + AREA_ARGS: "_ZN5relmc21relmc_hl1_area_kernelILb1EEEv" + AREA_ARGS,
+AREA_PACK = "PKNS_8AreaCaseEPKNS_8AreaTiesEPKdmmiiiilDpKT0_Pd"      # relmc_hl1_area_kernel<TIES, VAR...>: VAR empty, or AreaVarArgs for the former relmc_hl1_area_var_kernel<TIES>
+RENAMED = {"_ZN5relmc21relmc_hl1_area_kernelEPKNS_8AreaCaseEPKdmmiiiilPd": "_ZN5relmc21relmc_hl1_area_kernelILb0EJEEEv" + AREA_PACK,
+           "_ZN5relmc25relmc_hl1_area_tie_kernelE" + AREA_ARGS: "_ZN5relmc21relmc_hl1_area_kernelILb1EJEEEv" + AREA_PACK,
            "_ZN5relmc27relmc_hl1_seq_reduce_kernelEPKdlPd": "_ZN5relmc23relmc_hl1_reduce_kernelEPKdlPd"}
+for ties in "01":
+    RENAMED["_ZN5relmc21relmc_hl1_area_kernelILb%sEEEv" % ties + AREA_ARGS] = "_ZN5relmc21relmc_hl1_area_kernelILb%sEJEEEv" % ties + AREA_PACK
+    RENAMED["_ZN5relmc25relmc_hl1_area_var_kernelILb%sEEEv" % ties + AREA_ARGS[:-2] + "NS_11AreaVarArgsEPd"] = "_ZN5relmc21relmc_hl1_area_kernelILb%sEJNS_11AreaVarArgsEEEEv" % ties + AREA_PACK
+TRACK_ARGS = "PKNS_10Hl1SeqCaseEPKdmmliiNS_%sEPd"            # relmc_hl1_storage_track_kernel<0 | 1 | 2>: the storage, weather and stress kernels
+for track, (was, args) in enumerate((("24relmc_hl1_storage_kernel", "14Hl1StorageArgs"), ("20relmc_hl1_var_kernel", "10Hl1VarArgs"), ("23relmc_hl1_stress_kernel", "13Hl1StressArgs"))):
+    RENAMED["_ZN5relmc" + was + "E" + TRACK_ARGS % args] = "_ZN5relmc30relmc_hl1_storage_track_kernelILi%dEEEv" % track + TRACK_ARGS % "12Hl1TrackArgsIXT_EE4type"
 
 
 def asm(csrc, out):

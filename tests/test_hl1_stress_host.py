@@ -53,7 +53,7 @@ def test_library_exports_the_stress_entry_points():
     for sym in SYMS:
         assert re.search(r"\b%s\s*\(" % sym, hdr) and sym in _lib.EXPORTS and (":" + sym) in jl, sym
     assert re.search(r"#define RELMC_HL1_STRESS_MAX_CLASSES\s+%d\b" % _abi.HL1_STRESS_MAX_CLASSES, hdr) and "HL1_STRESS_MAX_CLASSES = 8" in jl
-    assert re.search(r"^UNITS = .*\brelmc_stress\b", mk, re.M) and re.search(r"^HDRS = .*\brelmc_stress_kernels\.h\b", mk, re.M)
+    assert re.search(r"^UNITS = .*\brelmc_stress\b", mk, re.M) and re.search(r"^HDRS = .*\brelmc_hl1_storage_kernels\.h\b", mk, re.M)
     if not os.path.exists(_lib.LIB_PATH):
         _lib.build()
     L = _lib.load()

@@ -108,6 +108,19 @@ constexpr int kInjNform = 1;         // 16-lane tile: injection evaluation with 
 constexpr int kInjNformWide = 0;     // 64-lane tile: the same, measured -0.75 % (with the pair mask 0xCD on top -0.85 %, profiles/r3_pf/c40_v96.log); not taken: with either, one of the
                                     // 317 RTS-96 fixture states ends 6 iterations away from the C oracle (17 -> 23; the pin is +-1 on every state), tried and reverted
 constexpr int kRpairMaskWide = 0;    // 64-lane tile
+// The line slacks' pair reciprocal R = 1/(z+ z-) ONCE per trip (bit m = MODE m).  z+ and z- of a line change only at the very end of the update, so
+// the evaluation (site 0), the ratio test (site 2) and the update (site 6) form R from the same bits; where all three are pair sites the
+// evaluation keeps R in one register per line slot and the other two read it: 1/z+ = z- R, 1/z- = z+ R, the expressions and operand order of
+// frcp_pair<true>, no new rounding.  The compiler cannot do it (the three sites sit under separate L_ACT regions, none dominates another).
+// Not the rejected "1/z kept for both step passes" (14 doubles per lane, spilled): three doubles, lines only.  The injections share nothing:
+// sites 1, 4 and 7 use three different forms.  Per mode, because the three live doubles are not free everywhere: MODE 2 (the sequential
+// track) gets scratch accesses inside the interior-point loop with it and stays off.  Measurements: profiles/line_rcp_share/README.md.
+#ifdef RELMC_NO_LINE_RCP_SHARE             // ablation build: every site computes its own reciprocal
+constexpr int kLineRcpShareMask = 0;
+#else
+constexpr int kLineRcpShareMask = 0x01;      // 16-lane tile: the fused path (MODE 0 and its calibration twin)
+#endif
+constexpr int kLineRcpShareMaskWide = 0;   // 64-lane tile: no pair sites there (kRpairMaskWide)
 template <bool PAIR>
 DEVFI void frcp_pair(double a, double b, double& ra, double& rb)
 {

@@ -68,6 +68,19 @@ constexpr int kShadowMaskWide = 0xff;   // 64-lane tile
 // and RELMC_TRACE builds take the norms form on every trip.  Measurements: profiles/norm_paths/README.md.
 constexpr int kNormSplitMask = 0xff;       // 16-lane tile
 constexpr int kNormSplitMaskWide = 0;      // 64-lane tile: off (RTS-96 fused path +0.27 % with it, 1.1 x the run-to-run spread, and 16-60 B/lane more scratch in every mode)
+// The all-zero line record nl and injection entry ninj (the dummies that unused gather slots point to; they alias the workspace, so every trip
+// rebuilds them) written by the slot lanes that stand behind the last line and the last injection, inside the evaluation's own stores: such a
+// lane holds no element, so what it would store is exactly zero in every mode (status -> model leaves its slot off, the start point and the
+// update touch LFv, LGv and p only through alpha * 0).  Lane 0's explicit stores remain for a tile filled to the last slot (nl = LS RW,
+// ninj = IS RW: no lane behind).  Taken only where a static shape compiles nl and ninj in, so that the choice is made by the compiler: with
+// run-time dimensions it is two wave-uniform tests per trip that remove no instruction from the text, add four branches and, compiled, put
+// one or two more scratch accesses into the interior-point loop of ten of the sixteen instantiations -- those keep lane 0's stores, byte for byte.
+// -DRELMC_ZERO_EXPLICIT (ablation): lane 0 writes them on every trip in every instantiation.
+#ifdef RELMC_ZERO_EXPLICIT
+constexpr bool kZeroBySlot = false;
+#else
+constexpr bool kZeroBySlot = true;
+#endif
 // the one compare a pass spends on its descriptor: field 0 == field 3 (updates, back substitution), fields 2, 3 non-zero (inversion)
 #define PASS_IDLE(d) (((d).x & 0xffffu) == ((d).y >> 16))
 #define PASS_IDLE_INV(d) ((d).y != 0u)
@@ -124,6 +137,8 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
     constexpr int PF_MASK = TL::RW == 16 ? kPfMask : kPfMaskWide;                 // which LDS round trips are taken off the critical path (PFSITE)
     constexpr bool SHADOW = (((TL::RW == 16 ? kShadowMask : kShadowMaskWide) >> MODE) & 1) != 0;   // solver passes: all lanes compute, the stores are predicated (above)
     constexpr bool NSPLIT = (((TL::RW == 16 ? kNormSplitMask : kNormSplitMaskWide) >> MODE) & 1) != 0;   // second-stage norms only on trips that can end (above)
+    constexpr bool LSHARE = (((TL::RW == 16 ? kLineRcpShareMask : kLineRcpShareMaskWide) >> MODE) & 1) != 0 && PAIRSITE(0) && PAIRSITE(2) && PAIRSITE(6);   // one pair reciprocal of the line slacks per trip (relmc_devfn.h)
+    constexpr bool ZSLOT = kZeroBySlot && (SH::kMask & SH::grp_nl) != 0 && (SH::kMask & SH::grp_ninj) != 0;   // zero records by the slot lanes behind the last line / injection (above)
     constexpr int RW = TL::RW, BS = TL::BS, LS = TL::LS, IS = TL::IS, NBT = TL::NBT, WPB = TL::WPB, SPW = TL::SPW, OW = TL::OW;
     using DevCase = DevCaseT<TL>;
     using Partial = PartialT<TL>;
@@ -363,6 +378,10 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
         // NSPLIT: what the update leaves for the next trip's test -- |x|inf and the NaN flag of the x it wrote, and the test's first stage
         double x_inf = 0.0;
         bool x_nan = false, stage1 = false;
+        // LSHARE: R = 1/(z+ z-) of the line slots, the evaluation's, read by the ratio test and the update of the same trip
+        double lzr[LS];
+#pragma unroll
+        for (int s = 0; s < LS; ++s) lzr[s] = 1.0;
         uint32_t lozero = 0;                // bit s: lower bound of injection slot s relaxed to 0 (island rules 3, 4)
 #define ISC(s) ((RW * (s) + rlane >= ng) ? lscale : 1.0)      /* virtual generators (loads) scale with the hourly factor */
 #define ILOV(s, lo_) (((lozero >> (s)) & 1u) ? 0.0 : (lo_) * ISC(s))      /* lower bound of injection slot s from its table value lo_ */
@@ -799,7 +818,9 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                     if (L_ACT(s)) {
                         const double b = lb(s), rr = lr(s);
                         const double hp = LFv[s] - rr, hm = -LFv[s] - rr;
-                        double rzp, rzm; frcp_pair<PAIRSITE(0)>(lzp[s], lzm[s], rzp, rzm);
+                        double rzp, rzm;
+                        if constexpr (LSHARE) { lzr[s] = frcp(lzp[s] * lzm[s]); rzp = lzm[s] * lzr[s]; rzm = lzp[s] * lzr[s]; }
+                        else frcp_pair<PAIRSITE(0)>(lzp[s], lzm[s], rzp, rzm);
                         g = b * b * (lmup[s] * rzp + lmum[s] * rzm);
                         lx = __builtin_fma(b, lmup[s] - lmum[s], lx);
                         q = b * ((lmup[s] * hp + gamma) * rzp - (lmum[s] * hm + gamma) * rzm);
@@ -810,7 +831,9 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                         }
                     }
                     gown[s] = g;
-                    if (l < nlp) { st2(LR + 4 * l, g, lx); st2(LR + 4 * l + 2, lx + q, LFv[s]); }   // nl / ninj records (they alias W)
+                    // nl / ninj records (they alias W).  ZSLOT: the lane behind the last line writes the all-zero record nl with the same two stores --
+                    // it holds no line, so g = q = 0 and LGv = LFv = 0 from the setup on (they only ever receive alpha * 0)
+                    if (ZSLOT ? l <= nlp : l < nlp) { st2(LR + 4 * l, g, lx); st2(LR + 4 * l + 2, lx + q, LFv[s]); }
                     SLOT_FENCE();
                 }
 #pragma unroll
@@ -844,12 +867,16 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                             mx_lammu = vmax(mx_lammu, vmax(imup[s], imum[s]));
                         }
                     }
-                    if (j < nip) IR[j] = pv;
+                    if (ZSLOT ? j <= nip : j < nip) IR[j] = pv;      // ZSLOT: ... and the lane behind the last injection the zero entry ninj (its p stays 0)
                     st2(Stash + 2 * RW * s, invD, npd);
                     SLOT_FENCE();
                 }
                 PT_MARK(1)
-                if (rlane == 0) { st2(LR + 4 * nlp, 0.0, 0.0); st2(LR + 4 * nlp + 2, 0.0, 0.0); IR[nip] = 0.0; }
+                // the all-zero dummies that unused gather slots point to: by lane 0 where no slot lane stands behind the last element (a full tile)
+                if (rlane == 0) {
+                    if (!ZSLOT || nlp >= LS * RW) { st2(LR + 4 * nlp, 0.0, 0.0); st2(LR + 4 * nlp + 2, 0.0, 0.0); }
+                    if (!ZSLOT || nip >= IS * RW) IR[nip] = 0.0;
+                }
                 // ---- assemble: gather everything the KKT blocks need into registers ... -------------
                 uint32_t lblk_pf[LS]; uint32_t zo_pf = 0;
                 if constexpr (PFSITE(1)) {
@@ -1265,7 +1292,9 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                         if (L_ACT(s)) {
                             const double hp = LFv[s] - lr(s), hm = -LFv[s] - lr(s);
                             const double dzp = -hp - lzp[s] - dF[s], dzm = -hm - lzm[s] + dF[s];
-                            double rzp, rzm; frcp_pair<PAIRSITE(2)>(lzp[s], lzm[s], rzp, rzm);
+                            double rzp, rzm;
+                            if constexpr (LSHARE) { rzp = lzm[s] * lzr[s]; rzm = lzp[s] * lzr[s]; }
+                            else frcp_pair<PAIRSITE(2)>(lzp[s], lzm[s], rzp, rzm);
                             const double dmup = -lmup[s] + (gamma - lmup[s] * dzp) * rzp;
                             const double dmum = -lmum[s] + (gamma - lmum[s] * dzm) * rzm;
                             // ratio tests without divisions by the steps: min_k z_k/(-dz_k) = 1 / max_k(-dz_k/z_k)
@@ -1327,7 +1356,9 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                         if (L_ACT(s)) {
                             const double hp = LFv[s] - lr(s), hm = -LFv[s] - lr(s);
                             const double dzp = -hp - lzp[s] - dF[s], dzm = -hm - lzm[s] + dF[s];
-                            double rzp, rzm; frcp_pair<PAIRSITE(6)>(lzp[s], lzm[s], rzp, rzm);
+                            double rzp, rzm;
+                            if constexpr (LSHARE) { rzp = lzm[s] * lzr[s]; rzm = lzp[s] * lzr[s]; }
+                            else frcp_pair<PAIRSITE(6)>(lzp[s], lzm[s], rzp, rzm);
                             const double dmup = -lmup[s] + (gamma - lmup[s] * dzp) * rzp;
                             const double dmum = -lmum[s] + (gamma - lmum[s] * dzm) * rzm;
                             lzp[s] = __builtin_fma(alphap, dzp, lzp[s]); lzm[s] = __builtin_fma(alphap, dzm, lzm[s]);

@@ -74,16 +74,17 @@ DEVFI void area_solve(double* __restrict__ mg, double* __restrict__ R, const dou
     }
 }
 
-// R of a step in which the ties of the mask `down` (bit t: tie t) are DOWN: from 0.0, the UP ties' capacities in ascending tie order
-DEVFI void area_tie_residual(double* __restrict__ R, const AreaTies* __restrict__ TL, int n, uint32_t down)
+// R of a step in which the ties of the mask `down` (bit t: tie t) are DOWN: from 0.0, the UP ties' capacities cap[t] in ascending tie
+// order (TL->cap, or those of a level of relmc_hl1_area_sweep)
+DEVFI void area_tie_residual(double* __restrict__ R, const AreaTies* __restrict__ TL, const double* __restrict__ cap, int n, uint32_t down)
 {
     for (int e = 0; e < n * n; ++e) R[e * 64] = 0.0;
     const int nt = TL->n_ties;
     for (int t = 0; t < nt; ++t)
         if (!((down >> t) & 1u)) {
             const int i = TL->from[t], j = TL->to[t];
-            R[(i * n + j) * 64] += TL->cap[t];
-            R[(j * n + i) * 64] += TL->cap[t];
+            R[(i * n + j) * 64] += cap[t];
+            R[(j * n + i) * 64] += cap[t];
         }
 }
 
@@ -308,7 +309,7 @@ __global__ void __launch_bounds__(64) relmc_hl1_area_kernel(const AreaCase* __re
                     if constexpr (TIES) {
                         if (inter && neg) {
                             const uint32_t tdown = seg[nw][i];
-                            if (tdown) { area_tie_residual(R, TL, na, tdown); area_solve<false>(mg, R, nullptr, na, flow); }
+                            if (tdown) { area_tie_residual(R, TL, TL->cap, na, tdown); area_solve<false>(mg, R, nullptr, na, flow); }
                             else area_solve(mg, R, A->tie, na, flow);
                         }
                     } else if (inter && neg) area_solve(mg, R, A->tie, na, flow);
@@ -409,7 +410,7 @@ __global__ void __launch_bounds__(64) relmc_hl1_area_kernel(const AreaCase* __re
                     if constexpr (TIES) {
                         if (inter && neg) {
                             const uint32_t tdown = seg[nw][i];
-                            if (tdown) { area_tie_residual(R, TL, na, tdown); area_solve<false>(mg, R, nullptr, na, flow); }
+                            if (tdown) { area_tie_residual(R, TL, TL->cap, na, tdown); area_solve<false>(mg, R, nullptr, na, flow); }
                             else area_solve(mg, R, A->tie, na, flow);
                         }
                     } else if (inter && neg) area_solve(mg, R, A->tie, na, flow);

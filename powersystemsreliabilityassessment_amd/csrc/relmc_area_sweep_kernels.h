@@ -7,29 +7,6 @@
 
 namespace relmc {
 
-// load of a level at one hour: scale * load + shift with the product and the sum each rounded, as numpy's scale * load + shift.  The rule
-// of hl1_sweep_load (relmc_sweep_kernels.h), restated here so that this unit does not take that header's kernel with it.
-DEVFI double area_sweep_load(double scale, double ld, double shift)
-{
-#pragma clang fp contract(off)
-    const double p = scale * ld;
-    return p + shift;
-}
-
-// area_tie_residual with the level's capacities: R of a step in which the ties of the mask `down` are DOWN, from 0.0, the UP ties'
-// capacities cap[t] in ascending tie order
-DEVFI void area_sweep_tie_residual(double* __restrict__ R, const AreaTies* __restrict__ TL, const double* __restrict__ cap, int n, uint32_t down)
-{
-    for (int e = 0; e < n * n; ++e) R[e * 64] = 0.0;
-    const int nt = TL->n_ties;
-    for (int t = 0; t < nt; ++t)
-        if (!((down >> t) & 1u)) {
-            const int i = TL->from[t], j = TL->to[t];
-            R[(i * n + j) * 64] += cap[t];
-            R[(j * n + i) * 64] += cap[t];
-        }
-}
-
 // Each area's capacity of one step, once per fleet in use: fleet 0 (every UP unit) to c0[a] and, with F1, fleet 1 (a withheld unit adds
 // 0.0) to c1[a], each from 0.0 over the area's units in ascending order as relmc_hl1_area_kernel sums them; the areas' loads of hour h to
 // ld[a].  The loop over the areas is written out (a is a constant in every body), so the three arrays are registers.
@@ -111,7 +88,7 @@ DEVFI void area_sweep_account(bool valid, int y, uint32_t fw, uint32_t rise, con
 
 // Chain c = first_chain + blockIdx.x: one wavefront per workgroup, one chain per wavefront, as relmc_hl1_area_kernel.  The window loop
 // below (the cursors of the units and, with TIES, of the ties; the window fill) is a COPY of that kernel's, on purpose: that kernel's code
-// must stay as it is, and sharing a window loop between kernels has cost the older kernel 1.6-3 % twice (relmc_sweep_kernels.h, DESIGN.md
+// must stay as it is, and sharing a window loop between kernels has cost the older kernel 1.6-3 % twice (relmc_hl1_chain_kernels.h, DESIGN.md
 // 6.12).
 //
 // Per step (one per lane): each area's capacity once per fleet in use and the areas' loads, in registers (area_sweep_caps).  Then the
@@ -119,12 +96,12 @@ DEVFI void area_sweep_account(bool valid, int y, uint32_t fw, uint32_t rise, con
 // shift_a); a level without a negative margin in the whole 64-step group takes nothing further (its flags are all down: no hour, no
 // event, no energy).  Otherwise the transfer solve where the lane's step has a negative margin -- left out for a level whose ties all
 // have capacity 0, where it could move nothing -- from the level's all-UP matrix X->lv[j].tie, or with a tie DOWN from the level's UP
-// ties (area_sweep_tie_residual); then relmc_hl1_area_kernel's flags, rising edges, counts and lane partials (area_sweep_account).
+// ties (area_tie_residual with the level's capacities); then relmc_hl1_area_kernel's flags, rising edges, counts and lane partials (area_sweep_account).
 //
 // Per-level state is held where a run-time level index costs nothing: the EUE partials aE[(j * rows + r) * 64 + lane] in LDS; the open
 // year and the previous-step loss mask of level j in lane j of two vector registers; the year's counts of level j, row r in lane
 // (j & 3) * 16 + r of the register pair of levels 0-3 or of levels 4-7.  No register array is indexed by the level, so the level loop
-// stays a loop and nothing goes to scratch (relmc_sweep_kernels.h tells what happened otherwise).  A level's year is closed when the
+// stays a loop and nothing goes to scratch (relmc_hl1_chain_kernels.h tells what happened otherwise).  A level's year is closed when the
 // level next takes a group with a later year in it, or at the end of the chain; a group it left out added nothing, so closing late
 // changes no sum.
 // Dynamic LDS, in this order: aE [n_levels * rows][64], margins [na][64], residuals [na * na][64] (fp64), masks [nw (+ 1 with
@@ -246,7 +223,7 @@ __global__ void __launch_bounds__(64) relmc_hl1_area_sweep_kernel(const AreaCase
 #pragma unroll
                 for (int a = 0; a < AREA_MAX; ++a) {
                     if (a >= na) break;
-                    const double m = (f1 ? c1[a] : c0[a]) - area_sweep_load(Lj->scale[a], ld[a], Lj->shift[a]);
+                    const double m = (f1 ? c1[a] : c0[a]) - hl1_sweep_load(Lj->scale[a], ld[a], Lj->shift[a]);
                     mg[a * 64] = m; neg |= valid && m < 0.0;
                 }
                 if (!__any(neg)) {                           // wave-uniform: every flag of the group is down
@@ -257,7 +234,7 @@ __global__ void __launch_bounds__(64) relmc_hl1_area_sweep_kernel(const AreaCase
                 if (neg) {
                     if ((solve >> j) & 1u) {
                         if constexpr (TIES) {
-                            if (tdown) { area_sweep_tie_residual(R, TL, Lj->cap, na, tdown); area_solve<false>(mg, R, nullptr, na, flow); }
+                            if (tdown) { area_tie_residual(R, TL, Lj->cap, na, tdown); area_solve<false>(mg, R, nullptr, na, flow); }
                             else area_solve(mg, R, Lj->tie, na, flow);
                         } else area_solve(mg, R, Lj->tie, na, flow);
                     }

@@ -11,8 +11,8 @@
 //   relmc_database.hip   the reference's dedupe and persistent unique-state database on the device
 //   relmc_comm.hip       the path's single collective: RCCL (bound at run time) or a host-supplied all-reduce, with a wall-clock guard
 //   relmc_seq.hip        sequential track (chronology, scaled-load hours, annual indices, the seqMain loop), the HL1 copper sheet, the HL1
-//                        sequential chronology (relmc_hl1_seq), its loss events (relmc_hl1_seq_events, kernels in relmc_event_kernels.h), its
-//                        load sweep (relmc_hl1_seq_sweep, kernel in relmc_sweep_kernels.h) and
+//                        sequential chronology (relmc_hl1_seq), its loss events (relmc_hl1_seq_events) and its load sweep
+//                        (relmc_hl1_seq_sweep), three instantiations of the one kernel template of relmc_hl1_chain_kernels.h, and
 //                        the record reduction and unit check of every HL1 chronology track
 //   relmc_hl1_host.h     (a header, included by the nine HL1 units around it) what their host code shares: the chunk rule, the loop over a
 //                        model's launches with the reduction of their year records (hl1_run_records), the argument and unit checks, and the one

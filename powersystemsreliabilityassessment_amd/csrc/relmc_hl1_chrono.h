@@ -1,6 +1,6 @@
-// relmc_hl1_chrono.h — device-only helpers of the HL1 chronology contract (include/relmc.h), shared by relmc_hl1_seq_kernel
-// (relmc_seq_kernels.h) and relmc_hl1_area_kernel (relmc_area_kernels.h).  Inline functions only: no kernel is defined here, so every
-// unit may include it.
+// relmc_hl1_chrono.h — device-only helpers of the HL1 chronology contract (include/relmc.h), shared by the kernels of every HL1
+// chronology track (relmc_hl1_chain_kernels.h, relmc_area_kernels.h and the others).  Inline functions only: no kernel is defined here,
+// so every unit may include it.
 #pragma once
 #include "relmc_devfn.h"
 
@@ -21,6 +21,16 @@ DEVFI void hl1_seq_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Load of a sweep level at one hour, L = scale * load + shift with the product and the sum each rounded, as numpy's scale * load + shift
+// (the contract's __dmul_rn / __dadd_rn: those two are plain operators in the HIP headers and were fused into one v_fma_f64, so the rule
+// is stated to the compiler).  For relmc_hl1_seq_sweep and, per area, relmc_hl1_area_sweep.
+DEVFI double hl1_sweep_load(double scale, double ld, double shift)
+{
+#pragma clang fp contract(off)
+    const double p = scale * ld;
+    return p + shift;
 }
 
 }  // namespace relmc

@@ -108,7 +108,7 @@ DEVFI uint32_t hl1_track_ncls(const Hl1StressArgs& A) { return (uint32_t)A.n_cla
 
 // Chain c = blockIdx.x * 4 + wave; the chronology is relmc_hl1_seq_kernel's, word for word (lane l owns units l and l + 64, windows of
 // HL1_SEQ_WINDOW steps filled into the wave's LDS masks, one step per lane, no workgroup barrier).  The window loop is written out here and
-// not shared with relmc_hl1_seq_kernel (relmc_seq_kernels.h), as relmc_hl1_sweep_kernel's is: sharing that loop between kernels cost the
+// not shared with relmc_hl1_seq_kernel (relmc_hl1_chain_kernels.h): sharing that loop between kernels as functions cost the
 // sequential kernel 1.6-3 % twice.  The three tracks are instantiations of this one text, each with the instructions it had as a kernel of
 // its own; what a track adds is under `if constexpr`, and the setup values a track has no use for are dead.
 //

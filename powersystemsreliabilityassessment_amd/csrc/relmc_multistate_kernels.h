@@ -48,7 +48,7 @@ DEVFI void hl1_ms_close_year(uint32_t& cl, double& e, uint32_t& cf, uint32_t& cd
 
 // Chain c = blockIdx.x * 4 + wave; the structure is relmc_hl1_seq_kernel's (lane l owns units l and l + 64, the cursors stay in
 // registers, windows filled into the wave's LDS masks, one step per lane, no workgroup barrier).  The window loop below is a COPY of
-// relmc_hl1_seq_kernel's (relmc_seq_kernels.h), on purpose: sharing that loop between kernels cost the sequential kernel 1.6-3 % twice
+// relmc_hl1_seq_kernel's (relmc_hl1_chain_kernels.h), on purpose: sharing that loop between kernels cost the sequential kernel 1.6-3 % twice
 // (DESIGN.md 6.12).  What differs:
 //   cursor    a state 0 / 1 / 2 instead of `down`, the unit's three means and how each state branches (hl1_ms_kinds); the transition
 //             that ends the sojourn timed by duration draw e takes its destination from branch draw e (hl1_ms_branch_u), and only when

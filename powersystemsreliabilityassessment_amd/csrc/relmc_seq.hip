@@ -9,8 +9,7 @@
 
 #include "relmc_hl1_host.h"
 #include "relmc_seq_kernels.h"
-#include "relmc_event_kernels.h"
-#include "relmc_sweep_kernels.h"
+#include "relmc_hl1_chain_kernels.h"
 
 namespace relmc_host {
 

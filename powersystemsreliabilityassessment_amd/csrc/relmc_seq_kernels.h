@@ -1,8 +1,8 @@
 // relmc_seq_kernels.h — kernels of the sequential track (Montecarlo_seq/: chronology sampling, contingency-hour compaction, annual indices)
-// and of the HL1 copper-sheet models (GeneratingAdequacy/PowerSystemAdequacy.jl:169-208 non-sequential, :214-268 sequential).
+// and of the HL1 copper-sheet non-sequential model (GeneratingAdequacy/PowerSystemAdequacy.jl:169-208), and the reduction of the year
+// records of every HL1 track.  The HL1 sequential chronology (:214-268) is relmc_hl1_chain_kernels.h's.
 #pragma once
 #include "relmc_devfn.h"
-#include "relmc_hl1_chrono.h"
 
 namespace relmc {
 
@@ -166,130 +166,6 @@ __global__ void __launch_bounds__(256) relmc_hl1_kernel(const Hl1Case* __restric
     if ((threadIdx.x & 63) == 0) { red[wv][0] = s_l; red[wv][1] = s_e; red[wv][2] = s_l2; red[wv][3] = s_e2; }
     __syncthreads();
     if (threadIdx.x < 4) partial[(size_t)blockIdx.x * 4 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-}
-
-// ---- HL1 sequential chronology (PowerSystemAdequacy.jl:214-268; contract in include/relmc.h): one wavefront per chain --------------
-// The wave's open year: fixed-order butterfly over the lanes' partials, lane 0 stores (lole, eue, lolf); the partials restart at zero
-DEVFI void hl1_seq_close_year(double& l, double& e, double& f, double* __restrict__ out)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { l += __shfl_xor(l, off); e += __shfl_xor(e, off); f += __shfl_xor(f, off); }
-    if ((threadIdx.x & 63) == 0) { out[0] = l; out[1] = e; out[2] = f; }
-    l = e = f = 0.0;
-}
-
-// Chain c = blockIdx.x * 4 + wave.  Lane l owns units l and l + 64; its cursor (state, next transition time, next draw) stays in
-// registers for the whole chain.  The chain advances in windows of HL1_SEQ_WINDOW steps: (1) the down intervals reaching into the
-// window are filled into the wave's LDS masks by the whole wave, 64 steps per instruction, one interval at a time (each lane touches
-// its own step, so a plain OR is race-free); (2) one step per lane: capacity of the UP units in ascending unit order, loss flag and
-// deficit against load[(n-1) mod H], rising edge (the previous step's flag from the neighbouring lane, lane 63's carried over), and the
-// lane partials of the open year, closed by a fixed-order reduction when a later year appears.  Records: year_out[chain][year][3].
-__global__ void __launch_bounds__(256) relmc_hl1_seq_kernel(const Hl1SeqCase* __restrict__ S, const double* __restrict__ load, uint64_t seed,
-                                                            uint64_t first_chain, int64_t n_chains, int32_t years, int32_t start,
-                                                            double* __restrict__ year_out)
-{
-    constexpr int W = HL1_SEQ_WINDOW;
-    __shared__ uint32_t masks[4][4][W];                     // [wave][mask word][step of the window], bit k & 31 of word k >> 5 = unit k down
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t cl = (int64_t)blockIdx.x * 4 + wv;
-    if (cl >= n_chains) return;                              // wave-uniform
-    const uint64_t chain = first_chain + (uint64_t)cl;
-    const int ngen = S->ngen, H = S->nhours, nw = (ngen + 31) >> 5, nslot = ngen > 64 ? 2 : 1;
-    uint32_t (*const seg)[W] = masks[wv];
-    const int64_t nsteps = (int64_t)years * H;
-    double* const out = year_out + (size_t)cl * (size_t)years * 3;
-
-    bool down[2], mine[2];
-    double tn[2], mf[2], mr[2];
-    int ev[2];
-    int64_t since[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const int k = lane + 64 * s;
-        mine[s] = k < ngen;
-        mf[s] = mine[s] ? S->mttf[k] : 1.0; mr[s] = mine[s] ? S->mttr[k] : 1.0;
-        down[s] = false; ev[s] = 0; since[s] = 1; tn[s] = 0.0;
-        if (mine[s]) {
-            if (start == RELMC_HL1_START_STATIONARY) { down[s] = hl1_seq_u(chain, k, 0, seed) < S->q[k]; ev[s] = 1; }
-            tn[s] = __dmul_rn(-(down[s] ? mr[s] : mf[s]), log(hl1_seq_u(chain, k, ev[s], seed)));    // T_1 (= 0 + duration)
-            ++ev[s];
-        }
-    }
-
-    double aL = 0.0, aE = 0.0, aF = 0.0;                     // this lane's partials of the open year ycur
-    int ycur = 0, gy = 0, gh = 0;                            // gy / gh: chain year and hour of the current 64-step group's first step
-    bool prev = false;                                       // loss flag of the step before the group (none before step 1)
-    for (int64_t w0 = 1; w0 <= nsteps; w0 += W) {
-        const int64_t w1 = w0 + W;
-        const int wlen = nsteps - w0 + 1 < W ? (int)(nsteps - w0 + 1) : W;
-        for (int q = 0; q < nw; ++q)
-            for (int i = lane; i < W; i += 64) seg[q][i] = 0u;
-        hl1_seq_wave_sync();
-        // (1) down intervals [ceil(T_odd), ceil(T_even)) of the window
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {                        // unrolled: the cursors stay in registers
-            if (s >= nslot) break;
-            bool more = mine[s];
-            while (__any(more)) {
-                int fb = 0, fe = 0;
-                if (more) {
-                    const int64_t c = (int64_t)__builtin_ceil(tn[s]);             // the transition takes effect from step c on
-                    if (down[s]) {
-                        const int64_t a = since[s] > w0 ? since[s] : w0, b = c < w1 ? c : w1;
-                        if (b > a) { fb = (int)(a - w0); fe = (int)(b - w0); }
-                    }
-                    if (c >= w1) more = false;                                    // the cursor waits for a later window
-                    else {
-                        down[s] = !down[s]; since[s] = c;
-                        const double l = log(hl1_seq_u(chain, lane + 64 * s, ev[s], seed));
-                        tn[s] = __dadd_rn(tn[s], __dmul_rn(-(down[s] ? mr[s] : mf[s]), l));   // no FMA: the host model rounds the same way
-                        ++ev[s];
-                    }
-                }
-                for (uint64_t pend = __ballot(fe > fb); pend; pend &= pend - 1) {
-                    const int src = __builtin_ctzll(pend);
-                    const int sb = __builtin_amdgcn_readlane(fb, src), se = __builtin_amdgcn_readlane(fe, src), sk = src + 64 * s;
-                    uint32_t* const row = seg[sk >> 5];
-                    const uint32_t bit = 1u << (sk & 31);
-                    for (int h = sb + lane; h < se; h += 64) row[h] |= bit;
-                }
-            }
-        }
-        hl1_seq_wave_sync();
-        // (2) one step per lane
-        for (int g = 0; g < wlen; g += 64) {
-            const int i = g + lane;
-            const bool valid = i < wlen;
-            int h = gh + lane, y = gy;
-            while (h >= H) { h -= H; ++y; }
-            bool f = false;
-            double d = 0.0;
-            if (valid) {
-                double cap = 0.0;
-                for (int q = 0; q < nw; ++q) {
-                    const uint32_t up = ~seg[q][i];
-                    const int kn = ngen - 32 * q < 32 ? ngen - 32 * q : 32;
-                    for (int b = 0; b < kn; ++b) cap += ((up >> b) & 1u) ? S->cap[32 * q + b] : 0.0;   // ascending units; + 0.0 is exact
-                }
-                const double ld = load[h];
-                f = cap < ld;
-                d = f ? ld - cap : 0.0;
-            }
-            const int fl = __shfl_up((int)f, 1);
-            const bool r = f && !(lane == 0 ? prev : fl != 0);
-            prev = __shfl((int)f, 63) != 0;
-            for (;;) {
-                if (valid && y == ycur) { aL += f ? 1.0 : 0.0; aE += d; aF += r ? 1.0 : 0.0; }
-                if (!__any(valid && y > ycur)) break;
-                hl1_seq_close_year(aL, aE, aF, out + (size_t)ycur * 3);
-                ++ycur;
-            }
-            gh += 64;
-            while (gh >= H) { gh -= H; ++gy; }
-        }
-        hl1_seq_wave_sync();
-    }
-    hl1_seq_close_year(aL, aE, aF, out + (size_t)ycur * 3);
 }
 
 // Sums of relmc_hl1_seq_acc over n year records (lole, eue, lolf) of any HL1 track (hl1_reduce_queue, relmc_seq.hip): grid-stride in a

@@ -6,7 +6,8 @@ for _area_var, whose launch holds 2^22 / (1000 * 6) = 699 chains), both start ru
 child process per library (RELMC_LIB_PATH), every child under a time limit, then the comparison.  The calls are the raw-ABI helpers of the
 tests.
   python scripts/hl1_bit_identity.py PARENT.so [NEW.so] [--out DIR]     -> DIR/bit_identity.txt (default DIR: a new temporary directory, printed), exit 1 if any differ
-NEW.so defaults to this tree's build.  Used for profiles/hl1_host_driver/bit_identity.txt, profiles/hl1_storage_devfn/bit_identity.txt and profiles/hl1_storage_template/bit_identity.txt."""
+NEW.so defaults to this tree's build.  Used for profiles/hl1_host_driver/bit_identity.txt, profiles/hl1_storage_devfn/bit_identity.txt, profiles/hl1_storage_template/bit_identity.txt and
+profiles/hl1_chain_template/bit_identity.txt."""
 import ctypes as C
 import hashlib
 import importlib.util

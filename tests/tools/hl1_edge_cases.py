@@ -4,7 +4,9 @@ and the two lanes' slots, years shorter than a 64-lane group or straddling the 5
 longer than the horizon, zero capacities, loads equal to reachable capacity sums, 8 areas on the topologies where augmenting paths are
 long, 32 failing ties on years around the window length, and the planning model's 8 ELU slots in week 53.  tests/test_hl1_chrono_edges.py
 and its _host companion run the sweep, storage and event kernels on the same seq shapes (chrono_shapes), with the storages, sweep levels,
-withheld units and coverage conditions defined beside them.  Every value is computed here; nothing is read from disk."""
+withheld units and coverage conditions defined beside them.  tests/test_hl1_track_edges.py and its _host companion run the weather,
+stress, multi-state and area-weather kernels there too (track_shapes, ms_shapes), with the weather libraries, stress multipliers, outage
+classes, three-state fleets and the largest area configuration defined below.  Every value is computed here; nothing is read from disk."""
 from __future__ import annotations
 
 import math
@@ -259,6 +261,252 @@ def area_tie_edges(ngen, nhours):
     kf[1::6] = rng.uniform(2.0, 6.0, kf[1::6].size)
     kf[7], kf[12] = math.inf, 1e30
     return units, cap, mttf, mttr, loads, ties, kf, kr
+
+
+# ---- the weather, stress, multi-state and area-weather kernels (tests/test_hl1_track_edges.py and its _host companion) -----------------
+EDGE_UNITS = (0, 31, 32, 63, 64, 127)                           # first and last unit of a mask word, of a lane slot, of the largest fleet
+MS_NHOURS_EDGES = (1, 24, 63, 64, 65, 255, 256, 257, 511, 512, 513)      # NHOURS_EDGES and the edges of the multi-state kernel's 256-step window
+SPIKE = 2.0 ** 60                                               # a multiplier that uses up every draw at once; 2^60 + E == 2^60 for E < 128
+
+
+def _tool(name):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", "tools", name + ".py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def edge_weather(load, n_weather, n_res, curves, share=0.06):
+    """A weather library for the curve `load` -> (output_mw[n_weather, n_res, H], load curves [n_weather, H] or None).  The outputs are
+    multiples of 1/64 MW; resource r gives at most share * (1 + r / 4) / n_res of the mean load, so all of them together stay below
+    2 * share of it.  The last resource is identically 0 in weather year 1 (0 if there is one weather year).  With `curves` weather year
+    w has the curve load * f_w, f_w spread evenly over 0.94 .. 1.06 (one year: 1.0): the first weather years lose little, the last ones
+    much, so two weather years give different records."""
+    load = np.asarray(load, dtype=np.float64)
+    H = load.size
+    rng = np.random.default_rng(7000 + 31 * n_weather + 7 * n_res + H)
+    top = share * abs(float(load.mean())) * (1.0 + np.arange(n_res) / 4.0) / max(n_res, 1)
+    out = np.floor(rng.uniform(0.0, 1.0, (n_weather, n_res, H)) * top[None, :, None] * 64.0) / 64.0
+    if n_res:
+        out[min(1, n_weather - 1), n_res - 1, :] = 0.0
+    wl = None
+    if curves:
+        lo, hi = (0.4, 0.6) if H == 1 else (0.6, 1.06)
+        f = np.linspace(lo, hi, n_weather) if n_weather > 1 else np.ones(1)
+        wl = load[None, :] * f[:, None]
+    return out, wl
+
+
+def spike_hours(H):
+    """The hours of edge_stress's spikes: every second hour of a stretch that starts at H // 3 and is about a quarter of the year long
+    (three spikes at least, where the year has room for them)."""
+    s0 = H // 3
+    return list(range(s0, min(H, s0 + max(5, H // 4)), 2))
+
+
+def edge_stress(n_weather, n_classes, H, spike=SPIKE):
+    """fail_mult[n_weather, n_classes, H], n_classes >= 3, dyadic.
+      class 0   1/8 .. 3 in steps of 1/8, with zero stretches at the start, in the middle and at the end of weather year 0, and weather
+                year 1 (0 if there is one) zero throughout: G[H] == 0 there, so a draw passes that year unchanged
+      class 1   as class 0 without the zero stretches, but in the last weather year zero except for SPIKE in every second hour of
+                spike_hours(H): a UP unit of the class fails at the start of the first spike; one that becomes UP inside a spike hour
+                fails within it; one that becomes UP in the hour between two spikes has t = G[j] + E == G[j] (E < 128 is below half an
+                ulp of 2^60), lands on that hour, which has no slope (d == 0), and fails at its end, where the next spike begins.  The
+                contract's arithmetic puts each of these failures on a whole hour n exactly (E / 2^60 of an hour is below half an ulp
+                of any n >= 1), and a transition at n counts for step n; an hour loop in real arithmetic has it a moment after n, in
+                step n + 1.  So hl1_stress_model.literal_stress_chain is held against the model with spike = 2^10, which still fails
+                every unit within the hour but absorbs no draw
+      class 2   2^-24 in every hour: no unit of it fails before a chain ends
+      others    1/4 .. 4 in steps of 1/4, each with a zero stretch of its own
+    At H = 1 a row is one hour: class 0 is 1/2, 0, 2, ... over the weather years, class 1 is 1 and SPIKE in the last weather year."""
+    assert n_classes >= 3
+    rng = np.random.default_rng(8000 + 31 * n_weather + 7 * n_classes + H)
+    m = rng.integers(1, 25, (n_weather, n_classes, H)) / 8.0
+    m[:, 3:, :] = rng.integers(1, 17, (n_weather, n_classes - 3, H)) / 4.0
+    zero_year, spike_year = min(1, n_weather - 1), n_weather - 1
+    if H == 1:
+        m[:, 0, 0] = [(0.5, 0.0, 2.0)[w % 3] for w in range(n_weather)]
+        m[:, 1, 0] = 1.0
+        m[spike_year, 1, 0] = spike
+    else:
+        a, b = max(1, H // 12), max(1, H // 10)
+        m[0, 0, :a] = 0.0
+        m[0, 0, H // 2 - b // 2:H // 2 - b // 2 + b] = 0.0
+        m[0, 0, H - b:] = 0.0
+        m[zero_year, 0, :] = 0.0
+        m[spike_year, 1, :] = 0.0
+        m[spike_year, 1, spike_hours(H)] = spike
+        for c in range(3, n_classes):
+            s = (c * H) // n_classes
+            m[:, c, s:s + a] = 0.0
+    m[:, 2, :] = 2.0 ** -24
+    return m
+
+
+def edge_classes(ngen, n_classes=3):
+    """unit_class[ngen]: the units of EDGE_UNITS that exist have a class (1, 2, 0, 1, ... in their order, so unit 0 is in the spike
+    class), the units next to them that are not EDGE_UNITS themselves have class -1, and the others take -1, 0, 1, ... in turn (unit 2,
+    seq_fleet's unit with repairs of minutes, is in class 1 when n_classes is 3).  Every class is used from n_classes + 3 units on."""
+    cls = np.array([k % (n_classes + 1) - 1 for k in range(ngen)], dtype=np.int32)
+    edge = [k for k in EDGE_UNITS if k < ngen]
+    for k in edge:
+        for nb in (k - 1, k + 1):
+            if 0 <= nb < ngen and nb not in edge:
+                cls[nb] = -1
+    for i, k in enumerate(edge):
+        cls[k] = (i + 1) % n_classes
+    return cls
+
+
+def track_shapes():
+    """chrono_shapes() with the weather pick of each: RANDOM (0) on the all-UP shapes, CYCLE (1) on the stationary ones."""
+    return [s + (s[6],) for s in chrono_shapes()]
+
+
+# (pick, n_weather) under which the g*-1 shapes (first_chain = 2^32 - 4, six-year chains) are run so that a weather pick without the
+# chain's upper word shows: RANDOM over 3 weather years (the upper word is a Philox counter word), CYCLE over 5 (2^32 * 6 mod 5 = 1; over
+# 3 weather years 2^32 * 6 mod 3 = 0: chain 2^32 + j would have chain j's weather years)
+UPPER_WORD_PICKS = ((0, 3), (1, 5))
+
+
+def mixed_weather_groups(W, H, years):
+    """The number of 64-step groups (of the 512-step windows) of the chains W[nchains, years] that hold steps of two or more different
+    weather years."""
+    W = np.asarray(W).reshape(-1, years)
+    S = years * H
+    n = 0
+    for w in W:
+        per_step = np.repeat(w, H)
+        for g0 in range(0, S, 64):
+            n += np.unique(per_step[g0:min(g0 + 64, S)]).size > 1      # 512 is a multiple of 64: the groups of every window start at g0
+    return n
+
+
+def track_coverage(label, cnt, W, H, years):
+    """The conditions on a shape's inputs under edge_weather and edge_storages, on the step counters of hl1_variable_model.variable_chain
+    and the weather years W: storage_coverage's (short, lost and discharging steps; long, served and charging steps, from which nhours = 1
+    is exempt as it is there: its curve has one hour, the all-UP capacity), quiet groups beside serial ones, every weather year of a
+    three-year library drawn, and for years shorter than a group some group that holds two weather years."""
+    storage_coverage(label, cnt)
+    assert 0 < cnt["serial_groups"] < cnt["groups"], (label, cnt)
+    assert np.unique(W).size >= 3, (label, np.unique(W))
+    if H < 64:
+        assert mixed_weather_groups(W, H, years) > 0, label
+
+
+def stress_coverage(label, cnt, H, ngen):
+    """The conditions on a shape's inputs under edge_stress and edge_classes, on hl1_stress_model.stress_chronology's counters: failures
+    through the failure time and plain transitions, a draw that no year uses up (`never`), and on every year longer than one hour a draw
+    carried across a year, a landing on an hour without slope, and a failure within the hour of the repair.  nhours = 1 is exempt from
+    these three: its one-hour rows have no second hour to carry into or land on (a carried draw and an immediate failure do occur and are
+    asserted; `flat` cannot).  A fleet of one unit has one class, so it has no failure of a class -1 unit: ngen = 1 is exempt from it."""
+    assert cnt["failures"] > 0 and cnt["plain"] > 0 and 0 < cnt["never"] < cnt["failures"], (label, cnt)
+    assert cnt["carried"] > 0 and cnt["immediate"] > 0, (label, cnt)
+    if H > 1:
+        assert cnt["flat"] > 0, (label, cnt)
+    if ngen > 1:
+        assert cnt["plain_failures"] > 0, (label, cnt)
+
+
+MS_PATTERNS = ((1.0, 0.3, 0.0), (0.5, 0.0, 1.0), (0.0, 1.0, 1.0))      # first_p of a derated unit beside three_state's, which lies strictly inside
+
+
+def ms_fleet(ngen, nhours):
+    """seq_fleet(ngen, nhours) with three-state units -> (units, two_state_image, load), units as hl1_multistate_model's tuples.
+    (hl1_multistate_model.edge_fleet does not do this: it draws capacities and rates of its own, has no derated unit at 0 or 127 and no
+    branch probability of 0.)  The units of EDGE_UNITS, every third unit from 2 on and every eighth from 7 on are derated at 0.55 of
+    their capacity (rounded to 1/8 MW).  They take in turn, from unit 0 on: MS_PATTERNS[0] (UP always leaves for DOWN, DOWN always for
+    DERATED, DERATED for UP three times in ten and for DOWN otherwise: DERATED -> DOWN -> DERATED), three_state's probabilities (all
+    strictly inside), MS_PATTERNS[1] (UP leaves for either state, DERATED always for DOWN, DOWN always for UP) and MS_PATTERNS[2] (UP <->
+    DERATED only, DOWN out of reach).  Over the four, hl1_ms_kinds' three kinds occur for each of the three states.  The mean times are
+    seq_fleet's: mttf in UP, mttr in DOWN, mttr / 2 in DERATED (three_state sets its own from the same two).  The two-state image has
+    every unit with first_p (1, 1, 1): relmc_hl1_seq's fleet."""
+    MM = _tool("hl1_multistate_model")
+    cap, mttf, mttr, load = seq_fleet(ngen, nhours)
+    units, i = [], 0
+    for k in range(ngen):
+        if k in EDGE_UNITS or k % 3 == 2 or k % 8 == 7:
+            der = float(np.round(0.55 * cap[k] * 8.0) / 8.0)
+            if i % 4 == 1:
+                units.append(MM.three_state(cap[k], der, mttf[k], mttr[k]))
+            else:
+                units.append((float(cap[k]), der, (float(mttf[k]), 0.5 * float(mttr[k]), float(mttr[k])), MS_PATTERNS[(i % 4 + 1) // 2]))
+            i += 1
+        else:
+            units.append(MM.two_state(cap[k], mttf[k], mttr[k]))
+    return units, [MM.two_state(cap[k], mttf[k], mttr[k]) for k in range(ngen)], load
+
+
+def ms_shapes():
+    """The multi-state shapes as (label, nhours or ngen arguments of ms_fleet, seed, first_chain, n_chains, years, start): 8 units on
+    MS_NHOURS_EDGES under both start rules, and NGEN_EDGES at H = 100 as chrono_shapes() has them."""
+    out = []
+    for nhours in MS_NHOURS_EDGES:
+        for start in (0, 1):
+            out.append(("h%d-%d" % (nhours, start), (8, nhours), 13, 40, 8, seq_years(nhours), start))
+    for ngen in NGEN_EDGES:
+        for start, first in ((0, 0), (1, (1 << 32) - 4)):
+            out.append(("g%d-%d" % (ngen, start), (ngen, 100), 3, first, 8, 6, start))
+    return out
+
+
+def ms_coverage(label, nhours, kinds):
+    """The conditions on a multi-state shape, on hl1_multistate_model.path_counts: sojourns that cover no step, DERATED -> DOWN -> DERATED
+    inside one 64-step group, and sojourns across a group edge, a 256-step window edge and a year boundary.  No year length is exempt:
+    every chain runs about 1600 steps, so it has group and window edges whatever the year length, and at nhours = 1 every sojourn of two
+    steps crosses a year boundary."""
+    assert all(kinds[k] > 0 for k in ("zero", "der_down_der", "group", "window", "year")), (label, nhours, kinds)
+
+
+def area_var_max_case(nhours):
+    """The largest configuration of relmc_hl1_area_var: area_fleet8 (8 areas, 128 units), the 32 ties of topologies8()["complete"], all
+    with finite MTTF and MTTR drawn as area_tie_edges draws them, 8 resources (areas 0 and 7 among them, resource 3 at scale 0), 8
+    storages (areas 0 and 7 among them) sized to their areas, 3 weather years with load curves per area -> a dict with
+    hl1_area_variable_model.shape's keys, and `out` and `wl`."""
+    units, cap, mttf, mttr, loads = area_fleet8(nhours)
+    ties = topologies8()["complete"][:32]                           # the 28 pairs and four parallel ties with reversed endpoints
+    rng = np.random.default_rng(900 + 128)
+    kf = rng.uniform(30.0, 200.0, 32)
+    kr = rng.uniform(3.0, 30.0, 32)
+    kr[2::5] = rng.uniform(0.01, 0.3, kr[2::5].size)
+    kf[1::6] = rng.uniform(2.0, 6.0, kf[1::6].size)
+    resource_area = [0, 7, 3, 2, 4, 7, 5, 0]
+    resource_scale = [1.0, 0.5, 1.25, 0.0, 1.0, 0.75, 1.0, 2.0]
+    storage_area = [7, 0, 3, 7, 2, 4, 6, 0]
+    mean = loads.mean(axis=1)
+    frac = [(0.05, 0.06, 0.2, 0.9, 0.95, 1.0), (0.03, 0.04, 0.1, 1.0, 1.0, 0.0), (0.08, 0.05, 0.3, 0.85, 0.8, 0.5), (0.02, 0.07, 0.15, 1.0, 0.9, 1.0)]
+    storages = []
+    for i, a in enumerate(storage_area):
+        c, d, e, ec, ed, s0 = frac[i % 4]
+        storages.append((a, (c * mean[a], d * mean[a], e * mean[a], ec, ed, s0 * (e * mean[a]))))
+    n_weather = 3
+    rng = np.random.default_rng(9100 + nhours)
+    top = np.array([0.06 * (1.0 + r / 4.0) * mean[a] for r, a in enumerate(resource_area)])
+    out = np.floor(rng.uniform(0.0, 1.0, (n_weather, 8, nhours)) * top[None, :, None] * 64.0) / 64.0
+    out[1, 7, :] = 0.0
+    f = 1.0 + 0.05 * np.cos(2.0 * np.pi * (np.arange(n_weather)[:, None] / n_weather + np.arange(8)[None, :] / 8.0))
+    wl = loads[None, :, :] * f[:, :, None]
+    return dict(units=units, cap=cap, mttf=mttf, mttr=mttr, loads=loads, ties=ties, tie_mttf=kf, tie_mttr=kr, resource_area=resource_area,
+                resource_scale=resource_scale, storages=storages, n_weather=n_weather, out=out, wl=wl)
+
+
+def area_var_tie_case(ngen, nhours):
+    """area_tie_edges(ngen, nhours) with 3 resources (areas 3, 0, 3: the odd tail), 2 storages (areas 3 and 1) and 3 weather years with
+    load curves per area -> a dict as area_var_max_case's."""
+    units, cap, mttf, mttr, loads, ties, kf, kr = area_tie_edges(ngen, nhours)
+    resource_area = [3, 0, 3]
+    mean = loads.mean(axis=1)
+    rng = np.random.default_rng(9200 + nhours + ngen)
+    top = np.array([0.08 * (1.0 + r / 4.0) * mean[a] for r, a in enumerate(resource_area)])
+    out = np.floor(rng.uniform(0.0, 1.0, (3, 3, nhours)) * top[None, :, None] * 64.0) / 64.0
+    out[1, 2, :] = 0.0
+    f = 1.0 + 0.05 * np.cos(2.0 * np.pi * (np.arange(3)[:, None] / 3.0 + np.arange(4)[None, :] / 4.0))
+    wl = loads[None, :, :] * f[:, :, None]
+    storages = [(3, (0.05 * mean[3], 0.06 * mean[3], 0.2 * mean[3], 0.9, 0.95, 0.2 * mean[3])),
+                (1, (0.1 * mean[1], 0.1 * mean[1], 0.3 * mean[1], 1.0, 0.8, 0.0))]
+    return dict(units=units, cap=cap, mttf=mttf, mttr=mttr, loads=loads, ties=ties, tie_mttf=kf, tie_mttr=kr, resource_area=resource_area,
+                resource_scale=[1.0, 0.5, 1.25], storages=storages, n_weather=3, out=out, wl=wl)
 
 
 # ---- relmc_hl1_plan --------------------------------------------------------------------------------------------------------------

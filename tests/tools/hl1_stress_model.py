@@ -44,9 +44,12 @@ def cumulative_tables(fail_mult) -> np.ndarray:
     return np.array([[cumulative(m[w, c]) for c in range(m.shape[1])] for w in range(m.shape[0])]).reshape(m.shape[0], m.shape[1], m.shape[2] + 1)
 
 
-def failure_time(T: float, E: float, H: int, years: int, weather, G) -> float:
+def failure_time(T: float, E: float, H: int, years: int, weather, G, cnt=None) -> float:
     """The chain time at which a unit that became UP at T fails, given the draw E; years * H + 1 if not within the chain.  weather[years]:
-    the weather year of every chain year; G[w]: the cumulative table (a list of H + 1 Python floats) of the unit's class in weather year w."""
+    the weather year of every chain year; G[w]: the cumulative table (a list of H + 1 Python floats) of the unit's class in weather year w.
+    cnt: an optional dict that counts the paths taken: `carried` (the draw outlasts a year and goes on in the next one), `flat` (the
+    search lands on an hour without slope, d == 0: the unit fails at that hour's end) and `immediate` (the unit fails within the hour in
+    which it became UP)."""
     T, E = float(T), float(E)
     never = float(years * H + 1)
     if not T < float(years * H):
@@ -64,6 +67,8 @@ def failure_time(T: float, E: float, H: int, years: int, weather, G) -> float:
         y += 1
         if y == years:
             return never
+        if cnt is not None:
+            cnt["carried"] += 1
         g = G[weather[y]]
         j, a, rem = 0, 0.0, g[H]
     t = a + E
@@ -81,6 +86,9 @@ def failure_time(T: float, E: float, H: int, years: int, weather, G) -> float:
         num = t - g0
         f = num / d
         f = 0.0 if f < 0.0 else 1.0 if f > 1.0 else f
+    if cnt is not None:
+        cnt["flat"] += not d > 0.0
+        cnt["immediate"] += y * H + lo == n0
     r = float(y * H + lo) + f
     return r if r > T else T
 
@@ -88,7 +96,8 @@ def failure_time(T: float, E: float, H: int, years: int, weather, G) -> float:
 def stress_chronology(seed: int, chains, mttf, mttr, start: int, H: int, years: int, W, G, unit_class, counters=None):
     """Start states down0[c, k] and transition times T[c, k, :] (padded with inf behind the first time beyond the chain) of the chains
     `chains`, whose weather years are W[c, :].  G[n_weather, n_classes, H + 1].  counters: an optional dict that counts the transitions
-    (`failures` through failure_time, `never` of them beyond the chain, `plain` the others)."""
+    (`failures` through failure_time, `never` of them beyond the chain, `plain` the others, `plain_failures` those of the others that
+    are failures of a unit of class -1; `carried`, `flat` and `immediate` as failure_time counts them)."""
     mttf, mttr = [float(v) for v in mttf], [float(v) for v in mttr]
     K, nsteps = len(mttf), years * H
     chains = np.atleast_1d(np.asarray(chains, dtype=np.uint64))
@@ -100,7 +109,7 @@ def stress_chronology(seed: int, chains, mttf, mttr, start: int, H: int, years: 
         lnU = np.log(U)
         down0 = np.zeros((chains.size, K), dtype=bool)
         times, short = [], False
-        cnt = dict(failures=0, never=0, plain=0)
+        cnt = dict(failures=0, never=0, plain=0, plain_failures=0, carried=0, flat=0, immediate=0)
         for c in range(chains.size):
             wy = [int(v) for v in W[c]]
             row = []
@@ -117,12 +126,13 @@ def stress_chronology(seed: int, chains, mttf, mttr, start: int, H: int, years: 
                         break
                     e = -(mttr[k] if down else mttf[k]) * l[ev]
                     if not down and cls[k] >= 0:
-                        T = failure_time(T, e, H, years, wy, Gl[cls[k]])
+                        T = failure_time(T, e, H, years, wy, Gl[cls[k]], cnt)
                         cnt["failures"] += 1
                         cnt["never"] += T == float(nsteps + 1)
                     else:
                         T = T + e
                         cnt["plain"] += 1
+                        cnt["plain_failures"] += not down
                     ts.append(T)
                     down, ev = not down, ev + 1
                     if T > nsteps:
@@ -144,14 +154,16 @@ def stress_chronology(seed: int, chains, mttf, mttr, start: int, H: int, years: 
 
 
 def stress_model(seed: int, chains, cap, mttf, mttr, load, years: int, start: int, weather_out, fail_mult, unit_class, weather_load=None,
-                 resource_scale=None, pick: int = PICK_RANDOM, storages=(), scale: float = 1.0, shift: float = 0.0, counters=None):
+                 resource_scale=None, pick: int = PICK_RANDOM, storages=(), scale: float = 1.0, shift: float = 0.0, counters=None,
+                 step_counters=None, weather=None):
     """Chains `chains` -> (rec[nchains * years, 6], weather[nchains * years]), as hl1_variable_model.variable_model.
-    fail_mult[n_weather, n_classes, H]; unit_class[K] in -1 .. n_classes - 1."""
+    fail_mult[n_weather, n_classes, H]; unit_class[K] in -1 .. n_classes - 1.  counters: stress_chronology's; step_counters:
+    hl1_storage_model's, of the step loop; weather: as hl1_variable_model.variable_model's."""
     chains = np.atleast_1d(np.asarray(chains, dtype=np.uint64))
     out = np.asarray(weather_out, dtype=np.float64)
     nw, nres, H = out.shape
     rs = [1.0] * nres if resource_scale is None else [float(v) for v in resource_scale][:nres]
-    W = VM.weather_years(seed, chains, years, nw, pick)
+    W = VM.weather_years(seed, chains, years, nw, pick) if weather is None else np.asarray(weather, dtype=np.int64).reshape(chains.size, years)
     G = cumulative_tables(fail_mult)
     recs = []
     for c0 in range(0, chains.size, 256):
@@ -159,7 +171,7 @@ def stress_model(seed: int, chains, cap, mttf, mttr, load, years: int, start: in
         for c in range(down0.shape[0]):
             cav = SM.cap_avail(down0[c], T[c], cap, years * H)
             cs, Ls = VM.step_curves(cav, W[c0 + c], load, out, weather_load, rs, scale, shift)
-            recs.append(VM.variable_chain(cs, Ls, H, years, storages)[0])
+            recs.append(VM.variable_chain(cs, Ls, H, years, storages, step_counters)[0])
     return np.concatenate(recs), W.reshape(-1)
 
 

@@ -148,17 +148,18 @@ def variable_chain(cap, L, H: int, years: int, storages, counters=None, trace=No
 
 
 def variable_model(seed: int, chains, cap, mttf, mttr, load, years: int, start: int, weather_out, weather_load=None, resource_scale=None,
-                   pick: int = PICK_RANDOM, storages=(), scale: float = 1.0, shift: float = 0.0, counters=None):
+                   pick: int = PICK_RANDOM, storages=(), scale: float = 1.0, shift: float = 0.0, counters=None, weather=None):
     """Chains `chains` -> (rec[nchains * years, 6], weather[nchains * years]): per year lole, eue, lolf, served_hours, discharged_mwh,
     charged_mwh and the weather year, chain-major.  weather_out[n_weather, n_resources, H]; weather_load None or [n_weather, H];
     resource_scale None (every resource at 1.0) or one scale per resource.  The energies are summed over a year's steps in step order
-    (the device sums lane partials; the tests compare them to a relative tolerance).  counters: as hl1_storage_model's."""
+    (the device sums lane partials; the tests compare them to a relative tolerance).  counters: as hl1_storage_model's.  weather: None, or
+    the weather years [nchains, years] to use in place of the contract's pick (the tests' perturbed models)."""
     chains = np.atleast_1d(np.asarray(chains, dtype=np.uint64))
     out = np.asarray(weather_out, dtype=np.float64)
     nw, nres, H = out.shape
     rs = [1.0] * nres if resource_scale is None else [float(v) for v in resource_scale][:nres]
     cnt = counters if counters is not None else SM.new_counters()
-    W = weather_years(seed, chains, years, nw, pick)
+    W = weather_years(seed, chains, years, nw, pick) if weather is None else np.asarray(weather, dtype=np.int64).reshape(chains.size, years)
     recs = []
     for c0 in range(0, chains.size, 256):
         down0, T, _ = SEQ.chronology(seed, chains[c0:c0 + 256], mttf, mttr, start, years * H)

@@ -103,17 +103,46 @@ int32_t relmc_debug_trace(relmc_ctx* ctx, double* out, int32_t n_doubles)
 // (relmc_shape_rts24.h; null = skip).  Returns the number of fields, or a negative error.
 int32_t relmc_debug_shape(const relmc_case_desc* d, const int32_t* order_hint, int32_t n_hint, int32_t* case_out, int32_t* static_out)
 {
-    if (static_out) ShapeRts24::values(static_out);
+    int32_t v[SF_COUNT_ALL];          // the fill-lane fields behind SF_COUNT are relmc_debug_fill_lanes'
+    if (static_out) { ShapeRts24::values(v); std::memcpy(static_out, v, sizeof(int32_t) * SF_COUNT); }
     if (case_out) {
         if (!d) return RELMC_ERR_INVALID;
         SymOpts so = sym_opts_default();
         if (order_hint && n_hint > 0) { so.order_hint = order_hint; so.n_hint = n_hint; }
         std::string err;
         SymGeom g;
-        const int rc = with_symbolic(d, 0, so, g, err, [&](const auto& C) { shape_of(C, g.stash_off, g.scen_doubles, case_out); return (int)RELMC_OK; });
+        const int rc = with_symbolic(d, 0, so, g, err, [&](const auto& C) { shape_of(C, g.stash_off, g.scen_doubles, v); return (int)RELMC_OK; });
         if (rc) return rc < 0 ? rc : -rc;
+        std::memcpy(case_out, v, sizeof(int32_t) * SF_COUNT);
     }
     return SF_COUNT;
+}
+
+// Host-only introspection: which lane clears which fill block (relmc_dev.h: l_blk_fill, b_lane_fill), for the case / order arguments of
+// relmc_debug_symbolic.
+//   hdr[17]: RW, nb, nl, nzero, nzero_res, nfill_line, nfill_bus, line-slot lanes of the tile (NLT), bus-slot lanes (NBT), the compiled-in
+//            shape's nzero_res and nfill_bus (relmc_shape_rts24.h; relmc_debug_shape keeps to the fields in front of them), nidle_line,
+//            nidle_bus_s[0], nidle_bus_s[1], and the compiled-in shape's three
+//   l_blk_fill[NLT], b_lane_fill[NBT], b_lane[NBT] (null = skip): the tables as the device gets them
+int32_t relmc_debug_fill_lanes(const relmc_case_desc* d, int32_t order_variant, const int32_t* order_hint, int32_t n_hint, int32_t* hdr, uint16_t* l_blk_fill,
+                               uint16_t* b_lane_fill, uint8_t* b_lane)
+{
+    if (!d || !hdr) return RELMC_ERR_INVALID;
+    SymOpts so = sym_opts_default();
+    if (order_hint && n_hint > 0) { so.order_hint = order_hint; so.n_hint = n_hint; }
+    std::string err;
+    SymGeom g;
+    return with_symbolic(d, order_variant, so, g, err, [&](const auto& C) {
+        using DC = std::decay_t<decltype(C)>;
+        int32_t st[SF_COUNT_ALL];
+        ShapeRts24::values(st);
+        hdr[0] = DC::ROWL; hdr[1] = C.nb; hdr[2] = C.nl; hdr[3] = C.nzero; hdr[4] = C.nzero_res; hdr[5] = C.nfill_line; hdr[6] = C.nfill_bus; hdr[7] = DC::NLT; hdr[8] = DC::NBT;
+        hdr[9] = st[SF_NZERO_RES]; hdr[10] = st[SF_NFILL_BUS];
+        hdr[11] = C.nidle_line; hdr[12] = C.nidle_bus_s[0]; hdr[13] = C.nidle_bus_s[1]; hdr[14] = st[SF_NIDLE_LINE]; hdr[15] = st[SF_NIDLE_BUS0]; hdr[16] = st[SF_NIDLE_BUS1];
+        for (int l = 0; l < DC::NLT; ++l) if (l_blk_fill) l_blk_fill[l] = C.l_blk_fill[l];
+        for (int q = 0; q < DC::NBT; ++q) { if (b_lane_fill) b_lane_fill[q] = C.b_lane_fill[q]; if (b_lane) b_lane[q] = C.b_lane[q]; }
+        return (int)RELMC_OK;
+    });
 }
 
 // relmc_nsq_run's stretch-length rule (stretch_length, relmc_nsq_run.hip; host only) with the library's own longest stretch for this batch:

@@ -107,6 +107,17 @@ struct DevCaseT {
     uint16_t zero_off[MAXOFF];      // W offsets of fill-only blocks (cleared every iteration)
     uint8_t pass_ntask[MAXPASS];
     uint16_t task[MAXPASS][ROWL][4];    // byte offsets into the scenario's workspace (< 32 KiB); a lane without a task shadows an active one and carries the idle marker (above)
+    // Fill blocks cleared by the spare lanes of the assembly's block stores (relmc_schedule.hip: fill_lanes; read only by an instantiation with
+    // kFillBySlot, relmc_kernels.hip).  A lane of a line slot that holds no owner line, and a lane of a bus slot that holds no bus, stores exact
+    // zeros with the block stores its slot issues anyway; given the W offset of a fill block it clears that block.  zero_off's entries
+    // [nzero_res, nzero) are assigned, nfill_line of them to line-slot lanes and nfill_bus to bus-slot lanes; [0, nzero_res) found no spare lane
+    // and keep the loop.  The tables stand behind the pass schedule, outside the part every workgroup copies to LDS: every field
+    // above keeps its offset and the LDS image its size.
+    uint16_t l_blk_fill[NLT];       // l_blk with the spare lanes' fill blocks filled in; 0xffff = the lane of line slot s at [RW * s + r] stores no block
+    uint16_t b_lane_fill[NBT];      // b_lane with the spare lanes carrying the POSITION of a fill block (W offset / 4, >= nb); 0xffff = none
+    uint16_t nzero_res, nfill_line, nfill_bus;
+    uint16_t nidle_line, nidle_bus_s[2];   // lanes of the line slots / of bus slot 0, 1 that store no block at all (0: the slot's block stores need no predicate)
+    uint16_t pad4[2];
 };
 
 // per-lane partial accumulators written once per workgroup-row, reduced by relmc_finalize_kernel

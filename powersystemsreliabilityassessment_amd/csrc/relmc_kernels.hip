@@ -81,6 +81,22 @@ constexpr bool kZeroBySlot = false;
 #else
 constexpr bool kZeroBySlot = true;
 #endif
+// The fill-only blocks of the factor (C.zero_off: every trip clears them before the solver runs) cleared by the SPARE lanes of the block stores
+// the assembly issues anyway, instead of by a loop of their own: a lane of a line slot that holds no owner line stores vown = c1 = c2 = 0
+// (vown is 0 off an owner, cBv is set under LF_OWNER only and starts every group at 0), a lane of a bus slot that holds no bus stores
+// d00 = d11 = cBd = 0.  The host hands such lanes the offset of a fill block (relmc_dev.h: l_blk_fill, b_lane_fill; relmc_schedule.hip:
+// fill_lanes), so the same exact zeros reach the same words from other lanes and the loop runs over the nzero_res blocks that found no lane
+// (none on the shipped shape).  Taken only where a static shape compiles nzero_res and nfill_bus in, like kZeroBySlot: the workgroup then
+// copies l_blk_fill over its LDS image of l_blk and reads its bus lanes from b_lane_fill; the tables in global memory and every other
+// instantiation see what they saw.  A lane's bus tests stay `vb < nb`: a fill position is >= nb, and the right-hand-side pair stays under
+// that test.  A slot whose lanes all have a target (nidle_line, nidle_bus0 / 1 = 0 compiled in: every line slot and bus slot 0 on the
+// shipped shape) issues its block stores without a predicate.  Measurements and the store model behind the assignment: profiles/fill_by_slot/.
+// -DRELMC_FILL_LOOP (ablation): the loop over all of them again, the fill-lane tables unused.
+#ifdef RELMC_FILL_LOOP
+constexpr bool kFillBySlot = false;
+#else
+constexpr bool kFillBySlot = true;
+#endif
 // the one compare a pass spends on its descriptor: field 0 == field 3 (updates, back substitution), fields 2, 3 non-zero (inversion)
 #define PASS_IDLE(d) (((d).x & 0xffffu) == ((d).y >> 16))
 #define PASS_IDLE_INV(d) ((d).y != 0u)
@@ -139,6 +155,8 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
     constexpr bool NSPLIT = (((TL::RW == 16 ? kNormSplitMask : kNormSplitMaskWide) >> MODE) & 1) != 0;   // second-stage norms only on trips that can end (above)
     constexpr bool LSHARE = (((TL::RW == 16 ? kLineRcpShareMask : kLineRcpShareMaskWide) >> MODE) & 1) != 0 && PAIRSITE(0) && PAIRSITE(2) && PAIRSITE(6);   // one pair reciprocal of the line slacks per trip (relmc_devfn.h)
     constexpr bool ZSLOT = kZeroBySlot && (SH::kMask & SH::grp_nl) != 0 && (SH::kMask & SH::grp_ninj) != 0;   // zero records by the slot lanes behind the last line / injection (above)
+    constexpr bool FSLOT = kFillBySlot && !DENSE && (SH::kMask & SH::grp_nzero_res) != 0 && (SH::kMask & SH::grp_nfill_bus) != 0;   // fill blocks cleared by the spare lanes of the block stores (above)
+    constexpr bool FBUS = FSLOT && SH::nfill_bus > 0;            // ... the bus slots' spare lanes among them
     constexpr int RW = TL::RW, BS = TL::BS, LS = TL::LS, IS = TL::IS, NBT = TL::NBT, WPB = TL::WPB, SPW = TL::SPW, OW = TL::OW;
     using DevCase = DevCaseT<TL>;
     using Partial = PartialT<TL>;
@@ -164,6 +182,12 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
         uint32_t* dst = reinterpret_cast<uint32_t*>(smem + OPT_BYTES);
         if (tid == 0) { OPT[0] = a.feastol; OPT[1] = a.gradtol; OPT[2] = a.comptol; OPT[3] = a.costtol; OPT[4] = a.xi; OPT[5] = a.sigma;
                         OPT[6] = a.z0; OPT[7] = a.alpha_min; OPT[8] = a.max_stepsize; OPT[9] = a.fail_threshold; }
+        if constexpr (FSLOT) {
+            // FSLOT: the LDS image of l_blk is l_blk_fill (from behind the pass schedule, which is not copied)
+            constexpr uint32_t LB0 = offsetof(DevCase, l_blk) / 4, LBN = sizeof(DevCase::l_blk) / 4, LF0 = offsetof(DevCase, l_blk_fill) / 4;
+            static_assert(offsetof(DevCase, l_blk) % 4 == 0 && sizeof(DevCase::l_blk) % 4 == 0 && offsetof(DevCase, l_blk_fill) % 4 == 0, "l_blk and l_blk_fill are copied as 32-bit words");
+            for (uint32_t i = tid; i < case_bytes / 4; i += 64 * WPB) dst[i] = src[i - LB0 < LBN ? LF0 + (i - LB0) : i];
+        } else
         for (uint32_t i = tid; i < case_bytes / 4; i += 64 * WPB) dst[i] = src[i];
     }
     __syncthreads();
@@ -217,7 +241,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
     for (int s = 0; s < IS; ++s) iinfo[s] = C.i_info[RW * s + rlane];
     int vb[BS];                                   // the bus of this lane in bus slot t (>= nb: none)
 #pragma unroll
-    for (int t = 0; t < BS; ++t) vb[t] = C.b_lane[RW * t + rlane];
+    for (int t = 0; t < BS; ++t) vb[t] = FBUS ? (int)gcase->b_lane_fill[RW * t + rlane] : (int)C.b_lane[RW * t + rlane];   // FBUS: a spare lane holds the position of the fill block it clears (>= nb), 0xffff = none
 
     // ---- accumulators (nsqMain.m:282-301 in per-sample form) ---------------------------
     // They live in this lane's Partial record in HBM (L2-resident, 104 B per lane) and are updated by a
@@ -882,7 +906,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 if constexpr (PFSITE(1)) {
 #pragma unroll
                     for (int s = 0; s < LS; ++s) lblk_pf[s] = C.l_blk[RW * s + rlane];
-                    zo_pf = C.zero_off[rlane];
+                    if constexpr (!FSLOT) zo_pf = C.zero_off[rlane];
                 }
                 unsigned long long pl_pf[BS], pj_pf[BS];
                 if constexpr (PFSITE(2)) {
@@ -988,25 +1012,36 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 } else {
 #pragma unroll
                 for (int s = 0; s < LS; ++s) {
-                    if ((linfo[s] >> 24) & LF_OWNER) {
+                    // FSLOT: every lane with a target stores -- an owner line's lane its block, a spare lane exact zeros into a fill block
+                    const uint32_t lbf = FSLOT ? (PFSITE(1) ? lblk_pf[s] : (uint32_t)C.l_blk[RW * s + rlane]) : 0u;
+                    if (FSLOT ? (SHAPE(nidle_line, 1) == 0 || lbf != 0xffffu) : ((linfo[s] >> 24) & LF_OWNER) != 0) {      // (no line-slot lane without a target: no predicate)
                         // block (hi, lo): rows of the later-eliminated bus, columns of the earlier one
                         const double c1 = L_C1Z(s) ? 0.0 : cBv[s];   // K[th_hi][lam_lo] = B(row lam_lo, col th_hi)
                         const double c2 = L_C2Z(s) ? 0.0 : cBv[s];   // K[lam_hi][th_lo] = B(row lam_hi, col th_lo)
-                        double* blk = W + (PFSITE(1) ? lblk_pf[s] : (uint32_t)C.l_blk[RW * s + rlane]);
+                        double* blk = W + (FSLOT ? lbf : (PFSITE(1) ? lblk_pf[s] : (uint32_t)C.l_blk[RW * s + rlane]));
                         st2(blk, vown[s], c1); st2(blk + 2, c2, 0.0);
                     }
                 }
-                if constexpr (PFSITE(1)) {
+                // FSLOT: the loop is left with the blocks that found no spare lane, the first entries of zero_off (relmc_dev.h)
+                const int nzloop = FSLOT ? SHAPE(nzero_res, 0) : nzero;
+                if constexpr (PFSITE(1) && !FSLOT) {
                     for (int z = rlane; z < nzero; z += RW) {
                         const uint32_t zn = C.zero_off[z + RW < TL::MAXOFF ? z + RW : z];      // the next offset is on its way while this block is cleared
                         double* blk = W + zo_pf; st2(blk, 0.0, 0.0); st2(blk + 2, 0.0, 0.0);
                         zo_pf = zn;
                     }
                 } else
-                for (int z = rlane; z < nzero; z += RW) { double* blk = W + C.zero_off[z]; st2(blk, 0.0, 0.0); st2(blk + 2, 0.0, 0.0); }
+                for (int z = rlane; z < nzloop; z += RW) { double* blk = W + C.zero_off[z]; st2(blk, 0.0, 0.0); st2(blk + 2, 0.0, 0.0); }
 #pragma unroll
                 for (int t = 0; t < BS; ++t) {
                     const int bi = vb[t];
+                    if constexpr (FBUS) {
+                        // a spare lane with a fill position stores d00 = d11 = cBd = 0 into that block; the rhs pair is the buses' alone
+                        if ((t == 0 ? SHAPE(nidle_bus0, 1) : SHAPE(nidle_bus1, 1)) == 0 || bi != 0xffff) {
+                            st2(W + 4 * bi, d00[t], cBd[t]); st2(W + 4 * bi + 2, cBd[t], d11[t]);
+                            if (bi < nb) st2(W + off_rhs + 2 * bi, r0[t], r1[t]);
+                        }
+                    } else
                     if (bi < nb) {
                         st2(W + 4 * bi, d00[t], cBd[t]); st2(W + 4 * bi + 2, cBd[t], d11[t]);
                         st2(W + off_rhs + 2 * bi, r0[t], r1[t]);

@@ -680,6 +680,74 @@ struct Symbolic {
         }
     }
 
+    // ---- the fill-only blocks handed to the spare lanes of the assembly's block stores (relmc_dev.h: l_blk_fill, b_lane_fill).  Spare are the
+    // lanes of the line slots without an owner line (slots behind nl, partner lines) and the lanes of the bus slots without a bus.  With more
+    // fill blocks than spare lanes the first entries of zero_off, [0, nzero_res), keep the clearing loop.  l_blk, b_lane, zero_off and nzero stay.
+    // Which lane takes which block is chosen by the modelled cost of the stores: a slot's lanes issue two 16-byte stores each (the block's
+    // two halves), served in groups of 8 contiguous lanes with bank = (byte address / 4) mod 32 (MI355X_MICROARCH.md), so every different
+    // 16-byte unit on one of a group's eight 4-bank sets is one LDS-array cycle, and a store costs the array cycles of all its groups or the
+    // 13 cycles its operands take to reach the LDS, whichever is more.  The scenario rows of a wavefront add the same cycles each (their
+    // workspaces differ by a common shift).  First fit, then exchanges of two lanes' targets while the modelled sum falls; the order tuner
+    // (place_moves = 0: its cost does not read these tables) stops at first fit.
+    long fill_slot_cost(const uint16_t* off) const      // off[ROWL]: W offset in doubles of the block a slot's lane stores, 0xffff = none
+    {
+        long cyc = 0;
+        for (int g = 0; g < ROWL / 8; ++g) {
+            int n[8] = {}, mx = 0; uint16_t seen[8][8];
+            for (int r = 8 * g; r < 8 * g + 8; ++r) {
+                if (off[r] == 0xffff) continue;
+                const int set = (off[r] / 2) & 7;
+                bool dup = false; for (int k = 0; k < n[set]; ++k) dup = dup || seen[set][k] == off[r];
+                if (!dup) seen[set][n[set]++] = off[r];
+                if (n[set] > mx) mx = n[set];
+            }
+            cyc += mx;
+        }
+        cyc *= SPW;
+        return 2 * (cyc > 13 ? cyc : 13);
+    }
+    int fill_lanes()
+    {
+        for (int l = 0; l < NLT; ++l) C.l_blk_fill[l] = ((C.l_info[l] >> 24) & LF_OWNER) ? C.l_blk[l] : (uint16_t)0xffff;
+        std::vector<uint16_t> boff(NBT);                 // the bus slots' targets as W offsets: 4 * position
+        for (int q = 0; q < NBT; ++q) boff[q] = C.b_lane[q] == 0xff ? (uint16_t)0xffff : (uint16_t)(4 * C.b_lane[q]);
+        std::vector<uint16_t*> spare;
+        for (int l = 0; l < NLT; ++l) if (C.l_blk_fill[l] == 0xffff) spare.push_back(&C.l_blk_fill[l]);
+        const int nspare_line = (int)spare.size();
+        for (int q = 0; q < NBT; ++q) if (boff[q] == 0xffff) spare.push_back(&boff[q]);
+        const int nres = C.nzero > spare.size() ? C.nzero - (int)spare.size() : 0;
+        // a bus-slot lane tells a bus from a fill block by the position: diagonal blocks come first in W (relmc_dev.h)
+        for (int z = nres; z < C.nzero; ++z) if (C.zero_off[z] < 4 * nb || C.zero_off[z] % 4) return failx(RELMC_ERR_INVALID, "relmc_case_load: fill block among the diagonal blocks");
+        auto slot_of = [&](const uint16_t* t) { return t >= boff.data() && t < boff.data() + NBT ? boff.data() + (t - boff.data()) / ROWL * ROWL : C.l_blk_fill + (t - C.l_blk_fill) / ROWL * ROWL; };
+        for (int z = nres, k = 0; z < C.nzero; ++z, ++k) *spare[k] = C.zero_off[z];
+        for (int sweep = 0; sweep < 8 && so.place_moves > 0; ++sweep) {
+            bool better = false;
+            for (size_t i = 0; i < spare.size(); ++i) for (size_t j = i + 1; j < spare.size(); ++j) {
+                if (*spare[i] == *spare[j]) continue;
+                const uint16_t* si = slot_of(spare[i]); const uint16_t* sj = slot_of(spare[j]);
+                const long before = fill_slot_cost(si) + (sj != si ? fill_slot_cost(sj) : 0);
+                std::swap(*spare[i], *spare[j]);
+                const long after = fill_slot_cost(si) + (sj != si ? fill_slot_cost(sj) : 0);
+                if (after < before) better = true; else std::swap(*spare[i], *spare[j]);
+            }
+            if (!better) break;
+        }
+        int nline = 0, nbus = 0;
+        for (int k = 0; k < (int)spare.size(); ++k) if (*spare[k] != 0xffff) { if (k < nspare_line) nline++; else nbus++; }
+        for (int q = 0; q < NBT; ++q) C.b_lane_fill[q] = boff[q] == 0xffff ? (uint16_t)0xffff : (uint16_t)(boff[q] / 4);
+        C.nfill_line = (uint16_t)nline; C.nfill_bus = (uint16_t)nbus; C.nzero_res = (uint16_t)nres;
+        C.nidle_line = 0; C.nidle_bus_s[0] = C.nidle_bus_s[1] = 0;
+        for (int l = 0; l < NLT; ++l) if (C.l_blk_fill[l] == 0xffff) C.nidle_line++;
+        for (int q = 0; q < NBT; ++q) if (C.b_lane_fill[q] == 0xffff) C.nidle_bus_s[q / ROWL]++;
+        if (verbose()) {
+            long cyc = 0;
+            for (int t = 0; t < NLT / ROWL; ++t) cyc += fill_slot_cost(C.l_blk_fill + ROWL * t);
+            for (int t = 0; t < NBT / ROWL; ++t) cyc += fill_slot_cost(boff.data() + ROWL * t);
+            fprintf(stderr, "relmc: order %d: %d fill blocks: %d cleared by line-slot lanes, %d by bus-slot lanes, %d by the loop; modelled LDS cycles of the block stores %ld\n", order_variant, (int)C.nzero, nline, nbus, nres, cyc);
+        }
+        return RELMC_OK;
+    }
+
     void base_connectivity()       // is the intact network connected?  (lets the kernel skip the island search when no line is out)
     {
         std::vector<int> lab(nb); for (int i = 0; i < nb; ++i) lab[i] = i;
@@ -736,6 +804,7 @@ int case_symbolic(const relmc_case_desc* d, DevCaseT<TL>& C, int order_variant, 
     s.byte_offsets();
     if (const int rc = run({&S::shadow_idle_lanes, &S::pass_counts, &S::lines, &S::injections})) return rc;
     s.bus_lanes();
+    if (const int rc = s.fill_lanes()) return rc;
     s.base_connectivity();
     s.thresholds();
     return s.geometry();

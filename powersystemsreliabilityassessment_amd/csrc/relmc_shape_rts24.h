@@ -26,6 +26,11 @@ struct ShapeRts24Values {
     static constexpr int bwd_all_half = 0;
     static constexpr int stash_off = 360;
     static constexpr int scen_doubles = 526;
+    static constexpr int nzero_res = 0;
+    static constexpr int nfill_bus = 6;
+    static constexpr int nidle_line = 0;
+    static constexpr int nidle_bus0 = 0;
+    static constexpr int nidle_bus1 = 2;
 };
 #ifndef RELMC_SHAPE_MASK
 // The field groups compiled into the specialised kernel (ablation builds: -DRELMC_SHAPE_MASK=<ShapeGroup bits>).  The gather lengths stay

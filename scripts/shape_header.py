@@ -1,14 +1,19 @@
 """Prints csrc/relmc_shape_rts24.h's ShapeRts24Values from what relmc_case_load computes for case24.rts24() (host only, no GPU):
     python scripts/shape_header.py          # compare with / paste into the struct of the checked-in header
-tests/test_shape_paths.py::test_header_is_the_shape_of_the_shipped_case fails when the header and these numbers disagree."""
+tests/test_shape_paths.py::test_header_is_the_shape_of_the_shipped_case fails when the header and these numbers disagree; the fill-lane
+fields behind them (relmc_debug_fill_lanes) are pinned by tests/test_fill_lanes.py."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 from powersystemsreliabilityassessment_amd import case24
 from test_shape_paths import FIELDS, shapes
+from test_fill_lanes import fill_lanes
 
 got, static = shapes(case24.rts24())
+fill = fill_lanes(case24.rts24())[0]
 print("struct ShapeRts24Values {")
 for k in FIELDS:
     print(f"    static constexpr int {k} = {got[k]};" + ("" if got[k] == static[k] else f"      // compiled in: {static[k]}"))
+for k in ("nzero_res", "nfill_bus", "nidle_line", "nidle_bus0", "nidle_bus1"):
+    print(f"    static constexpr int {k} = {fill[k]};" + ("" if fill[k] == fill["static_" + k] else f"      // compiled in: {fill['static_' + k]}"))
 print("};")

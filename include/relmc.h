@@ -427,6 +427,52 @@ int32_t relmc_hl1_seq_sweep(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain,
                             const uint32_t* withheld, relmc_hl1_seq_acc* acc,
                             relmc_hl1_seq_year* years_host);
 
+/* ---- planned maintenance on the HL1 sequential chronology: up to 8 schedules against one fleet history (an extension beyond the reference) ---- */
+/* What a maintenance plan costs in LOLE, EUE and LOLF, and whether plan B is better than plan A: up to 8 schedules are compared in ONE walk
+ * of every chain, so their differences are paired under one seed.
+ * Chronology  relmc_hl1_seq's, word for word (model of relmc_hl1_seq_load, draws (seed, chain, k | 0x40000000, event), both start rules,
+ *             no FMA, DOWN on steps [ceil(T_odd), ceil(T_even))): under one seed, chain c of every schedule sees exactly the fleet history
+ *             of chain c of relmc_hl1_seq.
+ * Overlay     A unit's failure and repair process runs on regardless of maintenance; a unit on maintenance in an hour adds 0.0 to that
+ *             hour's capacity (generating_adequancy_comparative.jl skips a unit in maintenance and samples the others by their FOR).
+ *             Clocks that pause during maintenance are not modelled.
+ * Windows     A schedule is a set of windows (unit, start_hour, hours) in hours of the year, 0-based, 0 <= start_hour < H,
+ *             1 <= hours <= H, periodic in the year: unit k is on maintenance at hour-of-year h iff some window of k has
+ *             (h - start_hour) mod H < hours.  A window that runs past the year's end therefore also covers the first hours of every year,
+ *             chain year 0 included.  Windows of one unit may overlap (the union counts); a unit may have any number of windows, a
+ *             schedule may have none.
+ * Load        L(h) = scale * load[h] + shift, the product and the sum each rounded (relmc_hl1_seq_sweep's rule); one curve for the call,
+ *             shared by all schedules.
+ * Per step and schedule j: cap_j = sum over the units in ascending order of (UP and not on maintenance under j) ? cap_k : 0.0; loss iff
+ *   cap_j < L(h) (strict), deficit L(h) - cap_j; per year and schedule: loss hours, EUE and loss events by relmc_hl1_seq's rules (step 1
+ *   counts, an event across a year boundary counts once, in the year it starts; every schedule has its own previous-step flag).  A year's
+ *   EUE is summed in relmc_hl1_seq's order (lane partials, then the fixed butterfly).
+ * So (1) a schedule without windows gives, bit for bit, relmc_hl1_seq_sweep's level (scale, shift, fleet 0), and at (1.0, 0.0)
+ *   relmc_hl1_seq's year records; (2) a schedule that keeps the units W on maintenance the whole year (start_hour 0, hours H) gives, bit
+ *   for bit, the sweep's level (scale, shift, fleet 1) with withheld = W; (3) a schedule's year records depend on (seed, chain, start,
+ *   years_per_chain, data, scale, shift, that schedule) only: not on the other schedules, their order, their number, or how a chain
+ *   range is split into calls, and acc[j] is summed in a fixed order, so a repeated call is bitwise identical; (4) if schedule A's
+ *   maintenance set contains schedule B's in every hour, every year's loss hours and EUE under A are >= those under B, exactly. */
+#define RELMC_HL1_MAINT_MAX_SCHEDULES 8
+typedef struct { int32_t schedule, unit, start_hour, hours; } relmc_hl1_maint_window;   /* 16 bytes */
+/* The schedules of the next relmc_hl1_maint_seq calls, for the model relmc_hl1_seq_load has loaded (RELMC_ERR_NO_CASE before that call):
+ * windows[i].schedule in 0 .. n_schedules - 1, unit in 0 .. ngen - 1, start_hour and hours as above.  The library keeps a per-schedule,
+ * per-hour mask table on the device (four uint32 words per hour, bit k & 31 of word k >> 5 = unit k on maintenance: 16 bytes x nhours x
+ * n_schedules) and the ngen and nhours it was built for.  RELMC_ERR_INVALID, with relmc_last_error naming the window and the field, for:
+ * a null ctx; n_schedules outside 1 .. RELMC_HL1_MAINT_MAX_SCHEDULES; n_windows < 0; n_windows > 0 with windows == NULL; a window with
+ * schedule, unit, start_hour or hours out of range.  A refused call changes nothing: the previous table still answers. */
+int32_t relmc_hl1_maint_load(relmc_ctx* ctx, int32_t n_schedules, int64_t n_windows, const relmc_hl1_maint_window* windows);
+/* chains [first_chain, first_chain + n_chains), each years_per_chain consecutive years, under every schedule of relmc_hl1_maint_load.
+ * RELMC_ERR_NO_CASE before relmc_hl1_seq_load or relmc_hl1_maint_load.  RELMC_ERR_INVALID for: a null ctx or acc; a model of
+ * relmc_hl1_seq_load whose ngen or nhours are not those the table was built for (load the schedules again after loading another model);
+ * a non-finite scale or shift; anything relmc_hl1_seq refuses.  n_chains == 0 zeroes the outputs.
+ *   acc         [n_schedules]
+ *   years_host  optional [n_schedules][n_chains * years_per_chain], schedule-major, then chain-major
+ * Long chain ranges go in launches of at most ~4M year records counted over all schedules; relmc_last_kernel_ms covers every launch. */
+int32_t relmc_hl1_maint_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain,
+                            int32_t start, double scale, double shift, relmc_hl1_seq_acc* acc,
+                            relmc_hl1_seq_year* years_host);
+
 /* ---- energy storage on the HL1 sequential chronology: state of charge carried from hour to hour (an extension beyond the reference) ---- */
 /* What a battery does to LOLE, EUE and LOLF exists only on a chronology: its state of charge couples the hours.  Up to 8 storages, given
  * in the call (as the sweep's levels are: no load call, no model state in the context), discharge into a shortfall of the fleet of

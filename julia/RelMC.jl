@@ -559,6 +559,54 @@ const LAYOUT_HL1_SWEEP = [
     ("relmc_hl1_sweep_level", 24, [("scale", 0), ("shift", 8), ("fleet", 16), ("reserved", 20)]),
 ]
 
+"relmc_hl1_maint_window (include/relmc.h, 16 bytes): unit `unit` (0-based) of schedule `schedule` is on maintenance in hours start_hour .. start_hour + hours - 1 of the year, modulo the year"
+struct Hl1MaintWindow
+    schedule::Int32; unit::Int32; start_hour::Int32; hours::Int32
+end
+const HL1_MAINT_MAX_SCHEDULES = 8                                          # RELMC_HL1_MAINT_MAX_SCHEDULES
+
+"""
+run_maintenance_schedules (an extension beyond the reference): run_sequential_mc's chronology, same arguments and same chains under one
+seed, under up to 8 planned-maintenance schedules in one walk of the chains, at the load scale * hourly_load + shift.  `schedules` holds
+one vector of (unit, start_hour, hours) triples per schedule: unit (1-based) is on maintenance in hours start_hour .. start_hour + hours - 1
+of every year (0-based, modulo the year) and adds nothing to those hours' capacity; its failures and repairs run on.  Every schedule sees
+the same fleet history, so two schedules may be differenced year by year.  Returns per schedule LOLE, EUE, LOLF and the per-year indices
+(n_schedules x years).
+"""
+function run_maintenance_schedules(eng::Engine, capacity::Vector{Float64}, mttf::Vector{Float64}, mttr::Vector{Float64},
+                                   hourly_load::Vector{Float64}, years::Integer, schedules::Vector{<:Vector{<:Tuple{Integer,Integer,Integer}}};
+                                   seed::Integer=1, chains::Integer=1, start::Symbol=:all_up, scale::Real=1.0, shift::Real=0.0)
+    (years >= 1 && chains >= 1 && years % chains == 0) || throw(ArgumentError("years must be a positive multiple of chains"))
+    n = length(schedules)
+    1 <= n <= HL1_MAINT_MAX_SCHEDULES || throw(ArgumentError("between 1 and $HL1_MAINT_MAX_SCHEDULES schedules"))
+    H = length(hourly_load)
+    for s in schedules, w in s
+        (1 <= w[1] <= length(capacity) && 0 <= w[2] < H && 1 <= w[3] <= H) || throw(ArgumentError("window $w: unit, start_hour or hours out of range"))
+    end
+    check(ccall((:relmc_hl1_seq_load, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}),
+                eng.h, length(capacity), capacity, mttf, mttr, H, hourly_load), eng.h, "relmc_hl1_seq_load")
+    win = [Hl1MaintWindow(Int32(j - 1), Int32(w[1] - 1), Int32(w[2]), Int32(w[3])) for j in 1:n for w in schedules[j]]
+    check(ccall((:relmc_hl1_maint_load, LIB), Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Hl1MaintWindow}),
+                eng.h, n, length(win), isempty(win) ? C_NULL : win), eng.h, "relmc_hl1_maint_load")
+    yrs = Vector{Hl1SeqYear}(undef, n * years)
+    raw = zeros(UInt8, 56 * n)                                              # relmc_hl1_seq_acc[n], contiguous
+    check(ccall((:relmc_hl1_maint_seq, LIB), Int32,
+                (Ptr{Cvoid}, UInt64, UInt64, Int64, Int32, Int32, Cdouble, Cdouble, Ptr{UInt8}, Ptr{Hl1SeqYear}),
+                eng.h, seed, 0, chains, years ÷ chains, HL1_START[start], Float64(scale), Float64(shift), raw, yrs),
+          eng.h, "relmc_hl1_maint_seq")
+    sums = reshape(reinterpret(Float64, raw), 7, n)                         # rows 2 .. 4: sum_lole, sum_eue, sum_lolf (row 1 is the Int64 years)
+    Y = reshape(yrs, years, n)
+    return (lole_hours_yr=[sums[2, j] / years for j in 1:n], eue_mwh_yr=[sums[3, j] / years for j in 1:n],
+            lolf_occ_yr=[sums[4, j] / years for j in 1:n],
+            year_lole=[Y[y, j].lole for j in 1:n, y in 1:years], year_eue=[Y[y, j].eue for j in 1:n, y in 1:years],
+            year_lolf=[Y[y, j].lolf for j in 1:n, y in 1:years])
+end
+
+# Layout of the maintenance window, kept apart from LAYOUT (tests/test_hl1_maint_host.py compares it with the C compiler's and with ctypes)
+const LAYOUT_HL1_MAINT = [
+    ("relmc_hl1_maint_window", 16, [("schedule", 0), ("unit", 4), ("start_hour", 8), ("hours", 12)]),
+]
+
 "relmc_hl1_storage (include/relmc.h, 48 bytes): one energy storage of relmc_hl1_seq_storage; powers in MW, energies in MWh, efficiencies in (0, 1]"
 struct Hl1Storage
     charge_mw::Cdouble; discharge_mw::Cdouble; energy_mwh::Cdouble; eta_charge::Cdouble; eta_discharge::Cdouble; soc0_mwh::Cdouble

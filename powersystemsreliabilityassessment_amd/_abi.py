@@ -137,6 +137,13 @@ class Hl1SweepLevel(C.Structure):         # relmc_hl1_sweep_level (24 bytes)
 
 
 HL1_SWEEP_MAX_LEVELS = 16                 # RELMC_HL1_SWEEP_MAX_LEVELS
+
+
+class Hl1MaintWindow(C.Structure):        # relmc_hl1_maint_window (16 bytes)
+    _fields_ = [("schedule", C.c_int32), ("unit", C.c_int32), ("start_hour", C.c_int32), ("hours", C.c_int32)]
+
+
+HL1_MAINT_MAX_SCHEDULES = 8               # RELMC_HL1_MAINT_MAX_SCHEDULES
 HL1_MAX_STORAGE = 8                       # RELMC_HL1_MAX_STORAGE
 
 

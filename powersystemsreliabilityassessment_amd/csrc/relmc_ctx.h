@@ -14,7 +14,7 @@
 //                        sequential chronology (relmc_hl1_seq), its loss events (relmc_hl1_seq_events) and its load sweep
 //                        (relmc_hl1_seq_sweep), three instantiations of the one kernel template of relmc_hl1_chain_kernels.h, and
 //                        the record reduction and unit check of every HL1 chronology track
-//   relmc_hl1_host.h     (a header, included by the nine HL1 units around it) what their host code shares: the chunk rule, the loop over a
+//   relmc_hl1_host.h     (a header, included by the ten HL1 units around it) what their host code shares: the chunk rule, the loop over a
 //                        model's launches with the reduction of their year records (hl1_run_records), the argument and unit checks, and the one
 //                        copy of what the storage and weather-year tracks check and fill alike (storage fields, resource scales, pick,
 //                        weather_host, the two-row copies, relmc_hl1_storage_acc)
@@ -25,6 +25,8 @@
 //                        kernel in relmc_hl1_storage_kernels.h)
 //   relmc_stress.hip     weather-dependent forced outage rates on that chronology, with those resources and storages (relmc_hl1_stress_load,
 //                        relmc_hl1_stress_seq, kernel in relmc_hl1_storage_kernels.h)
+//   relmc_maint.hip      planned maintenance on that chronology, up to 8 schedules on one fleet history (relmc_hl1_maint_load,
+//                        relmc_hl1_maint_seq, kernel in relmc_hl1_maint_kernels.h)
 //   relmc_multistate.hip that chronology with three-state units (relmc_hl1_ms_load, relmc_hl1_ms_seq, kernel in relmc_multistate_kernels.h)
 //   relmc_plan.hip       the HL1 planning model's Monte Carlo (relmc_hl1_plan)
 //   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area)
@@ -208,6 +210,11 @@ struct relmc_ctx {
     } hl1_events;
     // load sweep on that model (relmc_hl1_seq_sweep): per-level records; storage on that model (relmc_hl1_seq_storage): records of both rows
     Hl1Records hl1_sweep, hl1_storage;
+    // maintenance schedules of relmc_hl1_maint_load (relmc_hl1_maint_seq runs the fleet of hl1_seq under them): the mask table
+    // tab[width][nhours][4] (bit k & 31 of word k >> 5 = unit k on maintenance; width = n_schedules rounded up to the kernel's 1, 2, 4 or 8,
+    // the added schedules empty), the ngen and nhours it was built for, per-schedule records
+    bool has_hl1_maint = false;
+    struct Hl1Maint { int n_schedules = 0, ngen = 0, nhours = 0; DevBuf<uint32_t> tab; Hl1Records rec; } hl1_maint;
     // weather library of relmc_hl1_var_load (relmc_hl1_var_seq runs the fleet of hl1_seq against it): out[n_weather][n_res][nhours], the
     // optional load curves load[n_weather][nhours], records of both rows.  A slot of its own, apart from every other HL1 model
     bool has_hl1_var = false;

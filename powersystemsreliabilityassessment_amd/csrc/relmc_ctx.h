@@ -26,7 +26,7 @@
 //   relmc_stress.hip     weather-dependent forced outage rates on that chronology, with those resources and storages (relmc_hl1_stress_load,
 //                        relmc_hl1_stress_seq, kernel in relmc_hl1_storage_kernels.h)
 //   relmc_maint.hip      planned maintenance on that chronology, up to 8 schedules on one fleet history (relmc_hl1_maint_load,
-//                        relmc_hl1_maint_seq, kernel in relmc_hl1_maint_kernels.h)
+//                        relmc_hl1_maint_seq; the kernel is the fourth model of relmc_hl1_chain_kernels.h's template)
 //   relmc_multistate.hip that chronology with three-state units (relmc_hl1_ms_load, relmc_hl1_ms_seq, kernel in relmc_multistate_kernels.h)
 //   relmc_plan.hip       the HL1 planning model's Monte Carlo (relmc_hl1_plan)
 //   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area)

@@ -1,12 +1,18 @@
 // relmc_hl1_chain_kernels.h — the HL1 sequential chronology of one area (PowerSystemAdequacy.jl:214-268; contracts in include/relmc.h) in
-// its three models, as one kernel template:
-//   sequential  relmc_hl1_seq: loss hours, EUE and loss events of every chain year
-//   events      relmc_hl1_seq_events: a loss event is a maximal run of consecutive loss steps of a chain; every event's start step,
-//               duration, energy and peak, the per-chain summary records and the duration histogram (and the kernels that scan the
-//               counts and reduce the records in a fixed order)
-//   sweep       relmc_hl1_seq_sweep: one walk of a chain's fleet history compared with up to RELMC_HL1_SWEEP_MAX_LEVELS load levels
-//               L_j(h) = scale_j * load[h] + shift_j, each against the whole fleet or the fleet without the withheld units
-// The events and the sweep are extensions beyond the reference (PowerSystemAdequacy.jl has one load curve and no event list).
+// its four models, as one kernel template:
+//   sequential   relmc_hl1_seq: loss hours, EUE and loss events of every chain year
+//   events       relmc_hl1_seq_events: a loss event is a maximal run of consecutive loss steps of a chain; every event's start step,
+//                duration, energy and peak, the per-chain summary records and the duration histogram (the kernels that scan the
+//                counts and reduce the records in a fixed order are relmc_seq_kernels.h's)
+//   sweep        relmc_hl1_seq_sweep: one walk of a chain's fleet history compared with up to RELMC_HL1_SWEEP_MAX_LEVELS load levels
+//                L_j(h) = scale_j * load[h] + shift_j, each against the whole fleet or the fleet without the withheld units
+//   maintenance  relmc_hl1_maint_seq: one walk compared with up to RELMC_HL1_MAINT_MAX_SCHEDULES maintenance schedules.  A unit on
+//                maintenance under schedule j in an hour adds 0.0 to that hour's capacity of schedule j; its failure and repair
+//                process runs on
+// The events, the sweep and the maintenance are extensions beyond the reference (PowerSystemAdequacy.jl has one load curve and no event
+// list; generating_adequancy_comparative.jl has the overlay rule, on independently drawn hours).
+// Only the template and inline functions are defined here, and nothing is instantiated: a unit that includes this header holds the
+// instantiations it launches and no other kernel (relmc_seq.hip the first three models', relmc_maint.hip the fourth's).
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -27,12 +33,6 @@ DEVFI void hl1_seq_close_year(double& l, double& e, double& f, double* __restric
 }
 
 // ---- event model ----------------------------------------------------------------------------------------------------------------------
-DEVFI void hl1_event_rec_zero(Hl1EventRec& r)
-{
-    r.events = r.sum_dur = r.sum_dur2 = r.max_dur = r.censored = 0;
-    r.sum_energy = r.sum_energy2 = r.max_energy = r.max_peak = 0.0;
-}
-
 // Lane `src`'s value (src wave-uniform) / a value that is the same in every lane, moved into scalar registers: the carry and the chain's
 // record are wave-uniform, and held this way they cost no vector register (the event model keeps the sequential model's occupancy)
 DEVFI double hl1_event_lane(double x, int src)
@@ -49,16 +49,7 @@ DEVFI double hl1_event_uniform(double x)
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
 }
 
-// a += b (sums first + second: the order is part of the results)
-DEVFI void hl1_event_rec_add(Hl1EventRec& a, const Hl1EventRec& b)
-{
-    a.events += b.events; a.sum_dur += b.sum_dur; a.sum_dur2 += b.sum_dur2; a.censored += b.censored;
-    a.max_dur = a.max_dur > b.max_dur ? a.max_dur : b.max_dur;
-    a.sum_energy += b.sum_energy; a.sum_energy2 += b.sum_energy2;
-    a.max_energy = fmax(a.max_energy, b.max_energy); a.max_peak = fmax(a.max_peak, b.max_peak);
-}
-
-// ---- sweep model ----------------------------------------------------------------------------------------------------------------------
+// ---- sweep and maintenance models: one record row per level / per schedule -----------------------------------------------------------
 // The levels and the withheld-unit mask, passed BY VALUE as a kernel argument: every read of a level is a scalar load from the kernel
 // argument segment, and the per-level branches are wave-uniform
 struct Hl1SweepArgs {
@@ -70,23 +61,24 @@ struct Hl1SweepArgs {
 // The host fills lv[n_levels ..] with levels that never lose (scale 0, shift -inf: L = -inf, and no capacity is below it), so the passes
 // over the levels need no test against n_levels; only the year records are written for j < n_levels alone.
 
-// f(integral_constant<int, j>) for j = 0 .. NL - 1, written out at compile time: a level's registers are named by a constant.  (A
-// `#pragma unroll` loop with the run-time exit at n_levels was left a loop at NL = 16, and the partials were then indexed at run time.)
+// A row of the records is a level of the sweep or a schedule of the maintenance model; NR = the instantiation's row count.
+// f(integral_constant<int, j>) for j = 0 .. NR - 1, written out at compile time: a row's registers are named by a constant.  (A
+// `#pragma unroll` loop with the run-time exit at n_levels was left a loop at NR = 16, and the partials were then indexed at run time.)
 template <class F, int... J>
-DEVFI void hl1_sweep_each(F&& f, std::integer_sequence<int, J...>) { (f(std::integral_constant<int, J>{}), ...); }
-template <int NL, class F>
-DEVFI void hl1_sweep_levels(F&& f) { hl1_sweep_each(f, std::make_integer_sequence<int, NL>{}); }
+DEVFI void hl1_rows_each(F&& f, std::integer_sequence<int, J...>) { (f(std::integral_constant<int, J>{}), ...); }
+template <int NR, class F>
+DEVFI void hl1_rows(F&& f) { hl1_rows_each(f, std::make_integer_sequence<int, NR>{}); }
 
-// The wave's open year of every level: loss hours and events are wave-uniform counts, level j's in lane j of cL / cF (32 scalar registers
+// The wave's open year of every row: loss hours and events are wave-uniform counts, row j's in lane j of cL / cF (32 scalar registers
 // as arrays: 391 scalar spills at 16 levels); EUE is the sequential model's fixed-order butterfly
-// over the lanes' partials (hl1_seq_close_year) -- skipped for a level without a loss hour in the year, whose partials are all +0.0 and
-// sum to +0.0 in any order.  Lane 0 stores (lole, eue, lolf) at out + j * level_stride; the counts and partials restart at zero.
-template <int NL>
-DEVFI void hl1_sweep_close_year(int nl, uint32_t& cL, uint32_t& cF, double (&aE)[NL], double* __restrict__ out, size_t level_stride)
+// over the lanes' partials (hl1_seq_close_year) -- skipped for a row without a loss hour in the year, whose partials are all +0.0 and
+// sum to +0.0 in any order.  Lane 0 stores (lole, eue, lolf) at out + j * row_stride; the counts and partials restart at zero.
+template <int NR>
+DEVFI void hl1_rows_close_year(int nr, uint32_t& cL, uint32_t& cF, double (&aE)[NR], double* __restrict__ out, size_t row_stride)
 {
-    hl1_sweep_levels<NL>([&](auto jc) {
+    hl1_rows<NR>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
-        if (j < nl) {                                        // wave-uniform
+        if (j < nr) {                                        // wave-uniform
             const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)cL, j), f = (uint32_t)__builtin_amdgcn_readlane((int)cF, j);
             double e = 0.0;
             if (l != 0u) {                                   // wave-uniform
@@ -95,17 +87,17 @@ DEVFI void hl1_sweep_close_year(int nl, uint32_t& cL, uint32_t& cF, double (&aE)
                 for (int off = 32; off > 0; off >>= 1) e += __shfl_xor(e, off);
                 aE[j] = 0.0;
             }
-            if ((threadIdx.x & 63) == 0) { double* const o = out + (size_t)j * level_stride; o[0] = (double)l; o[1] = e; o[2] = (double)f; }
+            if ((threadIdx.x & 63) == 0) { double* const o = out + (size_t)j * row_stride; o[0] = (double)l; o[1] = e; o[2] = (double)f; }
         }
     });
     cL = 0u; cF = 0u;
 }
 
 // ---- the kernel template --------------------------------------------------------------------------------------------------------------
-enum Hl1ChainModel : int { HL1_CHAIN_SEQ, HL1_CHAIN_EVENTS, HL1_CHAIN_SWEEP };
+enum Hl1ChainModel : int { HL1_CHAIN_SEQ, HL1_CHAIN_EVENTS, HL1_CHAIN_SWEEP, HL1_CHAIN_MAINT };
 
 // What a model's kernel takes after `start`.  These are kernel parameters of their own (the template's pack) and not one by-value struct:
-// a pointer read out of a struct is not __restrict__ to the compiler, and the argument segments stay those the three kernels had.
+// a pointer read out of a struct is not __restrict__ to the compiler, and the argument segments stay those the four kernels had.
 template <int MODEL> struct Hl1ChainTail;
 template <> struct Hl1ChainTail<HL1_CHAIN_SEQ> {
     double* __restrict__ year_out;                           // year_out[chain of the launch][year][3]
@@ -123,6 +115,12 @@ template <> struct Hl1ChainTail<HL1_CHAIN_SWEEP> {
     const Hl1SweepArgs& A;
     double* __restrict__ year_out;                           // year_out[level][chain of the launch][year][3]
 };
+template <> struct Hl1ChainTail<HL1_CHAIN_MAINT> {
+    double scale, shift;                                     // the one load of all schedules: scale * load[h] + shift
+    int32_t n_sched;
+    const uint32_t* __restrict__ tab;                        // tab[schedule][hour of the year][4], P schedules
+    double* __restrict__ year_out;                           // year_out[schedule][chain of the launch][year][3]
+};
 
 // A variable that only some of the template's instantiations have: T where ON, elsewhere an empty object.  Either starts from `{}` (zero,
 // false, nullptr): an empty object built from an initialiser, or one declared in the step loop, changed the other models' code.
@@ -135,14 +133,15 @@ template <bool ON, class T> using Hl1Only = std::conditional_t<ON, T, Hl1Absent>
 // its own step, so a plain OR is race-free); (2) one step per lane: capacity of the UP units in ascending unit order, then what the model
 // does with the group's capacities.  No workgroup barrier: the four waves run four chains.
 //
-// The three models are instantiations of this one text (MODEL; P = LIST for the events, NL for the sweep; ARG = the members of
-// Hl1ChainTail<MODEL>, in order and with their __restrict__), each with the instructions it had as a kernel of its own: the prologue, the
-// cursor start, the window clear, stage (1), the step index with its hour / year walk and the capacity sum are written once, a model's
-// state (declared through Hl1Only, so that no instantiation holds another model's), its stage and its tail are under `if constexpr`.
+// The four models are instantiations of this one text (MODEL; P = LIST for the events, the row count for the sweep (NL levels) and the
+// maintenance (NS schedules); ARG = the members of Hl1ChainTail<MODEL>, in order and with their __restrict__), each with the instructions
+// it had as a kernel of its own: the prologue, the cursor start, the window clear, stage (1), the step index with its hour / year walk
+// and the capacity sum are written once, a model's state (declared through Hl1Only, so that no instantiation holds another model's;
+// what the sweep and the maintenance have in common, the rows' state, once for both), its stage and its tail are under `if constexpr`.
 // The *kernel* is the template, on purpose.  The window loop is not a function that the kernels call: the two attempts to share it that
 // way each cost the sequential model 1.6-3 %, with any of the start rule, the fill or the cursor in a function of its
 // own, while the template route gives the compiler each kernel's whole text as before.  DESIGN.md 6.12 lists the formulations of this
-// text that did not reproduce the three kernels' code.  The kernels of the other tracks (storage, multi-state, multi-area) keep a window
+// text that did not reproduce the kernels' code.  The kernels of the other tracks (storage, multi-state, multi-area) keep a window
 // loop of their own for the same reason.
 //
 // sequential  loss flag and deficit against load[(n-1) mod H], rising edge (the previous step's flag from the neighbouring lane, lane 63's
@@ -167,14 +166,25 @@ template <bool ON, class T> using Hl1Only = std::conditional_t<ON, T, Hl1Absent>
 //   deficit into the lane's fp64 partial of the level (the sequential model's order: the lane's steps of the year ascending, + 0.0 left
 //   out), and its bit of the wave-uniform previous-step mask.  Years are closed when a later year shows up in an active group, or at the
 //   end of the chain; a skipped group adds nothing, so closing late changes no sum.  The passes over the levels are written out at compile
-//   time (hl1_sweep_levels), so no register array is indexed at run time.  Records: year_out[level][chain of the launch][year][3].
+//   time (hl1_rows), so no register array is indexed at run time.  Records: year_out[level][chain of the launch][year][3].
+//
+// maintenance  tab[schedule][hour of the year][4]: bit k & 31 of word k >> 5 = unit k on maintenance.  The table holds NS schedules (the
+//   host adds empty ones above n_sched) and no bit at or above ngen.  Per step the lane reads its hour's words of each schedule --
+//   consecutive lanes read consecutive hours, 16 bytes apart, so a wave's read of a schedule is one contiguous kilobyte -- and forms
+//   cap_j for the NS schedules in ONE ascending loop over the units: a unit's capacity is one scalar load for all schedules, and unit k
+//   adds cap_k to cap_j where its bit of (UP & ~maintenance_j) is set, 0.0 elsewhere.  With more than one schedule a first pass over the
+//   words asks whether any lane of the group has an UP unit on maintenance under any schedule; if none has, every cap_j is the one sum
+//   over the UP units (a unit that is DOWN adds 0.0 with or without maintenance, so the bits are those of the ascending sum).  From there
+//   on it is the sweep's stage with schedules for levels, cap_j for the level's fleet and one load L = scale * load[h] + shift for every
+//   schedule.  Records: year_out[schedule][chain of the launch][year][3].
 template <int MODEL, int P, class... ARG>
 __global__ void __launch_bounds__(256) relmc_hl1_chain_kernel(const Hl1SeqCase* __restrict__ S, const double* __restrict__ load, uint64_t seed,
                                                               uint64_t first_chain, int64_t n_chains, int32_t years, int32_t start, ARG... arg)
 {
-    constexpr bool SEQ = MODEL == HL1_CHAIN_SEQ, EVENTS = MODEL == HL1_CHAIN_EVENTS, SWEEP = MODEL == HL1_CHAIN_SWEEP;
+    constexpr bool SEQ = MODEL == HL1_CHAIN_SEQ, EVENTS = MODEL == HL1_CHAIN_EVENTS, SWEEP = MODEL == HL1_CHAIN_SWEEP, MAINT = MODEL == HL1_CHAIN_MAINT;
     constexpr bool LIST = EVENTS && P != 0;
-    constexpr int NL = SWEEP ? P : 1;
+    constexpr bool ROWS = SWEEP || MAINT;                    // one record row per level / per schedule
+    constexpr int NR = ROWS ? P : 1;
     constexpr int W = HL1_SEQ_WINDOW;
     __shared__ uint32_t masks[4][4][W];                     // [wave][mask word][step of the window], bit k & 31 of word k >> 5 = unit k down
     const Hl1ChainTail<MODEL> T{arg...};
@@ -188,14 +198,15 @@ __global__ void __launch_bounds__(256) relmc_hl1_chain_kernel(const Hl1SeqCase* 
     }
     const uint64_t chain = first_chain + (uint64_t)cl;
     const int ngen = S->ngen, H = S->nhours, nw = (ngen + 31) >> 5, nslot = ngen > 64 ? 2 : 1;
-    Hl1Only<SWEEP, int> nl{};
+    Hl1Only<ROWS, int> nr{};                                 // rows that are written: the caller's levels / schedules, NR at the most
     Hl1Only<SWEEP, bool> use1{};                             // some level uses fleet 1
-    if constexpr (SWEEP) { nl = T.A.n_levels < NL ? T.A.n_levels : NL; use1 = T.A.fleet1 != 0u; }
+    if constexpr (SWEEP) { nr = T.A.n_levels < NR ? T.A.n_levels : NR; use1 = T.A.fleet1 != 0u; }
+    if constexpr (MAINT) nr = T.n_sched < NR ? T.n_sched : NR;
     uint32_t (*const seg)[W] = masks[wv];
     const int64_t nsteps = (int64_t)years * H;
-    Hl1Only<SWEEP, size_t> level_stride{};
-    if constexpr (SWEEP) level_stride = (size_t)n_chains * (size_t)years * 3;
-    Hl1Only<!EVENTS, double*> out{};                         // the chain's year records (the sweep's: of level 0)
+    Hl1Only<ROWS, size_t> row_stride{};
+    if constexpr (ROWS) row_stride = (size_t)n_chains * (size_t)years * 3;
+    Hl1Only<!EVENTS, double*> out{};                         // the chain's year records (with rows: of row 0)
     if constexpr (!EVENTS) out = T.year_out + (size_t)cl * (size_t)years * 3;
 
     bool down[2], mine[2];
@@ -249,15 +260,15 @@ __global__ void __launch_bounds__(256) relmc_hl1_chain_kernel(const Hl1SeqCase* 
             if (T.hist) atomicAdd(T.hist + ((D < T.n_bins ? D : (long long)T.n_bins) - 1), 1ull);
         }
     };
-    // sweep
-    Hl1Only<SWEEP, double[NL]> aEl;                          // this lane's EUE partial of the open year ycur, per level
-    Hl1Only<SWEEP, uint32_t> cL{}, cF{};                     // the wave's loss hours and loss events of the open year: level j's in lane j
-    if constexpr (SWEEP) hl1_sweep_levels<NL>([&](auto jc) { aEl[decltype(jc)::value] = 0.0; });
+    // sweep, maintenance
+    Hl1Only<ROWS, double[NR]> aEl;                           // this lane's EUE partial of the open year ycur, per row
+    Hl1Only<ROWS, uint32_t> cL{}, cF{};                      // the wave's loss hours and loss events of the open year: row j's in lane j
+    if constexpr (ROWS) hl1_rows<NR>([&](auto jc) { aEl[decltype(jc)::value] = 0.0; });
     Hl1Only<!EVENTS, int> ycur{};
     Hl1Only<!EVENTS, int> gy{};                              // chain year and
     int gh = 0;                                              // hour of the year of the current 64-step group's first step
     Hl1Only<SEQ, bool> prev{};                               // loss flag of the step before the group (none before step 1)
-    Hl1Only<SWEEP, uint32_t> prevs{};                        // bit j: level j's loss flag on the step before the group (wave-uniform)
+    Hl1Only<ROWS, uint32_t> prevs{};                         // bit j: row j's loss flag on the step before the group (wave-uniform)
     for (int64_t w0 = 1; w0 <= nsteps; w0 += W) {
         const int64_t w1 = w0 + W;
         const int wlen = nsteps - w0 + 1 < W ? (int)(nsteps - w0 + 1) : W;
@@ -305,12 +316,14 @@ __global__ void __launch_bounds__(256) relmc_hl1_chain_kernel(const Hl1SeqCase* 
             bool f = false;                                  // sequential, events: the step's loss flag and deficit
             double d = 0.0;
             // cap: capacity of the UP units, summed here by the lanes with a step; in the sweep by every lane, or, with a level on fleet 1,
-            // by none: its stage below then forms both fleets' capacities in one loop.  (One text for both loops did not hold: as a lambda
-            // or a function over F1 it exchanged two register pairs of the sequential model's year close, and with the fleet test inside
-            // this loop the sweep lost the two loops it had.)
+            // by none: its stage below then forms both fleets' capacities in one loop; never in the maintenance model, whose stage forms
+            // its schedules' capacities.  (One text for both loops did not hold: as a lambda or a function over F1 it exchanged two
+            // register pairs of the sequential model's year close, and with the fleet test inside this loop the sweep lost the two loops
+            // it had.)
             double cap = 0.0;
             bool plain = valid;
             if constexpr (SWEEP) plain = !use1;              // wave-uniform
+            if constexpr (MAINT) plain = false;
             if (plain) {
                 for (int q = 0; q < nw; ++q) {
                     const uint32_t up = ~seg[q][i];
@@ -399,7 +412,7 @@ __global__ void __launch_bounds__(256) relmc_hl1_chain_kernel(const Hl1SeqCase* 
                 int z = 0;
                 __asm__ volatile("" : "+s"(z));
                 const uint32_t fleet1 = A.fleet1 | (uint32_t)z;
-                hl1_sweep_levels<NL>([&](auto jc) {
+                hl1_rows<NR>([&](auto jc) {
                     constexpr int j = decltype(jc)::value;
                     const double L = hl1_sweep_load(A.lv[j + z].scale, ld, A.lv[j + z].shift);
                     const double cj = ((fleet1 >> j) & 1u) ? cap1 : cap;
@@ -415,7 +428,7 @@ __global__ void __launch_bounds__(256) relmc_hl1_chain_kernel(const Hl1SeqCase* 
                         const bool in = valid && y == ycur;
                         const uint64_t my = __builtin_amdgcn_ballot_w64(in);
                         next = 0u;
-                        hl1_sweep_levels<NL>([&](auto jc) {
+                        hl1_rows<NR>([&](auto jc) {
                             constexpr int j = decltype(jc)::value;
                             if ((act >> j) & 1u) {               // wave-uniform: a level without a loss step and without an open flag is left out
                                 const double L = hl1_sweep_load(A.lv[j + z].scale, lda, A.lv[j + z].shift);
@@ -429,7 +442,81 @@ __global__ void __launch_bounds__(256) relmc_hl1_chain_kernel(const Hl1SeqCase* 
                             }
                         });
                         if (!__any(valid && y > ycur)) break;
-                        hl1_sweep_close_year<NL>(nl, cL, cF, aEl, out + (size_t)ycur * 3, level_stride);
+                        hl1_rows_close_year<NR>(nr, cL, cF, aEl, out + (size_t)ycur * 3, row_stride);
+                        ++ycur;
+                    }
+                    prevs = next;
+                }
+            }
+            if constexpr (MAINT) {
+                const uint32_t* const mrow = T.tab + (size_t)h * 4;                   // schedule j's words of the hour: mrow[j * H * 4 + q]
+                const size_t sched_words = (size_t)H * 4;
+                double capj[NR];
+                hl1_rows<NR>([&](auto jc) { capj[decltype(jc)::value] = 0.0; });
+                bool overlay = true;                             // wave-uniform: some lane has an UP unit on maintenance under some schedule
+                if constexpr (NR > 1) {
+                    uint32_t hit = 0u;
+                    for (int q = 0; q < nw; ++q) {
+                        const uint32_t up = ~seg[q][i];
+                        hl1_rows<NR>([&](auto jc) { hit |= up & mrow[(size_t)decltype(jc)::value * sched_words + q]; });
+                    }
+                    overlay = __builtin_amdgcn_ballot_w64(valid && hit != 0u) != 0;
+                }
+                if (overlay) {
+                    for (int q = 0; q < nw; ++q) {
+                        const uint32_t up = ~seg[q][i];
+                        uint32_t on[NR];                         // UP and not on maintenance under schedule j
+                        hl1_rows<NR>([&](auto jc) {
+                            constexpr int j = decltype(jc)::value;
+                            on[j] = up & ~mrow[(size_t)j * sched_words + q];
+                        });
+                        const int kn = ngen - 32 * q < 32 ? ngen - 32 * q : 32;
+                        for (int b = 0; b < kn; ++b) {
+                            const double c = S->cap[32 * q + b];
+                            hl1_rows<NR>([&](auto jc) {                               // ascending units; + 0.0 is exact
+                                constexpr int j = decltype(jc)::value;
+                                capj[j] += ((on[j] >> b) & 1u) ? c : 0.0;
+                            });
+                        }
+                    }
+                } else {
+                    double all = 0.0;
+                    for (int q = 0; q < nw; ++q) {
+                        const uint32_t up = ~seg[q][i];
+                        const int kn = ngen - 32 * q < 32 ? ngen - 32 * q : 32;
+                        for (int b = 0; b < kn; ++b) all += ((up >> b) & 1u) ? S->cap[32 * q + b] : 0.0;
+                    }
+                    hl1_rows<NR>([&](auto jc) { capj[decltype(jc)::value] = all; });
+                }
+                const double L = hl1_sweep_load(T.scale, load[h], T.shift);
+                // which schedules have a loss step in the group (the comparison's lane mask is the ballot)
+                uint32_t act = prevs;
+                hl1_rows<NR>([&](auto jc) {
+                    constexpr int j = decltype(jc)::value;
+                    if (j < nr && __builtin_amdgcn_ballot_w64(valid && capj[j] < L) != 0) act |= 1u << j;
+                });
+                // The sweep's account of the group, with the one L and capj[j] for the level's load and fleet.  It is written a second time:
+                // as one text for both models (a lambda over the row's load and capacity, or one loop with the models' values declared
+                // ahead of it) it did not reproduce the sweep's or the maintenance kernels' code.
+                if (act != 0u) {                                 // wave-uniform
+                    uint32_t next = 0u;
+                    for (;;) {
+                        const bool in = valid && y == ycur;
+                        const uint64_t my = __builtin_amdgcn_ballot_w64(in);
+                        next = 0u;
+                        hl1_rows<NR>([&](auto jc) {
+                            constexpr int j = decltype(jc)::value;
+                            if ((act >> j) & 1u) {               // wave-uniform: a schedule without a loss step and without an open flag is left out
+                                const bool fj = valid && capj[j] < L;
+                                const uint64_t m = __builtin_amdgcn_ballot_w64(fj);
+                                const uint64_t r = m & ~((m << 1) | (uint64_t)((prevs >> j) & 1u));     // the flag rises: the step before had none
+                                cL += lane == j ? (uint32_t)__popcll(m & my) : 0u; cF += lane == j ? (uint32_t)__popcll(r & my) : 0u;
+                                aEl[j] += (fj && in) ? L - capj[j] : 0.0;
+                                next |= (uint32_t)(m >> 63) << j;
+                            }
+                        });
+                        if (!__any(valid && y > ycur)) break;
+                        hl1_rows_close_year<NR>(nr, cL, cF, aEl, out + (size_t)ycur * 3, row_stride);
                         ++ycur;
                     }
                     prevs = next;
@@ -444,52 +531,10 @@ __global__ void __launch_bounds__(256) relmc_hl1_chain_kernel(const Hl1SeqCase* 
     if constexpr (EVENTS && !LIST) {
         if (lane == 0) { a.events = cnt; T.rec[cl] = a; T.count[cl] = cnt; }
     }
-    if constexpr (SWEEP)
-        for (; ycur < years; ++ycur) hl1_sweep_close_year<NL>(nl, cL, cF, aEl, out + (size_t)ycur * 3, level_stride);
+    if constexpr (ROWS)
+        for (; ycur < years; ++ycur) hl1_rows_close_year<NR>(nr, cL, cF, aEl, out + (size_t)ycur * 3, row_stride);
 }
-
-// The seven instantiations, by the names their launches use (relmc_seq.hip)
-constexpr auto relmc_hl1_seq_kernel = relmc_hl1_chain_kernel<HL1_CHAIN_SEQ, 0, double* __restrict__>;
-template <bool LIST>
-constexpr auto relmc_hl1_event_kernel = relmc_hl1_chain_kernel<HL1_CHAIN_EVENTS, LIST, int32_t, unsigned long long* __restrict__, Hl1EventRec* __restrict__,
-                                                               long long* __restrict__, const long long* __restrict__, int64_t, int64_t, relmc_hl1_event* __restrict__>;
-template <int NL>
-constexpr auto relmc_hl1_sweep_kernel = relmc_hl1_chain_kernel<HL1_CHAIN_SWEEP, NL, const Hl1SweepArgs, double* __restrict__>;
-
-// ---- the event model's other kernels --------------------------------------------------------------------------------------------------
-// offset[i] = count[0] + ... + count[i - 1] for i < n, one workgroup: a contiguous slice per thread, the slices' sums scanned by thread 0
-__global__ void __launch_bounds__(256) relmc_hl1_event_scan_kernel(const long long* __restrict__ count, int64_t n, long long* __restrict__ offset)
-{
-    __shared__ long long tot[256];
-    const int tid = threadIdx.x;
-    const int64_t per = (n + 255) / 256, lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
-    long long s = 0;
-    for (int64_t i = lo; i < hi; ++i) s += count[i];
-    tot[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        long long run = 0;
-        for (int t = 0; t < 256; ++t) { const long long v = tot[t]; tot[t] = run; run += v; }
-    }
-    __syncthreads();
-    s = tot[tid];
-    for (int64_t i = lo; i < hi; ++i) { offset[i] = s; s += count[i]; }
-}
-
-// Sum of n chain records: grid-stride in a fixed order, then a fixed tree; partial[block] (relmc_hl1_reduce_kernel's pattern)
-__global__ void __launch_bounds__(256) relmc_hl1_event_reduce_kernel(const Hl1EventRec* __restrict__ rec, int64_t n, Hl1EventRec* __restrict__ partial)
-{
-    __shared__ Hl1EventRec red[256];
-    const int tid = threadIdx.x;
-    Hl1EventRec s;
-    hl1_event_rec_zero(s);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < n; i += (int64_t)gridDim.x * 256) hl1_event_rec_add(s, rec[i]);
-    red[tid] = s;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (tid < off) hl1_event_rec_add(red[tid], red[tid + off]);
-        __syncthreads();
-    }
-    if (tid == 0) partial[blockIdx.x] = red[0];
-}
+// The eleven instantiations go by the names relmc_hl1_seq_kernel, relmc_hl1_event_kernel<LIST>, relmc_hl1_sweep_kernel<NL>
+// (relmc_seq.hip) and relmc_hl1_maint_kernel<NS> (relmc_maint.hip), each defined in the unit that launches it: a name defined here
+// that is no template would instantiate its kernel in every unit that reads this header.
 }  // namespace relmc

@@ -33,4 +33,11 @@ DEVFI double hl1_sweep_load(double scale, double ld, double shift)
     return p + shift;
 }
 
+// An event record without events (relmc_hl1_seq_events: a chain's record before its first event, a reduction slice before its first record)
+DEVFI void hl1_event_rec_zero(Hl1EventRec& r)
+{
+    r.events = r.sum_dur = r.sum_dur2 = r.max_dur = r.censored = 0;
+    r.sum_energy = r.sum_energy2 = r.max_energy = r.max_peak = 0.0;
+}
+
 }  // namespace relmc

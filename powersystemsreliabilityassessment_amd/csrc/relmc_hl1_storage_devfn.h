@@ -10,7 +10,7 @@
 
 namespace relmc {
 
-// f(integral_constant<int, i>) for i = 0 .. RELMC_HL1_MAX_STORAGE - 1, written out at compile time (as hl1_sweep_levels): a storage's
+// f(integral_constant<int, i>) for i = 0 .. RELMC_HL1_MAX_STORAGE - 1, written out at compile time (as hl1_rows): a storage's
 // state of charge is a register named by a constant, never a run-time index into a per-thread array (scratch)
 template <class F, int... I>
 DEVFI void hl1_storage_each_(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }

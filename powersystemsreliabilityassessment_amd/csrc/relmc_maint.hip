@@ -1,19 +1,24 @@
 // relmc_maint.hip — planned maintenance on the HL1 sequential chronology (relmc_hl1_maint_load, relmc_hl1_maint_seq, contract in
 // include/relmc.h): the fleet of relmc_hl1_seq_load under up to 8 maintenance schedules, all compared on one fleet history.
-// A unit of its own, so that the code objects of relmc_seq.hip and the other tracks stay what they were; the kernel is
-// relmc_hl1_maint_kernels.h's, the launches and the sums relmc_hl1_host.h's hl1_run_records with one slice per schedule, the slices
-// summed by relmc_hl1_reduce_kernel (hl1_reduce_queue, relmc_seq.hip).
+// A unit of its own, so that the code objects of relmc_seq.hip and the other tracks stay what they were; the kernel is the maintenance
+// model of relmc_hl1_chain_kernels.h's template, of which this unit holds the four instantiations it launches and nothing else; the
+// launches and the sums are relmc_hl1_host.h's hl1_run_records with one slice per schedule, the slices summed by
+// relmc_hl1_reduce_kernel (hl1_reduce_queue, relmc_seq.hip).
 #include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "relmc_hl1_host.h"
-#include "relmc_hl1_maint_kernels.h"
+#include "relmc_hl1_chain_kernels.h"
 
 using namespace relmc_host;
 
 namespace {
+// The four instantiations of relmc_hl1_chain_kernels.h's template that this unit launches (NS = the schedules a walk compares)
+template <int NS>
+constexpr auto relmc_hl1_maint_kernel = relmc::relmc_hl1_chain_kernel<relmc::HL1_CHAIN_MAINT, NS, double, double, int32_t, const uint32_t* __restrict__, double* __restrict__>;
+
 // schedules the kernel instantiation for n_schedules walks (relmc_hl1_maint_kernel<1, 2, 4, 8>): the table holds that many
 int maint_width(int n_schedules) { return n_schedules <= 1 ? 1 : n_schedules <= 2 ? 2 : n_schedules <= 4 ? 4 : 8; }
 }  // namespace
@@ -85,8 +90,8 @@ int32_t relmc_hl1_maint_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain,
     if (n_chains == 0) return RELMC_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int width = maint_width(ns);
-    const auto kernel = width == 1 ? relmc::relmc_hl1_maint_kernel<1> : width == 2 ? relmc::relmc_hl1_maint_kernel<2>
-                      : width == 4 ? relmc::relmc_hl1_maint_kernel<4> : relmc::relmc_hl1_maint_kernel<8>;
+    const auto kernel = width == 1 ? relmc_hl1_maint_kernel<1> : width == 2 ? relmc_hl1_maint_kernel<2>
+                      : width == 4 ? relmc_hl1_maint_kernel<4> : relmc_hl1_maint_kernel<8>;
     std::vector<double> sum((size_t)6 * ns, 0.0);
     const int64_t per = hl1_chunk_items(n_chains, kHl1RecordBudget, (int64_t)years_per_chain * ns);      // a chain counts its records of all schedules
     const int rc = hl1_run_records(ctx, "relmc_hl1_maint_seq", M.rec, n_chains, per, years_per_chain, ns, sum.data(),

@@ -14,6 +14,14 @@
 namespace relmc_host {
 
 namespace {
+// The seven instantiations of relmc_hl1_chain_kernels.h's template that this unit launches, by the names of the launches
+constexpr auto relmc_hl1_seq_kernel = relmc_hl1_chain_kernel<HL1_CHAIN_SEQ, 0, double* __restrict__>;
+template <bool LIST>
+constexpr auto relmc_hl1_event_kernel = relmc_hl1_chain_kernel<HL1_CHAIN_EVENTS, LIST, int32_t, unsigned long long* __restrict__, Hl1EventRec* __restrict__,
+                                                               long long* __restrict__, const long long* __restrict__, int64_t, int64_t, relmc_hl1_event* __restrict__>;
+template <int NL>
+constexpr auto relmc_hl1_sweep_kernel = relmc_hl1_chain_kernel<HL1_CHAIN_SWEEP, NL, const Hl1SweepArgs, double* __restrict__>;
+
 // chronology of years [first_year, first_year + n_years) into the caller's device masks dm (n_years * hpy * mw words, every word written)
 int seq_sample(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int n_years, uint32_t* dm)
 {

@@ -1,8 +1,10 @@
 // relmc_seq_kernels.h — kernels of the sequential track (Montecarlo_seq/: chronology sampling, contingency-hour compaction, annual indices)
 // and of the HL1 copper-sheet non-sequential model (GeneratingAdequacy/PowerSystemAdequacy.jl:169-208), and the reduction of the year
-// records of every HL1 track.  The HL1 sequential chronology (:214-268) is relmc_hl1_chain_kernels.h's.
+// records of every HL1 track.  The HL1 sequential chronology (:214-268) is relmc_hl1_chain_kernels.h's; the two kernels that scan the event
+// counts and reduce the event records stand here, so that only relmc_seq.hip holds them.
 #pragma once
 #include "relmc_devfn.h"
+#include "relmc_hl1_chrono.h"
 
 namespace relmc {
 
@@ -191,5 +193,51 @@ __global__ void __launch_bounds__(256) relmc_hl1_reduce_kernel(const double* __r
         __syncthreads();
     }
     if (tid < 6) partial[(size_t)blockIdx.x * 6 + tid] = red[tid][0];
+}
+
+// ---- the event model's other kernels (relmc_hl1_seq_events; the chain kernel itself is relmc_hl1_chain_kernels.h's) ---------------------
+// a += b (sums first + second: the order is part of the results)
+DEVFI void hl1_event_rec_add(Hl1EventRec& a, const Hl1EventRec& b)
+{
+    a.events += b.events; a.sum_dur += b.sum_dur; a.sum_dur2 += b.sum_dur2; a.censored += b.censored;
+    a.max_dur = a.max_dur > b.max_dur ? a.max_dur : b.max_dur;
+    a.sum_energy += b.sum_energy; a.sum_energy2 += b.sum_energy2;
+    a.max_energy = fmax(a.max_energy, b.max_energy); a.max_peak = fmax(a.max_peak, b.max_peak);
+}
+
+// offset[i] = count[0] + ... + count[i - 1] for i < n, one workgroup: a contiguous slice per thread, the slices' sums scanned by thread 0
+__global__ void __launch_bounds__(256) relmc_hl1_event_scan_kernel(const long long* __restrict__ count, int64_t n, long long* __restrict__ offset)
+{
+    __shared__ long long tot[256];
+    const int tid = threadIdx.x;
+    const int64_t per = (n + 255) / 256, lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
+    long long s = 0;
+    for (int64_t i = lo; i < hi; ++i) s += count[i];
+    tot[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        long long run = 0;
+        for (int t = 0; t < 256; ++t) { const long long v = tot[t]; tot[t] = run; run += v; }
+    }
+    __syncthreads();
+    s = tot[tid];
+    for (int64_t i = lo; i < hi; ++i) { offset[i] = s; s += count[i]; }
+}
+
+// Sum of n chain records: grid-stride in a fixed order, then a fixed tree; partial[block] (relmc_hl1_reduce_kernel's pattern)
+__global__ void __launch_bounds__(256) relmc_hl1_event_reduce_kernel(const Hl1EventRec* __restrict__ rec, int64_t n, Hl1EventRec* __restrict__ partial)
+{
+    __shared__ Hl1EventRec red[256];
+    const int tid = threadIdx.x;
+    Hl1EventRec s;
+    hl1_event_rec_zero(s);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < n; i += (int64_t)gridDim.x * 256) hl1_event_rec_add(s, rec[i]);
+    red[tid] = s;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) hl1_event_rec_add(red[tid], red[tid + off]);
+        __syncthreads();
+    }
+    if (tid == 0) partial[blockIdx.x] = red[0];
 }
 }  // namespace relmc

@@ -21,12 +21,14 @@ for ties in "01":
 TRACK_ARGS = "PKNS_10Hl1SeqCaseEPKdmmliiNS_%sEPd"            # relmc_hl1_storage_track_kernel<0 | 1 | 2>: the storage, weather and stress kernels
 for track, (was, args) in enumerate((("24relmc_hl1_storage_kernel", "14Hl1StorageArgs"), ("20relmc_hl1_var_kernel", "10Hl1VarArgs"), ("23relmc_hl1_stress_kernel", "13Hl1StressArgs"))):
     RENAMED["_ZN5relmc" + was + "E" + TRACK_ARGS % args] = "_ZN5relmc30relmc_hl1_storage_track_kernelILi%dEEEv" % track + TRACK_ARGS % "12Hl1TrackArgsIXT_EE4type"
-CHAIN = "_ZN5relmc22relmc_hl1_chain_kernelILi%dELi%dEJ%sEEEvPKNS_10Hl1SeqCaseEPKdmmliiDpT1_"      # relmc_hl1_chain_kernel<MODEL, P, ARG...>: the sequential, event and sweep kernels
+CHAIN = "_ZN5relmc22relmc_hl1_chain_kernelILi%dELi%dEJ%sEEEvPKNS_10Hl1SeqCaseEPKdmmliiDpT1_"      # relmc_hl1_chain_kernel<MODEL, P, ARG...>: the sequential, event, sweep and maintenance kernels
 RENAMED["_ZN5relmc20relmc_hl1_seq_kernelEPKNS_10Hl1SeqCaseEPKdmmliiPd"] = CHAIN % (0, 0, "rPd")
 for p in (0, 1):
     RENAMED["_ZN5relmc22relmc_hl1_event_kernelILb%dEEEvPKNS_10Hl1SeqCaseEPKdmmliiiPyPNS_11Hl1EventRecEPxPKxllP15relmc_hl1_event" % p] = CHAIN % (1, p, "irPyrPNS_11Hl1EventRecErPxrPKxllrP15relmc_hl1_event")
 for p in (1, 4, 8, 16):
     RENAMED["_ZN5relmc22relmc_hl1_sweep_kernelILi%dEEEvPKNS_10Hl1SeqCaseEPKdmmliiNS_12Hl1SweepArgsEPd" % p] = CHAIN % (2, p, "KNS_12Hl1SweepArgsErPd")
+for p in (1, 2, 4, 8):                                       # the maintenance kernel, a template of its own at first, is the template's fourth model
+    RENAMED["_ZN5relmc22relmc_hl1_maint_kernelILi%dEEEvPKNS_10Hl1SeqCaseEPKdmmliiddiPKjPd" % p] = CHAIN % (3, p, "ddirPKjrPd")
 
 
 def asm(csrc, out):

@@ -473,6 +473,44 @@ int32_t relmc_hl1_maint_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain,
                             int32_t start, double scale, double shift, relmc_hl1_seq_acc* acc,
                             relmc_hl1_seq_year* years_host);
 
+/* ---- loss attribution on the HL1 sequential chronology: which units are down when load is lost (nsqMain.m:366-376, seqMain.m:144-158,233) ---- */
+/* The reference ranks components by the share of its loss hours in which each was out (comp_importance).  Here every loss step of a chain
+ * is charged to the units that are DOWN in it, and two of the charged quantities are exact counterfactuals on the same fleet history:
+ * the units are independent, so a history with unit k always UP is this history with cap_k added wherever k is DOWN.
+ * Chronology  relmc_hl1_seq's, word for word (model of relmc_hl1_seq_load, draws (seed, chain, k | 0x40000000, event), both start rules,
+ *             no FMA, DOWN on steps [ceil(T_odd), ceil(T_even))): under one seed, chain c sees exactly the fleet history of chain c of
+ *             relmc_hl1_seq.
+ * Load        L = scale * load[h] + shift, the product and the sum each rounded (relmc_hl1_seq_sweep's rule).
+ * Loss        iff cap_avail < L (strict), cap_avail the sum of the UP units' capacities in ascending unit order; deficit d = L - cap_avail.
+ * Year records are bitwise relmc_hl1_seq_sweep's level (scale, shift, fleet 0), and at (1.0, 0.0) bitwise relmc_hl1_seq's; acc sums them
+ *             as those calls do, launch by launch, so it is bitwise theirs whenever both calls take one launch (the chunk rule below).
+ * Unit record of a chain, over all its steps n = 1 .. Y*H that are loss steps with unit k DOWN:
+ *   down_hours      the number of such steps
+ *   down_mwh        the sum of d
+ *   critical_hours  the number of those with !(cap_avail + cap_k < L), the sum rounded once: the steps that would be no loss steps with k
+ *                   UP (a tie cap_avail + cap_k == L counts).  Summed over a run, loss hours - critical_hours_k is the loss hours of the
+ *                   fleet with unit k perfectly reliable, on the same history
+ *   relief_mwh      the sum of fmin(d, cap_k): EUE - relief_mwh_k is that fleet's EUE
+ *   The two fp64 sums are one accumulator per unit, added in ascending step order over the whole chain; the counts are exact (fp64,
+ *   below 2^53).  Steps past Y*H do not exist.
+ * unit_acc[k] sums x and x * x over the chains of the call, x = the chain's record of unit k in the field order above, reduced on the
+ * device in a fixed order: a repeated call is bitwise equal.  A chain's own record depends on (seed, chain, start, years_per_chain,
+ * data, scale, shift) only, never on the launch or call it is in. */
+typedef struct { double down_hours, down_mwh, critical_hours, relief_mwh; } relmc_hl1_attr_unit;   /* 32 bytes */
+typedef struct { double sum[4], sum2[4]; } relmc_hl1_attr_acc;                                     /* 64 bytes */
+/* chains [first_chain, first_chain + n_chains), each years_per_chain consecutive years, of the model loaded by relmc_hl1_seq_load
+ * (RELMC_ERR_NO_CASE before that call).  RELMC_ERR_INVALID for: a null ctx, acc or unit_acc; a non-finite scale or shift; anything
+ * relmc_hl1_seq refuses.  A refused call changes nothing; n_chains == 0 zeroes the outputs.
+ *   unit_acc    [ngen]
+ *   years_host  optional [n_chains * years_per_chain], chain-major
+ *   unit_host   optional [n_chains][ngen], chain-major
+ * Long chain ranges go in launches of at most ~4M records, a chain counting years_per_chain + (4 * ngen + 2) / 3 (its year records and
+ * its unit records in year records' size); relmc_last_kernel_ms covers every launch. */
+int32_t relmc_hl1_attr_seq(relmc_ctx* ctx, uint64_t seed, uint64_t first_chain, int64_t n_chains, int32_t years_per_chain,
+                           int32_t start, double scale, double shift, relmc_hl1_seq_acc* acc,
+                           relmc_hl1_seq_year* years_host, relmc_hl1_attr_acc* unit_acc,
+                           relmc_hl1_attr_unit* unit_host);
+
 /* ---- energy storage on the HL1 sequential chronology: state of charge carried from hour to hour (an extension beyond the reference) ---- */
 /* What a battery does to LOLE, EUE and LOLF exists only on a chronology: its state of charge couples the hours.  Up to 8 storages, given
  * in the call (as the sweep's levels are: no load call, no model state in the context), discharge into a shortfall of the fleet of

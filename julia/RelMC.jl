@@ -607,6 +607,49 @@ const LAYOUT_HL1_MAINT = [
     ("relmc_hl1_maint_window", 16, [("schedule", 0), ("unit", 4), ("start_hour", 8), ("hours", 12)]),
 ]
 
+"relmc_hl1_attr_unit (include/relmc.h, 32 bytes): one chain's loss steps with the unit DOWN: their number, their deficit, those the unit, UP, would have prevented, and the deficit it would have served"
+struct Hl1AttrUnit
+    down_hours::Cdouble; down_mwh::Cdouble; critical_hours::Cdouble; relief_mwh::Cdouble
+end
+"relmc_hl1_attr_acc (64 bytes): sums of x and x * x over the chains of a call, x = a chain's Hl1AttrUnit in field order"
+struct Hl1AttrAcc
+    sum::NTuple{4,Cdouble}; sum2::NTuple{4,Cdouble}
+end
+
+"""
+run_sequential_attribution (the reference's comp_importance, seqMain.m:144-158, 233, on the HL1 chronology): run_sequential_mc's chronology,
+same arguments and same chains under one seed, at the load scale * hourly_load + shift, with every loss step charged to the units that
+are DOWN in it.  Returns the indices and, per unit, importance = down_hours / loss hours, energy_importance = down_mwh / EUE, and the
+exact counterfactuals on the same fleet history lole_if_perfect = LOLE - critical_hours / years and eue_if_perfect = EUE - relief_mwh /
+years, with the chains' unit records (units x chains).
+"""
+function run_sequential_attribution(eng::Engine, capacity::Vector{Float64}, mttf::Vector{Float64}, mttr::Vector{Float64},
+                                    hourly_load::Vector{Float64}, years::Integer;
+                                    seed::Integer=1, chains::Integer=1, start::Symbol=:all_up, scale::Real=1.0, shift::Real=0.0)
+    (years >= 1 && chains >= 1 && years % chains == 0) || throw(ArgumentError("years must be a positive multiple of chains"))
+    K = length(capacity)
+    check(ccall((:relmc_hl1_seq_load, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cdouble}),
+                eng.h, K, capacity, mttf, mttr, length(hourly_load), hourly_load), eng.h, "relmc_hl1_seq_load")
+    acc = Hl1SeqAcc(); yrs = Vector{Hl1SeqYear}(undef, years)
+    uacc = Vector{Hl1AttrAcc}(undef, K); rec = Vector{Hl1AttrUnit}(undef, K * chains)
+    check(ccall((:relmc_hl1_attr_seq, LIB), Int32,
+                (Ptr{Cvoid}, UInt64, UInt64, Int64, Int32, Int32, Cdouble, Cdouble, Ref{Hl1SeqAcc}, Ptr{Hl1SeqYear}, Ptr{Hl1AttrAcc}, Ptr{Hl1AttrUnit}),
+                eng.h, seed, 0, chains, years ÷ chains, HL1_START[start], Float64(scale), Float64(shift), acc, yrs, uacc, rec),
+          eng.h, "relmc_hl1_attr_seq")
+    lole, eue = acc.sum_lole / years, acc.sum_eue / years
+    return (lole_hours_yr=lole, eue_mwh_yr=eue, lolf_occ_yr=acc.sum_lolf / years,
+            importance=[uacc[k].sum[1] / acc.sum_lole for k in 1:K], energy_importance=[uacc[k].sum[2] / acc.sum_eue for k in 1:K],
+            lole_if_perfect=[lole - uacc[k].sum[3] / years for k in 1:K], eue_if_perfect=[eue - uacc[k].sum[4] / years for k in 1:K],
+            year_lole=[y.lole for y in yrs], year_eue=[y.eue for y in yrs], year_lolf=[y.lolf for y in yrs],
+            unit_records=reshape(rec, K, chains))
+end
+
+# Layout of the attribution records, kept apart from LAYOUT (tests/test_hl1_attr_host.py compares it with the C compiler's and with ctypes)
+const LAYOUT_HL1_ATTR = [
+    ("relmc_hl1_attr_unit", 32, [("down_hours", 0), ("down_mwh", 8), ("critical_hours", 16), ("relief_mwh", 24)]),
+    ("relmc_hl1_attr_acc", 64, [("sum", 0), ("sum2", 32)]),
+]
+
 "relmc_hl1_storage (include/relmc.h, 48 bytes): one energy storage of relmc_hl1_seq_storage; powers in MW, energies in MWh, efficiencies in (0, 1]"
 struct Hl1Storage
     charge_mw::Cdouble; discharge_mw::Cdouble; energy_mwh::Cdouble; eta_charge::Cdouble; eta_discharge::Cdouble; soc0_mwh::Cdouble

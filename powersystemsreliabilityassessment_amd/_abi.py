@@ -144,6 +144,16 @@ class Hl1MaintWindow(C.Structure):        # relmc_hl1_maint_window (16 bytes)
 
 
 HL1_MAINT_MAX_SCHEDULES = 8               # RELMC_HL1_MAINT_MAX_SCHEDULES
+
+
+class Hl1AttrUnit(C.Structure):           # relmc_hl1_attr_unit (32 bytes): one chain's loss steps with the unit DOWN
+    _fields_ = [("down_hours", C.c_double), ("down_mwh", C.c_double), ("critical_hours", C.c_double), ("relief_mwh", C.c_double)]
+
+
+class Hl1AttrAcc(C.Structure):            # relmc_hl1_attr_acc (64 bytes): sums of x and x * x over the chains, x in Hl1AttrUnit's field order
+    _fields_ = [("sum", C.c_double * 4), ("sum2", C.c_double * 4)]
+
+
 HL1_MAX_STORAGE = 8                       # RELMC_HL1_MAX_STORAGE
 
 

@@ -24,7 +24,7 @@ EXPORTS = [
     "relmc_last_kernel_ms", "relmc_acc_zero", "relmc_acc_merge", "relmc_nsq_indices",
     "relmc_nsq_run", "relmc_hl1_load", "relmc_hl1_nsq", "relmc_hl1_seq_load", "relmc_hl1_seq", "relmc_hl1_seq_events", "relmc_hl1_seq_sweep",
     "relmc_hl1_seq_storage", "relmc_hl1_var_load", "relmc_hl1_var_seq", "relmc_hl1_var_weather_year", "relmc_hl1_stress_load", "relmc_hl1_stress_seq",
-    "relmc_hl1_stress_cumulative", "relmc_hl1_stress_failure_time", "relmc_hl1_maint_load", "relmc_hl1_maint_seq", "relmc_hl1_ms_load", "relmc_hl1_ms_seq",
+    "relmc_hl1_stress_cumulative", "relmc_hl1_stress_failure_time", "relmc_hl1_maint_load", "relmc_hl1_maint_seq", "relmc_hl1_attr_seq", "relmc_hl1_ms_load", "relmc_hl1_ms_seq",
     "relmc_hl1_plan_load", "relmc_hl1_plan", "relmc_hl1_area_load", "relmc_hl1_area", "relmc_hl1_area_tie_outages", "relmc_hl1_area_sweep",
     "relmc_hl1_area_var_load", "relmc_hl1_area_var",
     "relmc_comm_unique_id", "relmc_comm_init", "relmc_comm_allreduce_acc", "relmc_comm_destroy", "relmc_comm_set_host_allreduce", "relmc_comm_info",
@@ -173,6 +173,9 @@ def load():
     L.relmc_hl1_maint_seq.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                       C.POINTER(_abi.Hl1SeqAcc), C.POINTER(_abi.Hl1SeqYear)]
     L.relmc_hl1_maint_seq.restype = C.c_int32
+    L.relmc_hl1_attr_seq.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                     C.POINTER(_abi.Hl1SeqAcc), C.POINTER(_abi.Hl1SeqYear), C.POINTER(_abi.Hl1AttrAcc), C.POINTER(_abi.Hl1AttrUnit)]
+    L.relmc_hl1_attr_seq.restype = C.c_int32
     L.relmc_hl1_ms_load.argtypes = [vp, C.c_int32, C.POINTER(_abi.Hl1MsUnit), C.c_int32, dp]
     L.relmc_hl1_ms_load.restype = C.c_int32
     L.relmc_hl1_ms_seq.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(_abi.Hl1MsAcc),

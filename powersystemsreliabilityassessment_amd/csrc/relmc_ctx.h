@@ -14,7 +14,7 @@
 //                        sequential chronology (relmc_hl1_seq), its loss events (relmc_hl1_seq_events) and its load sweep
 //                        (relmc_hl1_seq_sweep), three instantiations of the one kernel template of relmc_hl1_chain_kernels.h, and
 //                        the record reduction and unit check of every HL1 chronology track
-//   relmc_hl1_host.h     (a header, included by the ten HL1 units around it) what their host code shares: the chunk rule, the loop over a
+//   relmc_hl1_host.h     (a header, included by the eleven HL1 units around it) what their host code shares: the chunk rule, the loop over a
 //                        model's launches with the reduction of their year records (hl1_run_records), the argument and unit checks, and the one
 //                        copy of what the storage and weather-year tracks check and fill alike (storage fields, resource scales, pick,
 //                        weather_host, the two-row copies, relmc_hl1_storage_acc)
@@ -27,6 +27,8 @@
 //                        relmc_hl1_stress_seq, kernel in relmc_hl1_storage_kernels.h)
 //   relmc_maint.hip      planned maintenance on that chronology, up to 8 schedules on one fleet history (relmc_hl1_maint_load,
 //                        relmc_hl1_maint_seq; the kernel is the fourth model of relmc_hl1_chain_kernels.h's template)
+//   relmc_attr.hip       loss attribution on that chronology: every loss step charged to the units that are down (relmc_hl1_attr_seq,
+//                        kernels in relmc_hl1_attr_kernels.h)
 //   relmc_multistate.hip that chronology with three-state units (relmc_hl1_ms_load, relmc_hl1_ms_seq, kernel in relmc_multistate_kernels.h)
 //   relmc_plan.hip       the HL1 planning model's Monte Carlo (relmc_hl1_plan)
 //   relmc_area.hip       the HL1 multi-area chronology with tie-line transfers (relmc_hl1_area)
@@ -210,6 +212,9 @@ struct relmc_ctx {
     } hl1_events;
     // load sweep on that model (relmc_hl1_seq_sweep): per-level records; storage on that model (relmc_hl1_seq_storage): records of both rows
     Hl1Records hl1_sweep, hl1_storage;
+    // loss attribution on that model (relmc_hl1_attr_seq): year records, and grow-only the chains' unit records of one launch
+    // unit[chain][ngen][4] with the partials of their reduction upart[slice][ngen][8]
+    struct Hl1Attr { Hl1Records rec; DevBuf<double> unit, upart; } hl1_attr;
     // maintenance schedules of relmc_hl1_maint_load (relmc_hl1_maint_seq runs the fleet of hl1_seq under them): the mask table
     // tab[width][nhours][4] (bit k & 31 of word k >> 5 = unit k on maintenance; width = n_schedules rounded up to the kernel's 1, 2, 4 or 8,
     // the added schedules empty), the ngen and nhours it was built for, per-schedule records

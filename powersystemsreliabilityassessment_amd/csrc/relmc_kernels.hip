@@ -97,6 +97,30 @@ constexpr bool kFillBySlot = false;
 #else
 constexpr bool kFillBySlot = true;
 #endif
+// Test first, assemble after, on the trips that can end (bit m = MODE m; 16-lane tile).  The norms form of the front half (kNormSplitMask) runs
+// on the trips where some row's first stage holds, and the last of them only finds its rows converged: the barrier terms, the second record
+// halves, the stash, most of the gather and the KKT blocks it built are never read.  With the bit set that form runs in two stages.  Stage 1
+// computes what the test reads -- h, Lx = G + b (mu+ - mu-), the bus sums of Lx and the balance, none of which needs a reciprocal -- from
+// record halves {Lx, F} (one b128 store per line, one b128 load per list entry), and takes the test.  Stage 2, under a wave-uniform
+// __any(iterating) and per lane under `iterating`, does the rest: the barrier terms, the record halves {g, Lx + q}, the stash, a second walk of
+// the lists for md, nq, E, ssum, the blocks.  Only the balance of each bus slot is carried across the test.  Every stored bit is the one-stage
+// form's: each accumulator was a register of its own and keeps its chain over the same entries in the same order (md, Lx, nq, bal, E, ssum
+// never fed one another), every other expression is the same text on the same operands, and x, z, mu, gamma do not change between the stages;
+// a row that ends leaves its workspace unassembled, which nothing reads (the output phase takes registers and Lam).  The records are regrouped
+// in this form only: a record is written and consumed inside one front half, so the two forms never see each other's layout.  Taken only where
+// a static shape compiles the dimensions in (the conditions of kZeroBySlot and kFillBySlot together), on the sparse solve of the fused path:
+// every run-time-shape instantiation keeps the one-stage text byte for byte.  The bit is tested on the mapped mode, so bit 0 covers MODE 5 (the
+// order-calibration probe is MODE 0 under a name of its own) should it ever get a static shape.  Stage 1 and stage 2 MIRROR the one-stage pieces
+// of front_half (evaluation, injection loop, list walk, block stores): a change of arithmetic there is made in both, and
+// tests/test_test_first.py (bytes against the interpreter, which runs the one-stage text) is what shows a copy that was missed.  In
+// RELMC_PHASE_TIMING builds the two-stage form passes PT_MARK(1) and PT_MARK(2) twice: stage 2's evaluation is charged to phase 2 (assembly)
+// and the test to phase 2 as well, so the phase shares of DESIGN.md 3.0 are those of the one-stage form.  Measurements: profiles/test_first/README.md.
+// -DRELMC_TEST_AFTER (ablation): the one-stage form on every trip again.
+#ifdef RELMC_TEST_AFTER
+constexpr int kTestFirstMask = 0;
+#else
+constexpr int kTestFirstMask = 0x01;
+#endif
 // the one compare a pass spends on its descriptor: field 0 == field 3 (updates, back substitution), fields 2, 3 non-zero (inversion)
 #define PASS_IDLE(d) (((d).x & 0xffffu) == ((d).y >> 16))
 #define PASS_IDLE_INV(d) ((d).y != 0u)
@@ -157,6 +181,8 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
     constexpr bool ZSLOT = kZeroBySlot && (SH::kMask & SH::grp_nl) != 0 && (SH::kMask & SH::grp_ninj) != 0;   // zero records by the slot lanes behind the last line / injection (above)
     constexpr bool FSLOT = kFillBySlot && !DENSE && (SH::kMask & SH::grp_nzero_res) != 0 && (SH::kMask & SH::grp_nfill_bus) != 0;   // fill blocks cleared by the spare lanes of the block stores (above)
     constexpr bool FBUS = FSLOT && SH::nfill_bus > 0;            // ... the bus slots' spare lanes among them
+    constexpr bool TFIRST = TL::RW == 16 && ((kTestFirstMask >> MODE) & 1) != 0 && NSPLIT && !DENSE && (SH::kMask & SH::grp_nl) != 0 && (SH::kMask & SH::grp_ninj) != 0 &&
+                            (SH::kMask & SH::grp_nzero_res) != 0 && (SH::kMask & SH::grp_nfill_bus) != 0;   // norms form of the front half: test first, assemble after (above)
     constexpr int RW = TL::RW, BS = TL::BS, LS = TL::LS, IS = TL::IS, NBT = TL::NBT, WPB = TL::WPB, SPW = TL::SPW, OW = TL::OW;
     using DevCase = DevCaseT<TL>;
     using Partial = PartialT<TL>;
@@ -833,7 +859,11 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 // ---- evaluate h, Lx, barrier terms; scatter to LDS; convergence norms -------------
                 double mx_gh = -DINF, mx_x = 0.0, mx_z = 0.0, mx_lx = 0.0, mx_lammu = 0.0;
                 bool nanx = false;
+                // TFIRST: the norms form in two stages (above) -- this one forms what the test reads, the assembly follows the test
+                constexpr bool TF = TFIRST && NORMS;
+                static_assert(!TFIRST || (!PFSITE(1) && !PFSITE(2)), "the two-stage form reads its tables where it uses them");
                 double gown[LS];
+                if constexpr (!TF) { // (the one-stage pieces stand at this level so that their locals do: stage 2 uses them; TF's stages 1 and 2 below mirror them)
 #pragma unroll
                 for (int s = 0; s < LS; ++s) {
                     const int l = RW * s + rlane;
@@ -860,6 +890,8 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                     if (ZSLOT ? l <= nlp : l < nlp) { st2(LR + 4 * l, g, lx); st2(LR + 4 * l + 2, lx + q, LFv[s]); }
                     SLOT_FENCE();
                 }
+                }
+                if constexpr (!TF) {
 #pragma unroll
                 for (int s = 0; s < IS; ++s) {
                     const int j = RW * s + rlane;
@@ -895,12 +927,13 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                     st2(Stash + 2 * RW * s, invD, npd);
                     SLOT_FENCE();
                 }
+                }
                 PT_MARK(1)
                 // the all-zero dummies that unused gather slots point to: by lane 0 where no slot lane stands behind the last element (a full tile)
-                if (rlane == 0) {
+                if constexpr (!TF) { if (rlane == 0) {
                     if (!ZSLOT || nlp >= LS * RW) { st2(LR + 4 * nlp, 0.0, 0.0); st2(LR + 4 * nlp + 2, 0.0, 0.0); }
                     if (!ZSLOT || nip >= IS * RW) IR[nip] = 0.0;
-                }
+                } }
                 // ---- assemble: gather everything the KKT blocks need into registers ... -------------
                 uint32_t lblk_pf[LS]; uint32_t zo_pf = 0;
                 if constexpr (PFSITE(1)) {
@@ -914,7 +947,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                     for (int t = 0; t < BS; ++t) { const int bq = vb[t] < nb ? vb[t] : 0; pl_pf[t] = PLIST(t, bq); pj_pf[t] = JLIST(t, bq); }
                 }
                 double vown[LS];
-                {   // the partner's g of every slot in one batch of loads (the all-zero record when there is none) instead of one LDS round trip per
+                if constexpr (!TF) {   // the partner's g of every slot in one batch of loads (the all-zero record when there is none) instead of one LDS round trip per
                     // owner slot, each in a branch of its own (round 3: -1.7 % / -2.3 % kernel time on RTS-24 / RTS-96, bit-identical)
                     double gp[LS];
 #pragma unroll
@@ -923,6 +956,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                     for (int s = 0; s < LS; ++s) vown[s] = (((linfo[s] >> 24) & LF_OWNER) && !L_PIN(s)) ? -(gown[s] + gp[s]) : 0.0;
                 }
                 double d00[BS], d11[BS], r0[BS], r1[BS];
+                if constexpr (!TF) {
 #pragma unroll
                 for (int t = 0; t < BS; ++t) {
                     const int bi = vb[t];
@@ -978,6 +1012,82 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                         if constexpr (!NSPLIT) { mx_x = vmax(mx_x, __builtin_fabs(bth[t])); nanx = nanx || bth[t] != bth[t]; }
                     }
                 }
+                }
+                // TF, stage 1 (it stands behind the one-stage pieces it replaces, which are not compiled with it)
+                if constexpr (TFIRST) { if constexpr (TF) {      // (TFIRST by itself: decided with the kernel's arguments, so that no other instantiation's closure sees this text)
+#pragma unroll
+                    for (int s = 0; s < LS; ++s) {
+                        const int l = RW * s + rlane;
+                        double lx = LGv[s];
+                        if (L_ACT(s)) {
+                            const double b = lb(s), rr = lr(s);
+                            const double hp = LFv[s] - rr, hm = -LFv[s] - rr;
+                            lx = __builtin_fma(b, lmup[s] - lmum[s], lx);
+                            mx_gh = vmax(mx_gh, vmax(hp, hm));
+                            mx_z = vmax(mx_z, vmax(lzp[s], lzm[s]));
+                            mx_lammu = vmax(mx_lammu, vmax(lmup[s], lmum[s]));
+                        }
+                        // record half {lx, F}; ZSLOT: the lane behind the last line writes the zero record's (below)
+                        if (ZSLOT ? l <= nlp : l < nlp) st2(LR + 4 * l, lx, LFv[s]);
+                        SLOT_FENCE();
+                    }
+#pragma unroll
+                    for (int s = 0; s < IS; ++s) {
+                        const int j = RW * s + rlane;
+                        const double pv = ip[s];
+                        if (I_BOX(s)) {
+                            const d2 hl = IHL(s, j);
+                            const double hp = pv - hl.x, hm = ILOV(s, hl.y) - pv;
+                            const double lxp = ICOST(s, j) - Lam[iinfo[s] & 0xff] + (imup[s] - imum[s]);
+                            mx_lx = vmax(mx_lx, __builtin_fabs(lxp));
+                            mx_gh = vmax(mx_gh, vmax(hp, hm));
+                            mx_z = vmax(mx_z, vmax(izp[s], izm[s]));
+                            mx_lammu = vmax(mx_lammu, vmax(imup[s], imum[s]));
+                        }
+                        if (ZSLOT ? j <= nip : j < nip) IR[j] = pv;
+                        SLOT_FENCE();
+                    }
+                    PT_MARK(1)
+                    if (rlane == 0) {            // the all-zero dummies of a full tile, both record halves (stage 2 leaves them alone)
+                        if (!ZSLOT || nlp >= LS * RW) { st2(LR + 4 * nlp, 0.0, 0.0); st2(LR + 4 * nlp + 2, 0.0, 0.0); }
+                        if (!ZSLOT || nip >= IS * RW) IR[nip] = 0.0;
+                    }
+#pragma unroll
+                    for (int t = 0; t < BS; ++t) {
+                        const int bi = vb[t];
+                        r1[t] = 0.0;
+                        if (bi < nb) {
+                            double lx = 0.0, bal = 0.0;
+                            const unsigned long long pl = PLIST(t, bi), pj = JLIST(t, bi);
+#pragma unroll
+                            for (int e = 0; e < DEGMAX; e += 2) {
+                                if (e >= (t == 0 ? maxdeg0 : maxdeg1)) break;
+                                const uint32_t ent0 = (uint32_t)(pl >> (8 * e)) & 0xffu, ent1 = (uint32_t)(pl >> (8 * e + 8)) & 0xffu;
+                                const int l0 = (int)(ent0 & 0x7f), l1 = (int)(ent1 & 0x7f);
+                                const double sg0 = (ent0 & 0x80) ? -1.0 : 1.0, sg1 = (ent1 & 0x80) ? -1.0 : 1.0;
+                                const d2 ra0 = ld2(LR + 4 * l0), ra1 = ld2(LR + 4 * l1);
+                                lx = __builtin_fma(sg0, ra0.x, lx);
+                                bal = __builtin_fma(sg0, ra0.y, bal);
+                                lx = __builtin_fma(sg1, ra1.x, lx);
+                                bal = __builtin_fma(sg1, ra1.y, bal);
+                            }
+#pragma unroll
+                            for (int e = 0; e < BINJMAX; e += 2) {
+                                if (e >= (t == 0 ? maxinj0 : maxinj1)) break;
+                                const int j0 = (int)((uint32_t)(pj >> (8 * e)) & 0xffu), j1 = (int)((uint32_t)(pj >> (8 * e + 8)) & 0xffu);
+                                const double p0 = IR[j0], p1 = IR[j1];
+                                bal -= p0;
+                                bal -= p1;
+                            }
+                            if (B_PIN(t)) mx_lammu = vmax(mx_lammu, __builtin_fabs(lx)); else mx_lx = vmax(mx_lx, __builtin_fabs(lx));
+                            if (!B_DROP(t)) {
+                                mx_gh = vmax(mx_gh, __builtin_fabs(bal));
+                                mx_lammu = vmax(mx_lammu, __builtin_fabs(bla[t]));
+                            }
+                            r1[t] = bal;                // all that stage 2 takes from here: it forms -bal - ssum
+                        }
+                    }
+                } }
                 double o_ct = 0.0, o_cc = 0.0, o_am = 0.0;
                 if constexpr (NSPLIT && PFSITE(7)) o_am = A_(7, alpha_min);     // the one option the test still reads: requested ahead of the block stores
                 // ---- ... then overwrite the workspace (same LDS words as the evaluation arrays) ------
@@ -1009,7 +1119,7 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                         }
                     }
                     __threadfence_block();
-                } else {
+                } else if constexpr (!TF) {
 #pragma unroll
                 for (int s = 0; s < LS; ++s) {
                     // FSLOT: every lane with a target stores -- an owner line's lane its block, a spare lane exact zeros into a fill block
@@ -1085,6 +1195,120 @@ __global__ void __launch_bounds__(64 * TL::WPB, kMinWaves) relmc_eval_kernel(con
                 if (conv) { status = 0; iterating = false; }
                 else if (it > 0 && (xnan || alphap < (PFSITE(7) ? o_am : A_(7, alpha_min)) || alphad < (PFSITE(7) ? o_am : A_(7, alpha_min)) || gamma < eps || gamma > 1.0 / eps)) { status = 2; iterating = false; }
                 else if (it >= a.max_it) { status = 1; iterating = false; }
+                // TF, stage 2: the assembly, for the rows that go on (none on a group's last trip).  The same expressions as the one-stage form's on
+                // the same x, z, mu, gamma; the record halves written here are {g, lx + q}, the balance is stage 1's.
+                if constexpr (TFIRST) { if constexpr (TF) { if (__any(iterating)) { if (iterating) {
+#pragma unroll
+                    for (int s = 0; s < LS; ++s) {
+                        const int l = RW * s + rlane;
+                        double g = 0.0, q = 0.0;
+                        double lx = LGv[s];
+                        if (L_ACT(s)) {
+                            const double b = lb(s), rr = lr(s);
+                            const double hp = LFv[s] - rr, hm = -LFv[s] - rr;
+                            double rzp, rzm;
+                            if constexpr (LSHARE) { lzr[s] = frcp(lzp[s] * lzm[s]); rzp = lzm[s] * lzr[s]; rzm = lzp[s] * lzr[s]; }
+                            else frcp_pair<PAIRSITE(0)>(lzp[s], lzm[s], rzp, rzm);
+                            g = b * b * (lmup[s] * rzp + lmum[s] * rzm);
+                            lx = __builtin_fma(b, lmup[s] - lmum[s], lx);
+                            q = b * ((lmup[s] * hp + gamma) * rzp - (lmum[s] * hm + gamma) * rzm);
+                        }
+                        gown[s] = g;
+                        if (ZSLOT ? l <= nlp : l < nlp) st2(LR + 4 * l + 2, g, lx + q);      // ZSLOT: zeros from the lane behind the last line
+                        SLOT_FENCE();
+                    }
+#pragma unroll
+                    for (int s = 0; s < IS; ++s) {
+                        const int j = RW * s + rlane;
+                        double invD = 0.0, npd = 0.0;
+                        const double pv = ip[s];
+                        if (I_BOX(s)) {
+                            const d2 hl = IHL(s, j);
+                            const double hp = pv - hl.x, hm = ILOV(s, hl.y) - pv;
+                            const double lxp = ICOST(s, j) - Lam[iinfo[s] & 0xff] + (imup[s] - imum[s]);
+                            if constexpr ((RW == 16 && kInjNform) || (RW == 64 && kInjNformWide)) {
+                                const double N = __builtin_fma(imup[s], izm[s], imum[s] * izp[s]);
+                                const double rN = frcp(N), zz = izp[s] * izm[s];
+                                invD = zz * rN;
+                                npd = __builtin_fma(lxp, zz, (imup[s] * hp + gamma) * izm[s] - (imum[s] * hm + gamma) * izp[s]) * rN;
+                            } else {
+                                double rzp, rzm; frcp_pair<PAIRSITE(1)>(izp[s], izm[s], rzp, rzm);
+                                const double D = imup[s] * rzp + imum[s] * rzm;
+                                const double np = lxp + (imup[s] * hp + gamma) * rzp - (imum[s] * hm + gamma) * rzm;
+                                invD = frcp(D); npd = np * invD;
+                            }
+                        }
+                        st2(Stash + 2 * RW * s, invD, npd);
+                        SLOT_FENCE();
+                    }
+                    {
+                        double gp[LS];
+#pragma unroll
+                        for (int s = 0; s < LS; ++s) gp[s] = LR[4 * (lpart[s] >= 0 ? lpart[s] : nlp) + 2];
+#pragma unroll
+                        for (int s = 0; s < LS; ++s) vown[s] = (((linfo[s] >> 24) & LF_OWNER) && !L_PIN(s)) ? -(gown[s] + gp[s]) : 0.0;
+                    }
+#pragma unroll
+                    for (int t = 0; t < BS; ++t) {
+                        const int bi = vb[t];
+                        const double bal = r1[t];        // stage 1's
+                        d00[t] = 0; d11[t] = 0; r0[t] = 0; r1[t] = 0;
+                        if (bi < nb) {
+                            double md = 0.0, nq_ = 0.0, E = 0.0, ssum = 0.0;
+                            const unsigned long long pl = PLIST(t, bi), pj = JLIST(t, bi);
+#pragma unroll
+                            for (int e = 0; e < DEGMAX; e += 2) {
+                                if (e >= (t == 0 ? maxdeg0 : maxdeg1)) break;
+                                const uint32_t ent0 = (uint32_t)(pl >> (8 * e)) & 0xffu, ent1 = (uint32_t)(pl >> (8 * e + 8)) & 0xffu;
+                                const int l0 = (int)(ent0 & 0x7f), l1 = (int)(ent1 & 0x7f);
+                                const double sg0 = (ent0 & 0x80) ? -1.0 : 1.0, sg1 = (ent1 & 0x80) ? -1.0 : 1.0;
+                                const d2 rb0 = ld2(LR + 4 * l0 + 2), rb1 = ld2(LR + 4 * l1 + 2);
+                                md += rb0.x;
+                                nq_ = __builtin_fma(sg0, rb0.y, nq_);
+                                md += rb1.x;
+                                nq_ = __builtin_fma(sg1, rb1.y, nq_);
+                            }
+#pragma unroll
+                            for (int e = 0; e < BINJMAX; e += 2) {
+                                if (e >= (t == 0 ? maxinj0 : maxinj1)) break;
+                                const int j0 = (int)((uint32_t)(pj >> (8 * e)) & 0xffu), j1 = (int)((uint32_t)(pj >> (8 * e + 8)) & 0xffu);
+                                const d2 sh0 = ld2(StashJ + 2 * j0), sh1 = ld2(StashJ + 2 * j1);
+                                E += sh0.x; ssum += sh0.y;
+                                E += sh1.x; ssum += sh1.y;
+                            }
+                            if (B_PIN(t)) { d00[t] = 1.0; r0[t] = 0.0; } else { d00[t] = md; r0[t] = -nq_; }
+                            if (B_DROP(t)) { d11[t] = -1.0; r1[t] = 0.0; } else { d11[t] = -E; r1[t] = -bal - ssum; }
+                        }
+                    }
+                    RELOAD_FENCE();
+                    // the block stores of the one-stage form (above), its comments with them; site 1 of kPfMask is off here
+#pragma unroll
+                    for (int s = 0; s < LS; ++s) {
+                        const uint32_t lbf = (uint32_t)C.l_blk[RW * s + rlane];
+                        if (FSLOT ? (SHAPE(nidle_line, 1) == 0 || lbf != 0xffffu) : ((linfo[s] >> 24) & LF_OWNER) != 0) {
+                            const double c1 = L_C1Z(s) ? 0.0 : cBv[s], c2 = L_C2Z(s) ? 0.0 : cBv[s];
+                            double* blk = W + lbf;
+                            st2(blk, vown[s], c1); st2(blk + 2, c2, 0.0);
+                        }
+                    }
+                    const int nzloop = FSLOT ? SHAPE(nzero_res, 0) : nzero;
+                    for (int z = rlane; z < nzloop; z += RW) { double* blk = W + C.zero_off[z]; st2(blk, 0.0, 0.0); st2(blk + 2, 0.0, 0.0); }
+#pragma unroll
+                    for (int t = 0; t < BS; ++t) {
+                        const int bi = vb[t];
+                        if constexpr (FBUS) {
+                            if ((t == 0 ? SHAPE(nidle_bus0, 1) : SHAPE(nidle_bus1, 1)) == 0 || bi != 0xffff) {
+                                st2(W + 4 * bi, d00[t], cBd[t]); st2(W + 4 * bi + 2, cBd[t], d11[t]);
+                                if (bi < nb) st2(W + off_rhs + 2 * bi, r0[t], r1[t]);
+                            }
+                        } else
+                        if (bi < nb) {
+                            st2(W + 4 * bi, d00[t], cBd[t]); st2(W + 4 * bi + 2, cBd[t], d11[t]);
+                            st2(W + off_rhs + 2 * bi, r0[t], r1[t]);
+                        }
+                    }
+                    PT_MARK(2)
+                } } } }
             };
             if (iterating) {
                 if (need_norms) front_half(std::true_type{}); else front_half(std::false_type{});

@@ -990,6 +990,52 @@ int32_t relmc_seq_years(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int3
                         const relmc_solver_opts* opts, double curtail_threshold, relmc_seq_year* years_out,
                         relmc_acc* acc_out);
 
+/* ---- loss events of the sequential HL2 track: how often failures occur and how long they last (seqMain.m:15-16) ---- */
+/* The years are relmc_seq_years' under the same arguments, word for word: same chronology, same hourly OPFs, same system curtailment
+ * curt[h] per hour (0 on an hour without an outage and on an hour the pre-screen certifies).  System level only: the nodal split of a
+ * curtailment is not a well-conditioned function of the data, so a per-bus threshold test has no defined answer.
+ *   loss hour    an hour with curt[h] > curtail_threshold (strict, seqMain.m:140)
+ *   loss event   a maximal run of consecutive loss hours inside one simulated year.  Years are independent and start all-up, and hour 0
+ *                counts as a start (calnlc.m).  A run that reaches the year's last hour ends there and is flagged censored; it is an
+ *                event like any other in every other field.
+ * Per event: year relative to first_year, start_hour 0-based, duration in hours, energy_mwh = the sum of curt over its hours added left
+ * to right in hour order, peak_mw the largest of them; onset = the components (bit k of word k / 32) that are down in the start hour and
+ * were up in the hour before (in hour 0: every component that is down); involved = the OR of the down masks over the event's hours.
+ * An event with an empty onset started without a new outage (a load rise) and is counted in load_onset_events.
+ * So the events of a year number its nlc, their durations sum to its dlc, and their energies sum to at most its ens, with equality
+ * iff no hour of the year has 0 < curt <= curtail_threshold. */
+typedef struct {
+    int32_t year;             /* relative to first_year */
+    int32_t start_hour;       /* 0-based */
+    int32_t duration;         /* hours */
+    int32_t censored;         /* 1 if the run reaches the year's last hour */
+    double energy_mwh, peak_mw;
+    uint32_t onset[RELMC_MAX_COMP / 32];
+    uint32_t involved[RELMC_MAX_COMP / 32];
+} relmc_seq_event;
+typedef struct {
+    int64_t years, events, censored, load_onset_events, sum_dur, sum_dur2, max_dur;   /* years = simulated years; sums and maxima over the events */
+    double sum_energy, sum_energy2, max_energy, max_peak;
+    int64_t onset_events[RELMC_MAX_COMP];       /* events component k initiated (bit k of onset) */
+    int64_t involved_events[RELMC_MAX_COMP];    /* events component k was down in (bit k of involved) */
+    double onset_energy[RELMC_MAX_COMP];        /* MWh of the events it initiated, added in list order */
+    double involved_energy[RELMC_MAX_COMP];     /* MWh of the events it was down in, added in list order */
+} relmc_seq_event_acc;
+/* years [first_year, first_year + n_years) of the chronology loaded by relmc_seq_load (RELMC_ERR_NO_CASE before that call).
+ *   years_out, acc_out   as relmc_seq_years with the same arguments, byte for byte (one body serves both entries)
+ *   ev_acc               required
+ *   dur_hist_host        optional [n_dur_bins], 1 <= n_dur_bins <= 4096 when given (else RELMC_ERR_INVALID): dur_hist_host[d - 1] = events
+ *                        with duration d for d < n_dur_bins, the last bin counts durations >= n_dur_bins; overwritten with this call's counts
+ *   events_host          optional [events_cap], events_cap >= 0 (else RELMC_ERR_INVALID): the first min(ev_acc->events, events_cap) events
+ *                        in (year, start_hour) order; ev_acc->events is always the true count, so a caller sees that its buffer was short
+ * n_years == 0 zeroes the outputs.  Every output depends on (seed, year, options, data) only: a repeated call is bitwise identical;
+ * splitting a year range into calls gives lists that concatenate (with `year` rebased), integer fields and histograms that add exactly
+ * and maxima that combine by max; the floating-point sums are taken in a fixed order and agree to rounding across a split.
+ * relmc_last_kernel_ms covers relmc_seq_years' kernels and the event kernels.  relmc_seq_run is unchanged and has no event output. */
+int32_t relmc_seq_events(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int32_t n_years, const relmc_solver_opts* opts,
+                         double curtail_threshold, relmc_seq_year* years_out, relmc_acc* acc_out, relmc_seq_event_acc* ev_acc,
+                         int32_t n_dur_bins, int64_t* dur_hist_host, int64_t events_cap, relmc_seq_event* events_host);
+
 /* relmc_seq_run <- the whole yearly loop of seqMain.m:85-199 (CoV stop at :194) and its post-processing :211-249, below the C ABI like
  * relmc_nsq_run.  With a communicator of more than one rank in the context (relmc_comm_init / relmc_comm_set_host_allreduce) it IS the
  * multi-rank loop: the years of every batch shard contiguously over the ranks, the annual triples are all-gathered in year order, every rank

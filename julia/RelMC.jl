@@ -393,6 +393,40 @@ function seq_years(eng::Engine, seed::Integer, first_year::Integer, n_years::Int
     return yrs, acc
 end
 
+"relmc_seq_event / relmc_seq_event_acc (include/relmc.h); tests/test_seq_events_host.py compares the fields with the C compiler's layout"
+struct SeqEvent
+    year::Int32; start_hour::Int32; duration::Int32; censored::Int32
+    energy_mwh::Cdouble; peak_mw::Cdouble
+    onset::NTuple{8,UInt32}; involved::NTuple{8,UInt32}
+end
+mutable struct SeqEventAcc
+    years::Int64; events::Int64; censored::Int64; load_onset_events::Int64; sum_dur::Int64; sum_dur2::Int64; max_dur::Int64
+    sum_energy::Cdouble; sum_energy2::Cdouble; max_energy::Cdouble; max_peak::Cdouble
+    onset_events::NTuple{256,Int64}; involved_events::NTuple{256,Int64}
+    onset_energy::NTuple{256,Cdouble}; involved_energy::NTuple{256,Cdouble}
+    SeqEventAcc() = new()
+end
+
+"""
+Loss events of `seq_years`' years (same arguments, same years byte for byte): a maximal run of consecutive hours with system curtailment
+above the threshold inside one simulated year, with its duration, energy, peak and the outages that set it off (relmc_seq_events).
+Returns the years, both accumulators, the duration histogram (`duration_bins` bins, the last one counts that many hours or more) and the
+first `max_events` events in (year, start_hour) order.
+"""
+function seq_events(eng::Engine, seed::Integer, first_year::Integer, n_years::Integer, mpopt::SolverOpts=mpoption(); curtail_threshold=0.01,
+                    duration_bins::Integer=168, max_events::Integer=0)
+    (1 <= duration_bins <= 4096 && max_events >= 0 && n_years >= 0) ||
+        throw(ArgumentError("duration_bins must lie in 1:4096, max_events and n_years must not be negative"))
+    yrs = Vector{SeqYear}(undef, n_years); acc = Acc(); ev_acc = SeqEventAcc()
+    hist = zeros(Int64, duration_bins); evs = Vector{SeqEvent}(undef, max_events)
+    check(ccall((:relmc_seq_events, LIB), Int32,
+                (Ptr{Cvoid}, UInt64, UInt64, Int32, Ref{SolverOpts}, Cdouble, Ptr{SeqYear}, Ref{Acc}, Ref{SeqEventAcc}, Int32, Ptr{Int64}, Int64, Ptr{SeqEvent}),
+                eng.h, seed, first_year, n_years, mpopt, curtail_threshold, yrs, acc, ev_acc, duration_bins, hist, max_events, evs), eng.h, "relmc_seq_events")
+    n = ev_acc.events
+    return (years=yrs, acc=acc, ev_acc=ev_acc, lolf_occ_yr=n_years > 0 ? n / n_years : NaN, mean_duration_hours=n > 0 ? ev_acc.sum_dur / n : NaN,
+            mean_energy_mwh=n > 0 ? ev_acc.sum_energy / n : NaN, duration_hist=hist, events=evs[1:min(n, max_events)])
+end
+
 "relmc_seq_opts (include/relmc.h): the options of the whole seqMain loop"
 struct SeqOpts
     cov_threshold::Cdouble; max_years::Int32; batch_years::Int32; seed::UInt64; curtail_threshold::Cdouble

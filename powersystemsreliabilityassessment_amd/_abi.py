@@ -119,6 +119,20 @@ class SeqYear(C.Structure):
     _fields_ = [("ens", C.c_double), ("dlc", C.c_double), ("nlc", C.c_double), ("n_contingency", C.c_int64)]
 
 
+class SeqEvent(C.Structure):              # relmc_seq_event
+    _fields_ = [("year", C.c_int32), ("start_hour", C.c_int32), ("duration", C.c_int32), ("censored", C.c_int32),
+                ("energy_mwh", C.c_double), ("peak_mw", C.c_double),
+                ("onset", C.c_uint32 * (RELMC_MAX_COMP // 32)), ("involved", C.c_uint32 * (RELMC_MAX_COMP // 32))]
+
+
+class SeqEventAcc(C.Structure):           # relmc_seq_event_acc
+    _fields_ = [("years", C.c_int64), ("events", C.c_int64), ("censored", C.c_int64), ("load_onset_events", C.c_int64),
+                ("sum_dur", C.c_int64), ("sum_dur2", C.c_int64), ("max_dur", C.c_int64),
+                ("sum_energy", C.c_double), ("sum_energy2", C.c_double), ("max_energy", C.c_double), ("max_peak", C.c_double),
+                ("onset_events", C.c_int64 * RELMC_MAX_COMP), ("involved_events", C.c_int64 * RELMC_MAX_COMP),
+                ("onset_energy", C.c_double * RELMC_MAX_COMP), ("involved_energy", C.c_double * RELMC_MAX_COMP)]
+
+
 class Hl1SeqYear(C.Structure):            # relmc_hl1_seq_year
     _fields_ = [("lole", C.c_double), ("eue", C.c_double), ("lolf", C.c_double)]
 

@@ -29,7 +29,7 @@ EXPORTS = [
     "relmc_hl1_area_var_load", "relmc_hl1_area_var",
     "relmc_comm_unique_id", "relmc_comm_init", "relmc_comm_allreduce_acc", "relmc_comm_destroy", "relmc_comm_set_host_allreduce", "relmc_comm_info",
     "relmc_db_reset", "relmc_nsq_db_batch", "relmc_db_accumulate", "relmc_db_size", "relmc_db_export", "relmc_db_import",
-    "relmc_seq_load", "relmc_seq_mcsampling", "relmc_seq_mcsimulation", "relmc_seq_years", "relmc_retry_stats", "relmc_retry_overflow", "relmc_retry_dense_stats", "relmc_case_order",
+    "relmc_seq_load", "relmc_seq_mcsampling", "relmc_seq_mcsimulation", "relmc_seq_years", "relmc_seq_events", "relmc_retry_stats", "relmc_retry_overflow", "relmc_retry_dense_stats", "relmc_case_order",
     "relmc_case_order_hint", "relmc_tune_order",
     "relmc_comm_set_timeout", "relmc_comm_allreduce_f64", "relmc_comm_set_host_allreduce_f64", "relmc_device_pci_bus_id", "relmc_seq_opts_default", "relmc_seq_run",
     "relmc_is_ratios", "relmc_is_sampling", "relmc_is_sampling_dev", "relmc_nsq_is_accumulate", "relmc_is_acc_zero", "relmc_is_acc_merge", "relmc_nsq_is_indices",
@@ -289,6 +289,10 @@ def load():
         L.relmc_debug_tail_plan.restype = C.c_int32
         L.relmc_debug_tail_groups.argtypes = [vp, _abi.c_int64_p, i32p]
         L.relmc_debug_tail_groups.restype = C.c_int32
+    if hasattr(L, "relmc_debug_seq_events"):
+        L.relmc_debug_seq_events.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, _abi.c_uint32_p, C.c_double, C.POINTER(_abi.SeqEventAcc),
+                                             C.c_int32, _abi.c_int64_p, C.c_int64, C.POINTER(_abi.SeqEvent)]
+        L.relmc_debug_seq_events.restype = C.c_int32
     if hasattr(L, "relmc_dpp_probe"):
         L.relmc_dpp_probe.argtypes = [vp, dp, dp]
         L.relmc_dpp_probe.restype = C.c_int32

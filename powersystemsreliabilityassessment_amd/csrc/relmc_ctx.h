@@ -44,6 +44,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <string>
@@ -120,6 +121,12 @@ struct relmc_ctx {
         DevBuf<uint32_t> dm, counts, off;    // counts: [0, n) listed hours per year, [n, 2 n) contingency hours per year (pre-screen)
         DevBuf<uint16_t> hours; DevBuf<double> curt, year;
     } sq;
+    // loss events of that step (relmc_seq_events; relmc_debug_seq_events on caller-given hours): grow-only year counts / list offsets, the
+    // list, reduction partials, histogram, per-component arrays
+    struct SeqEvents {
+        DevBuf<long long> count, offset; DevBuf<relmc_seq_event> list; DevBuf<relmc::SeqEventPart> part; DevBuf<unsigned long long> hist;
+        DevBuf<relmc::SeqEventComp> comp;
+    } sq_events;
     std::vector<int32_t> order_hint;     // relmc_case_order_hint: primary elimination order of the next relmc_case_load (external bus numbers), empty = the rule
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -460,5 +467,20 @@ int screen_gather_keys(relmc_ctx* ctx, uint32_t n_surv, uint32_t* keys_out);    
 int screen_prepass_rows(relmc_ctx* ctx, int64_t first, int64_t n, uint32_t* n_surv);      // new database rows: certified ones filled in, the others listed
 int screen_seq_compact(relmc_ctx* ctx, const uint32_t* masks, int n_years, uint16_t* hours, uint32_t* counts, uint32_t* ncont);
 constexpr int64_t kScreenChunk = (int64_t)1 << 22;                   // samples per pre-pass of the fused path (its buffers: 4 OW + 5 bytes per sample)
+
+// ---- relmc_seq.hip ------------------------------------------------------------------------------------------------------------
+// relmc_seq_events' accumulator and histogram (optional) zeroed: what seq_events_device expects to be handed
+inline void seq_events_zero(relmc_seq_event_acc* ev_acc, int32_t n_dur_bins, int64_t* dur_hist_host)
+{
+    std::memset(ev_acc, 0, sizeof(*ev_acc));
+    if (dur_hist_host) std::memset(dur_hist_host, 0, sizeof(int64_t) * n_dur_bins);
+}
+// Loss events of device hours curt[n_years][hpy] with masks[n_years][hpy][mw] (relmc_seq_events behind its relmc_seq_years step;
+// relmc_debug_seq_events on uploaded hours): count -> offsets -> fill -> reduce, outputs as relmc_seq_events documents them (ev_acc->years
+// = n_years).  total_hint: the number of events if the caller knows it (the years' nlc), which saves the synchronisation that reads it
+// back; -1 = read it.  Adds the kernels' time to *ms.  The caller hands in zeroed outputs (seq_events_zero).
+int seq_events_device(relmc_ctx* ctx, const char* who, const double* curt, const uint32_t* masks, int n_years, int hpy, int mw, double threshold,
+                      int64_t total_hint, relmc_seq_event_acc* ev_acc, int32_t n_dur_bins, int64_t* dur_hist_host, int64_t events_cap,
+                      relmc_seq_event* events_host, double* ms);
 
 }  // namespace relmc_host

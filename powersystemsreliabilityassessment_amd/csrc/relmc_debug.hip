@@ -185,6 +185,35 @@ int32_t relmc_debug_tail_groups(const relmc_ctx* ctx, int64_t* launches_out, int
     return ctx->last_tail_groups;
 }
 
+// test hook: the event kernels of relmc_seq_events (count -> offsets -> fill -> reduce, seq_events_device of relmc_seq.hip) on caller-given
+// hours curt[n_years][hpy] and masks[n_years][hpy][mw] (mw 32-bit words per hour, bit k of word k / 32 = component k down) instead of a
+// relmc_seq_years step's.  Needs a context but no case.  hpy 1..65535 and mw 1..8, the chronology kernel's limits; the other arguments as
+// relmc_seq_events.
+int32_t relmc_debug_seq_events(relmc_ctx* ctx, int32_t n_years, int32_t hpy, int32_t mw, const double* curt_host, const uint32_t* masks_host,
+                               double curtail_threshold, relmc_seq_event_acc* ev_acc, int32_t n_dur_bins, int64_t* dur_hist_host, int64_t events_cap,
+                               relmc_seq_event* events_host)
+{
+    if (!ctx) return RELMC_ERR_INVALID;
+    if (n_years < 0 || hpy < 1 || hpy > 65535 || mw < 1 || mw > SEQ_EVENT_MW || !ev_acc || (n_years > 0 && (!curt_host || !masks_host)) ||
+        (dur_hist_host && (n_dur_bins < 1 || n_dur_bins > 4096)) || events_cap < 0)
+        return fail(ctx, RELMC_ERR_INVALID, "relmc_debug_seq_events: bad arguments");
+    seq_events_zero(ev_acc, n_dur_bins, dur_hist_host);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t nh = (size_t)n_years * hpy;
+    DevBuf<double> dc; DevBuf<uint32_t> dm;
+    if (nh > 0) {
+        HIP_TRY(ctx, dc.grow(nh));
+        HIP_TRY(ctx, dm.grow(nh * mw));
+        HIP_TRY(ctx, hipMemcpy(dc.get(), curt_host, sizeof(double) * nh, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(dm.get(), masks_host, sizeof(uint32_t) * nh * mw, hipMemcpyHostToDevice));
+    }
+    double ms = 0.0;
+    const int rc = seq_events_device(ctx, "relmc_debug_seq_events", dc.get(), dm.get(), n_years, hpy, mw, curtail_threshold, -1, ev_acc, n_dur_bins,
+                                     dur_hist_host, events_cap, events_host, &ms);
+    ctx->last_kernel_ms = ms;
+    return rc;
+}
+
 // diagnosis switches of the context (tests): "no_retry", "retry_dense_first", "nsq_no_stretch", "db_no_probe", "dynamic_shape", "static_tail",
 // "norms_always"; value 0 / 1.  static_tail may change between launches: the fused path then runs without the dynamic tail (tests/test_tail_paths.py).
 // no_retry must be set before relmc_case_load (the order calibration and the list arming must agree).  dynamic_shape may change between

@@ -267,6 +267,17 @@ struct Hl1EventRec {
     long long events, sum_dur, sum_dur2, max_dur, censored;
     double sum_energy, sum_energy2, max_energy, max_peak;
 };
+// Loss events of the sequential HL2 track (relmc_seq_events) in summary: one reduction slice's.  Integers add, maxima combine by max.
+struct SeqEventPart {
+    long long events, censored, load_onset, sum_dur, sum_dur2, max_dur;
+    double sum_energy, sum_energy2, max_energy, max_peak;
+};
+constexpr int SEQ_EVENT_MW = SEQ_NCOMPMAX / 32;   // mask words of an event record (relmc_seq_event::onset / involved)
+// the per-component arrays of relmc_seq_event_acc, in its order (copied to its tail as they stand)
+struct SeqEventComp {
+    long long onset_events[SEQ_NCOMPMAX], involved_events[SEQ_NCOMPMAX];
+    double onset_energy[SEQ_NCOMPMAX], involved_energy[SEQ_NCOMPMAX];
+};
 
 // HL1 planning model (relmc_hl1_plan): maintenance windows, ELU slots and Bernoulli thresholds, mirrored by include/relmc.h's contract
 constexpr int PLAN_MAX_ELU = 8;

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -10,6 +11,7 @@
 #include "relmc_hl1_host.h"
 #include "relmc_seq_kernels.h"
 #include "relmc_hl1_chain_kernels.h"
+#include "relmc_seq_event_kernels.h"
 
 namespace relmc_host {
 
@@ -63,6 +65,154 @@ int hl1_reduce_queue(relmc_ctx* ctx, const char* who, const double* rec, int64_t
     if (hipGetLastError() != hipSuccess) return fail(ctx, RELMC_ERR_HIP, std::string(who) + ": launch failed");
     part.resize((size_t)blocks * 6 * rows);
     HIP_TRY(ctx, hipMemcpyAsync(part.data(), dpart, sizeof(double) * part.size(), hipMemcpyDeviceToHost, ctx->stream));
+    return RELMC_OK;
+}
+
+// The body of relmc_seq_years (arguments checked by the entry): the step that relmc_seq_years and relmc_seq_events share.  It leaves the
+// years' per-hour curtailment in ctx->sq.curt and their masks in ctx->sq.dm, and the kernels' time in ctx->last_kernel_ms.
+int seq_years_step(relmc_ctx* ctx, const std::string& who, uint64_t seed, uint64_t first_year, int32_t n_years, const relmc_solver_opts* opts,
+                   double curtail_threshold, relmc_seq_year* years_out, relmc_acc* acc_out)
+{
+    relmc_acc_zero(acc_out);
+    if (n_years == 0) return RELMC_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const relmc_solver_opts o = solver_opts_or_default(opts);
+    const int hpy = ctx->hseq.hpy;
+    // the device buffers of a step live in the context and only ever grow
+    const size_t nh = (size_t)n_years * hpy, words = nh * (size_t)ctx->hseq.mw;
+    auto& Q = ctx->sq;
+    // counts: [0, n) listed hours per year, [n, 2 n) contingency hours per year (pre-screen), n = the years the buffer was made for
+    if (Q.dm.grow(words) != hipSuccess || Q.hours.grow(nh) != hipSuccess || Q.curt.grow(nh) != hipSuccess || Q.counts.grow(2 * (size_t)n_years) != hipSuccess ||
+        Q.off.grow((size_t)n_years + 1) != hipSuccess || Q.year.grow(3 * (size_t)n_years) != hipSuccess)
+        return fail(ctx, RELMC_ERR_HIP, who + ": device allocation failed");
+    uint32_t* const dm = Q.dm.get(); uint16_t* const dhours = Q.hours.get(); uint32_t* const dcounts = Q.counts.get(); uint32_t* const doff = Q.off.get();
+    double* const dcurt = Q.curt.get(); double* const dyear = Q.year.get();
+    int rc = seq_sample(ctx, seed, first_year, n_years, dm);
+    if (rc) return rc;
+    std::vector<uint32_t> counts(n_years), ncont(n_years), off(n_years + 1, 0);
+    bool ok = hipMemsetAsync(dcurt, 0, nh * sizeof(double), ctx->stream) == hipSuccess;
+    // screen = 1 (relmc_screen.hip): the contingency hours are counted as before, but only the ones the zero-curtailment certificate does not cover
+    // -- at the hour's own load factor -- are listed for the interior point; a covered hour's curtailment stays the 0 it was set to above
+    const bool screen = screen_active(ctx, o);
+    uint32_t* const dncont = dcounts + Q.counts.size() / 2;
+    if (screen) ok = ok && screen_seq_compact(ctx, dm, n_years, dhours, dcounts, dncont) == RELMC_OK;
+    else hipLaunchKernelGGL(relmc_seq_compact_kernel, dim3(n_years), dim3(256), 0, ctx->stream, dm, hpy, ctx->hseq.mw, dhours, dcounts);
+    ok = ok && hipGetLastError() == hipSuccess && hipMemcpyAsync(counts.data(), dcounts, sizeof(uint32_t) * n_years, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+         (!screen || hipMemcpyAsync(ncont.data(), dncont, sizeof(uint32_t) * n_years, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess) &&
+         hipStreamSynchronize(ctx->stream) == hipSuccess;
+    if (!ok) return fail(ctx, RELMC_ERR_HIP, who + ": compaction failed");
+    int64_t certified = 0;
+    for (int y = 0; y < n_years; ++y) {
+        off[y + 1] = off[y] + counts[y];
+        years_out[y].n_contingency = screen ? ncont[y] : counts[y];
+        if (screen) certified += (int64_t)ncont[y] - (int64_t)counts[y];
+    }
+    const int64_t nlp = off[n_years];
+    double ms = 0.0;
+    if (screen) { float t = 0.f; if (hipEventElapsedTime(&t, ctx->screen_ev0, ctx->screen_ev1) == hipSuccess) ms += t; }      // the certificate's pre-pass (the stream was synchronised above)
+    if (nlp > 0) {
+        if (hipMemcpyAsync(doff, off.data(), sizeof(uint32_t) * (n_years + 1), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(ctx, RELMC_ERR_HIP, who + ": H2D failed");
+        EvalArgs a = make_args(o);
+        a.fail_threshold = curtail_threshold;
+        a.n = nlp; a.seq_masks = dm; a.seq_offsets = doff; a.seq_hours = dhours; a.load_factors = ctx->dlf.get(); a.curt = dcurt;
+        a.seq_nyears = n_years; a.seq_hpy = hpy;
+        Collected c;
+        rc = eval_collect(ctx, who.c_str(), 2, a, 0, a.n, acc_out, c);
+        if (rc) return rc;
+        ms += c.ms;
+        RetryOut ro;                                                   // hours the primary elimination order did not converge on
+        const ScaleFn scale = [&](unsigned long long u) { return ctx->hlf[(size_t)(u % (unsigned long long)hpy)]; };
+        rc = fail_retry(ctx, o, curtail_threshold, &scale, ro, &ms, c.known());
+        if (rc) return rc;
+        acc_add_retry(acc_out, ro, ctx->ncomp, curtail_threshold);
+        for (size_t r = 0; r < ro.size(); ++r) {
+            const RetryUnit u = ro[r];
+            if (hipMemcpy(dcurt + u.unit, &u.dns, sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(ctx, RELMC_ERR_HIP, who + ": H2D failed");
+        }
+    }
+    acc_out->n += certified; acc_out->n_screened += certified;
+    hipLaunchKernelGGL(relmc_seq_annual_kernel, dim3(n_years), dim3(256), 0, ctx->stream, dcurt, hpy, curtail_threshold, dyear);
+    std::vector<double> yr((size_t)3 * n_years);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(yr.data(), dyear, sizeof(double) * 3 * n_years, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(ctx, RELMC_ERR_HIP, who + ": annual indices failed");
+    for (int y = 0; y < n_years; ++y) { years_out[y].ens = yr[3 * y]; years_out[y].dlc = yr[3 * y + 1]; years_out[y].nlc = yr[3 * y + 2]; }
+    ctx->last_kernel_ms = ms;
+    return RELMC_OK;
+}
+
+int seq_events_device(relmc_ctx* ctx, const char* who_, const double* curt, const uint32_t* masks, int n_years, int hpy, int mw, double threshold,
+                      int64_t total_hint, relmc_seq_event_acc* ev_acc, int32_t n_dur_bins, int64_t* dur_hist_host, int64_t events_cap,
+                      relmc_seq_event* events_host, double* ms)
+{
+    static_assert(SEQ_NCOMPMAX == RELMC_MAX_COMP && SEQ_NCOMPMAX == 256, "one lane of relmc_seq_event_comp_kernel per component");
+    static_assert(offsetof(relmc_seq_event_acc, onset_events) + sizeof(SeqEventComp) == sizeof(relmc_seq_event_acc) &&
+                  offsetof(relmc_seq_event_acc, involved_energy) - offsetof(relmc_seq_event_acc, onset_events) == offsetof(SeqEventComp, involved_energy),
+                  "SeqEventComp is the tail of relmc_seq_event_acc");
+    const std::string who(who_);
+    ev_acc->years = n_years;
+    if (n_years == 0) return RELMC_OK;
+    // the targets of the queued copies, and behind them a guard that waits for the stream on an early return, so that no copy is left
+    // pending into storage that has gone (it is destroyed first)
+    long long total = total_hint, dev_total = -1;
+    std::vector<SeqEventPart> part;
+    struct Drain { hipStream_t s; bool armed; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{ctx->stream, true};
+    auto& E = ctx->sq_events;
+    HIP_TRY(ctx, E.count.grow((size_t)n_years + 1));
+    HIP_TRY(ctx, E.offset.grow((size_t)n_years + 1));
+    long long* const dcount = E.count.get(); long long* const doff = E.offset.get();
+    // count[n_years] = 0, so that the scan of n_years + 1 counts leaves the total in offset[n_years]
+    (void)hipEventRecord(ctx->ev0, ctx->stream);
+    HIP_TRY(ctx, hipMemsetAsync(dcount + n_years, 0, sizeof(long long), ctx->stream));
+    hipLaunchKernelGGL(relmc_seq_event_count_kernel, dim3(n_years), dim3(256), 0, ctx->stream, curt, hpy, threshold, dcount);
+    hipLaunchKernelGGL(relmc_hl1_event_scan_kernel, dim3(1), dim3(256), 0, ctx->stream, (const long long*)dcount, (int64_t)n_years + 1, doff);
+    if (hipGetLastError() != hipSuccess) return fail(ctx, RELMC_ERR_HIP, who + ": launch failed");
+    if (total < 0) {
+        (void)hipEventRecord(ctx->ev1, ctx->stream);
+        HIP_TRY(ctx, hipMemcpyAsync(&total, doff + n_years, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, who + ": synchronisation failed");
+        *ms += ctx->last_kernel_ms;
+        (void)hipEventRecord(ctx->ev0, ctx->stream);
+    }
+    const int64_t blocks = total > 0 ? hl1_reduce_blocks(total) : 0;
+    const int64_t want = events_host ? std::min<int64_t>(total, events_cap) : 0;
+    unsigned long long* dhist = nullptr;
+    if (total > 0) {
+        HIP_TRY(ctx, E.list.grow((size_t)total));
+        HIP_TRY(ctx, E.part.grow((size_t)blocks));
+        HIP_TRY(ctx, E.comp.grow(1));
+        if (dur_hist_host) {
+            HIP_TRY(ctx, E.hist.grow((size_t)n_dur_bins));
+            dhist = E.hist.get();
+            HIP_TRY(ctx, hipMemsetAsync(dhist, 0, sizeof(unsigned long long) * n_dur_bins, ctx->stream));
+        }
+        hipLaunchKernelGGL(relmc_seq_event_fill_kernel, dim3(n_years), dim3(256), 0, ctx->stream, curt, masks, hpy, mw, threshold, (const long long*)doff,
+                           total, E.list.get());
+        hipLaunchKernelGGL(relmc_seq_event_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (const relmc_seq_event*)E.list.get(),
+                           (const long long*)(doff + n_years), total, dhist ? n_dur_bins : 0, dhist, E.part.get());
+        hipLaunchKernelGGL(relmc_seq_event_comp_kernel, dim3(1), dim3(256), 0, ctx->stream, (const relmc_seq_event*)E.list.get(), (const long long*)(doff + n_years), total,
+                           E.comp.get());
+        if (hipGetLastError() != hipSuccess) return fail(ctx, RELMC_ERR_HIP, who + ": launch failed");
+    }
+    (void)hipEventRecord(ctx->ev1, ctx->stream);
+    part.resize((size_t)blocks);
+    HIP_TRY(ctx, hipMemcpyAsync(&dev_total, doff + n_years, sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (total > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(part.data(), E.part.get(), sizeof(SeqEventPart) * blocks, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ev_acc->onset_events, E.comp.get(), sizeof(SeqEventComp), hipMemcpyDeviceToHost, ctx->stream));
+        if (dhist) HIP_TRY(ctx, hipMemcpyAsync(dur_hist_host, dhist, sizeof(int64_t) * n_dur_bins, hipMemcpyDeviceToHost, ctx->stream));
+        if (want > 0) HIP_TRY(ctx, hipMemcpyAsync(events_host, E.list.get(), sizeof(relmc_seq_event) * want, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (finish_timing(ctx) != RELMC_OK) return fail(ctx, RELMC_ERR_HIP, who + ": synchronisation failed");
+    drain.armed = false;
+    *ms += ctx->last_kernel_ms;
+    if (dev_total != total)
+        return fail(ctx, RELMC_ERR_HIP, who + ": " + std::to_string(dev_total) + " loss events on the device, " + std::to_string(total) + " in the annual indices");
+    for (const SeqEventPart& p : part) {                     // block by block: the order is part of the results
+        ev_acc->events += p.events; ev_acc->censored += p.censored; ev_acc->load_onset_events += p.load_onset;
+        ev_acc->sum_dur += p.sum_dur; ev_acc->sum_dur2 += p.sum_dur2; ev_acc->max_dur = std::max<int64_t>(ev_acc->max_dur, p.max_dur);
+        ev_acc->sum_energy += p.sum_energy; ev_acc->sum_energy2 += p.sum_energy2;
+        ev_acc->max_energy = std::max(ev_acc->max_energy, p.max_energy); ev_acc->max_peak = std::max(ev_acc->max_peak, p.max_peak);
+    }
     return RELMC_OK;
 }
 
@@ -133,71 +283,29 @@ int32_t relmc_seq_years(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int3
     if (!ctx) return RELMC_ERR_INVALID;
     if (!ctx->has_seq) return fail(ctx, RELMC_ERR_NO_CASE, "relmc_seq_years: relmc_seq_load has not been called");
     if (n_years < 0 || !acc_out || (n_years > 0 && !years_out)) return fail(ctx, RELMC_ERR_INVALID, "relmc_seq_years: bad arguments");
-    relmc_acc_zero(acc_out);
-    if (n_years == 0) return RELMC_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const relmc_solver_opts o = solver_opts_or_default(opts);
-    const int hpy = ctx->hseq.hpy;
-    // the device buffers of a step live in the context and only ever grow
-    const size_t nh = (size_t)n_years * hpy, words = nh * (size_t)ctx->hseq.mw;
-    auto& Q = ctx->sq;
-    // counts: [0, n) listed hours per year, [n, 2 n) contingency hours per year (pre-screen), n = the years the buffer was made for
-    if (Q.dm.grow(words) != hipSuccess || Q.hours.grow(nh) != hipSuccess || Q.curt.grow(nh) != hipSuccess || Q.counts.grow(2 * (size_t)n_years) != hipSuccess ||
-        Q.off.grow((size_t)n_years + 1) != hipSuccess || Q.year.grow(3 * (size_t)n_years) != hipSuccess)
-        return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: device allocation failed");
-    uint32_t* const dm = Q.dm.get(); uint16_t* const dhours = Q.hours.get(); uint32_t* const dcounts = Q.counts.get(); uint32_t* const doff = Q.off.get();
-    double* const dcurt = Q.curt.get(); double* const dyear = Q.year.get();
-    int rc = seq_sample(ctx, seed, first_year, n_years, dm);
-    if (rc) return rc;
-    std::vector<uint32_t> counts(n_years), ncont(n_years), off(n_years + 1, 0);
-    bool ok = hipMemsetAsync(dcurt, 0, nh * sizeof(double), ctx->stream) == hipSuccess;
-    // screen = 1 (relmc_screen.hip): the contingency hours are counted as before, but only the ones the zero-curtailment certificate does not cover
-    // -- at the hour's own load factor -- are listed for the interior point; a covered hour's curtailment stays the 0 it was set to above
-    const bool screen = screen_active(ctx, o);
-    uint32_t* const dncont = dcounts + Q.counts.size() / 2;
-    if (screen) ok = ok && screen_seq_compact(ctx, dm, n_years, dhours, dcounts, dncont) == RELMC_OK;
-    else hipLaunchKernelGGL(relmc_seq_compact_kernel, dim3(n_years), dim3(256), 0, ctx->stream, dm, hpy, ctx->hseq.mw, dhours, dcounts);
-    ok = ok && hipGetLastError() == hipSuccess && hipMemcpyAsync(counts.data(), dcounts, sizeof(uint32_t) * n_years, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
-         (!screen || hipMemcpyAsync(ncont.data(), dncont, sizeof(uint32_t) * n_years, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess) &&
-         hipStreamSynchronize(ctx->stream) == hipSuccess;
-    if (!ok) return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: compaction failed");
-    int64_t certified = 0;
-    for (int y = 0; y < n_years; ++y) {
-        off[y + 1] = off[y] + counts[y];
-        years_out[y].n_contingency = screen ? ncont[y] : counts[y];
-        if (screen) certified += (int64_t)ncont[y] - (int64_t)counts[y];
-    }
-    const int64_t nlp = off[n_years];
-    double ms = 0.0;
-    if (screen) { float t = 0.f; if (hipEventElapsedTime(&t, ctx->screen_ev0, ctx->screen_ev1) == hipSuccess) ms += t; }      // the certificate's pre-pass (the stream was synchronised above)
-    if (nlp > 0) {
-        if (hipMemcpyAsync(doff, off.data(), sizeof(uint32_t) * (n_years + 1), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: H2D failed");
-        EvalArgs a = make_args(o);
-        a.fail_threshold = curtail_threshold;
-        a.n = nlp; a.seq_masks = dm; a.seq_offsets = doff; a.seq_hours = dhours; a.load_factors = ctx->dlf.get(); a.curt = dcurt;
-        a.seq_nyears = n_years; a.seq_hpy = hpy;
-        Collected c;
-        rc = eval_collect(ctx, "relmc_seq_years", 2, a, 0, a.n, acc_out, c);
-        if (rc) return rc;
-        ms += c.ms;
-        RetryOut ro;                                                   // hours the primary elimination order did not converge on
-        const ScaleFn scale = [&](unsigned long long u) { return ctx->hlf[(size_t)(u % (unsigned long long)hpy)]; };
-        rc = fail_retry(ctx, o, curtail_threshold, &scale, ro, &ms, c.known());
-        if (rc) return rc;
-        acc_add_retry(acc_out, ro, ctx->ncomp, curtail_threshold);
-        for (size_t r = 0; r < ro.size(); ++r) {
-            const RetryUnit u = ro[r];
-            if (hipMemcpy(dcurt + u.unit, &u.dns, sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: H2D failed");
-        }
-    }
-    acc_out->n += certified; acc_out->n_screened += certified;
-    hipLaunchKernelGGL(relmc_seq_annual_kernel, dim3(n_years), dim3(256), 0, ctx->stream, dcurt, hpy, curtail_threshold, dyear);
-    std::vector<double> yr((size_t)3 * n_years);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(yr.data(), dyear, sizeof(double) * 3 * n_years, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(ctx, RELMC_ERR_HIP, "relmc_seq_years: annual indices failed");
-    for (int y = 0; y < n_years; ++y) { years_out[y].ens = yr[3 * y]; years_out[y].dlc = yr[3 * y + 1]; years_out[y].nlc = yr[3 * y + 2]; }
+    return seq_years_step(ctx, "relmc_seq_years", seed, first_year, n_years, opts, curtail_threshold, years_out, acc_out);
+}
+
+// Loss events of the years above: relmc_seq_years' step, then count -> offsets -> fill -> reduce on the curtailment and the masks it left
+// on the device.  The years' nlc are the event counts, so the list is sized without reading the device's count back.
+int32_t relmc_seq_events(relmc_ctx* ctx, uint64_t seed, uint64_t first_year, int32_t n_years, const relmc_solver_opts* opts,
+                         double curtail_threshold, relmc_seq_year* years_out, relmc_acc* acc_out, relmc_seq_event_acc* ev_acc,
+                         int32_t n_dur_bins, int64_t* dur_hist_host, int64_t events_cap, relmc_seq_event* events_host)
+{
+    if (!ctx) return RELMC_ERR_INVALID;
+    if (!ctx->has_seq) return fail(ctx, RELMC_ERR_NO_CASE, "relmc_seq_events: relmc_seq_load has not been called");
+    if (n_years < 0 || !acc_out || !ev_acc || (n_years > 0 && !years_out) || (dur_hist_host && (n_dur_bins < 1 || n_dur_bins > 4096)) || events_cap < 0)
+        return fail(ctx, RELMC_ERR_INVALID, "relmc_seq_events: bad arguments");
+    seq_events_zero(ev_acc, n_dur_bins, dur_hist_host);      // here for every return below; seq_events_device adds to them
+    int rc = seq_years_step(ctx, "relmc_seq_events", seed, first_year, n_years, opts, curtail_threshold, years_out, acc_out);
+    if (rc || n_years == 0) return rc;
+    int64_t total = 0;
+    for (int y = 0; y < n_years; ++y) total += (int64_t)years_out[y].nlc;
+    double ms = ctx->last_kernel_ms;
+    rc = seq_events_device(ctx, "relmc_seq_events", ctx->sq.curt.get(), ctx->sq.dm.get(), n_years, ctx->hseq.hpy, ctx->hseq.mw, curtail_threshold, total,
+                           ev_acc, n_dur_bins, dur_hist_host, events_cap, events_host, &ms);
     ctx->last_kernel_ms = ms;
-    return RELMC_OK;
+    return rc;
 }
 
 void relmc_seq_opts_default(relmc_seq_opts* o)

@@ -27,6 +27,8 @@ MAX_SIM_YEARS = 4000         # seqMain.m:39
 
 
 SeqYear = _abi.SeqYear
+EVENT_DTYPE = np.dtype(_abi.SeqEvent)     # the structured view of relmc_seq_event: year, start_hour, duration, censored, energy_mwh, peak_mw, onset[8], involved[8]
+_YEAR_DTYPE = np.dtype([("ens", "<f8"), ("dlc", "<f8"), ("nlc", "<f8"), ("n_contingency", "<i8")])
 
 
 def seqmeantime() -> np.ndarray:
@@ -50,10 +52,36 @@ def _bind(L):
     L.relmc_seq_mcsimulation.argtypes = [C.c_void_p, u8p, dp, C.c_int64, C.POINTER(_abi.SolverOpts), dp, dp, i32p, i32p]
     L.relmc_seq_years.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(_abi.SolverOpts), C.c_double,
                                   C.POINTER(SeqYear), C.POINTER(_abi.Acc)]
+    L.relmc_seq_events.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(_abi.SolverOpts), C.c_double,
+                                   C.POINTER(SeqYear), C.POINTER(_abi.Acc), C.POINTER(_abi.SeqEventAcc), C.c_int32, _abi.c_int64_p,
+                                   C.c_int64, C.POINTER(_abi.SeqEvent)]
+    L.relmc_seq_events.restype = C.c_int32
     L.relmc_seq_opts_default.argtypes = [C.POINTER(_abi.SeqOpts)]
     L.relmc_seq_opts_default.restype = None
     L.relmc_seq_run.argtypes = [C.c_void_p, C.POINTER(_abi.SeqOpts), C.POINTER(_abi.SeqResult)]
     L.relmc_seq_run.restype = C.c_int32
+
+
+def _event_args(who, seed, first_year, n_years, curtail_threshold, dur_bins, events_cap):
+    """The argument rules of seq_events (checked before the library is called): integers in the C entry's ranges, a finite threshold."""
+    seed, first_year, n_years, dur_bins, events_cap = int(seed), int(first_year), int(n_years), int(dur_bins), int(events_cap)
+    if not 0 <= seed < 2 ** 64 or not 0 <= first_year < 2 ** 64:
+        raise ValueError(f"{who}: seed and first_year must lie in [0, 2^64)")
+    if not 0 <= n_years < 2 ** 31:
+        raise ValueError(f"{who}: n_years must lie in [0, 2^31), not {n_years}")
+    if not np.isfinite(float(curtail_threshold)):
+        raise ValueError(f"{who}: curtail_threshold must be finite, not {curtail_threshold}")
+    if not 1 <= dur_bins <= 4096:
+        raise ValueError(f"{who}: dur_bins must lie in [1, 4096], not {dur_bins}")
+    if events_cap < 0:
+        raise ValueError(f"{who}: events_cap must not be negative, not {events_cap}")
+    return seed, first_year, n_years, dur_bins, events_cap
+
+
+def mask_components(words) -> list[int]:
+    """Component indices (0-based, ascending) of an event's onset / involved words."""
+    w = np.asarray(words, dtype=np.uint32)
+    return [32 * q + b for q in range(w.size) for b in range(32) if (int(w[q]) >> b) & 1]
 
 
 class SeqEngine:
@@ -113,6 +141,26 @@ class SeqEngine:
                                                yrs, C.byref(acc)), "relmc_seq_years")
         raw = np.frombuffer(yrs, dtype=np.dtype([("ens", "<f8"), ("dlc", "<f8"), ("nlc", "<f8"), ("n_contingency", "<i8")]), count=int(n_years))
         return raw["ens"].copy(), raw["dlc"].copy(), raw["nlc"].copy(), raw["n_contingency"].copy(), acc
+
+    def seq_events(self, seed: int, first_year: int, n_years: int, mpopt=None, curtail_threshold: float = CURTAIL_THRESHOLD,
+                   dur_bins: int = 168, events_cap: int = 0) -> "SeqEventResult":
+        """The loss events of seq_years' years (same arguments, same years, byte for byte): how often interruptions of the composite
+        system occur, how long they last, what energy and peak each costs and which outages set it off (relmc_seq_events).  duration_hist
+        has dur_bins bins (the last one counts that many hours or more); `events` holds the first events_cap events in (year, start_hour)
+        order."""
+        seed, first_year, n_years, dur_bins, events_cap = _event_args("seq_events", seed, first_year, n_years, curtail_threshold, dur_bins, events_cap)
+        o = mpopt if mpopt is not None else api.mpoption()
+        yrs = (SeqYear * n_years)()
+        acc = _abi.Acc(); ev_acc = _abi.SeqEventAcc()
+        hist = np.zeros(dur_bins, dtype=np.int64)
+        ev = np.zeros(events_cap, dtype=EVENT_DTYPE)
+        self.eng._check(self.L.relmc_seq_events(self.eng._h, seed, first_year, n_years, C.byref(o), float(curtail_threshold), yrs, C.byref(acc),
+                                                C.byref(ev_acc), dur_bins, hist.ctypes.data_as(_abi.c_int64_p), events_cap,
+                                                ev.ctypes.data_as(C.POINTER(_abi.SeqEvent)) if events_cap else None), "relmc_seq_events")
+        raw = np.frombuffer(yrs, dtype=_YEAR_DTYPE, count=n_years) if n_years else np.zeros(0, dtype=_YEAR_DTYPE)
+        return SeqEventResult(n_years=n_years, ncomp=self.eng.case.ncomp, ens=raw["ens"].copy(), dlc=raw["dlc"].copy(), nlc=raw["nlc"].copy(),
+                              n_contingency=raw["n_contingency"].copy(), acc=acc, ev_acc=ev_acc, duration_hist=hist,
+                              events=ev[:min(int(ev_acc.events), events_cap)])
 
     # seqMain.m:85-262
     def seqMain(self, max_sim_years: int = MAX_SIM_YEARS, cov_threshold: float = COV_THRESHOLD,
@@ -225,3 +273,86 @@ class SeqResult:
         from scipy.io import savemat
         savemat(path, dict(results_year=self.results_year, results_cum=self.results_cum,
                            nodal_eens_avg=self.nodal_eens_avg[None, :], comp_importance=self.comp_importance[:, None]))
+
+
+@dataclass
+class SeqEventResult:
+    """SeqEngine.seq_events' result.  A loss event is a maximal run of consecutive loss hours (system curtailment above the threshold) inside
+    one simulated year; one that reaches the year's last hour ends there and counts as censored.  So the events of a year number its nlc
+    and their durations sum to its dlc."""
+    n_years: int
+    ncomp: int
+    ens: np.ndarray                   # the years of seq_years, byte for byte
+    dlc: np.ndarray
+    nlc: np.ndarray
+    n_contingency: np.ndarray
+    acc: _abi.Acc = field(repr=False, default=None)
+    ev_acc: _abi.SeqEventAcc = field(repr=False, default=None)
+    duration_hist: np.ndarray = field(default_factory=lambda: np.zeros(0, dtype=np.int64))   # [d - 1] = events of d hours, last bin: that long or longer
+    events: np.ndarray = field(default_factory=lambda: np.zeros(0, dtype=EVENT_DTYPE))       # the first events_cap events, (year, start_hour) order
+
+    @property
+    def n_events(self) -> int:
+        return int(self.ev_acc.events)
+
+    @property
+    def lolf(self) -> float:
+        """Loss events per simulated year (occ/yr); NaN without a year."""
+        return self.n_events / self.n_years if self.n_years else float("nan")
+
+    @property
+    def mean_duration(self) -> float:
+        """Hours per event, the reference's "hr/occ"; NaN without an event."""
+        return self.ev_acc.sum_dur / self.n_events if self.n_events else float("nan")
+
+    @property
+    def mean_energy(self) -> float:
+        """MWh per event; NaN without an event."""
+        return self.ev_acc.sum_energy / self.n_events if self.n_events else float("nan")
+
+    @property
+    def max_duration(self) -> int:
+        return int(self.ev_acc.max_dur)
+
+    def duration_quantile(self, q: float) -> float:
+        """Smallest duration d (hours) with P(D <= d) >= q, read off the histogram; NaN if it falls into the overflow bin (or there is no event)."""
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(f"duration_quantile: q must lie in [0, 1], not {q}")
+        total = int(self.duration_hist.sum())
+        if total == 0:
+            return float("nan")
+        d = int(np.searchsorted(np.cumsum(self.duration_hist), q * total, side="left"))      # 0-based bin
+        return float("nan") if d >= self.duration_hist.size - 1 else float(max(d, 0) + 1)
+
+    def top_initiators(self, k: int = 5, numGenerators: int = 33):
+        """[(type, id 1-based, events initiated, MWh of those events)] of the k components whose outages set off the most energy
+        (components that initiated no event are not listed)."""
+        if int(k) < 0:
+            raise ValueError(f"top_initiators: k must not be negative, not {k}")
+        en = np.array(self.ev_acc.onset_energy[:self.ncomp]); cnt = np.array(self.ev_acc.onset_events[:self.ncomp])
+        order = np.argsort(-en, kind="stable")[:int(k)]
+        return [(("Gen", int(c) + 1) if c < numGenerators else ("Line", int(c) - numGenerators + 1)) + (int(cnt[c]), float(en[c]))
+                for c in order if cnt[c] > 0]
+
+    def report(self, numGenerators: int = 33) -> str:
+        """Frequency and duration of the interruptions in the style of SeqResult.report."""
+        a = self.ev_acc
+        L = ["--- LOSS EVENTS (%d simulated years) ---" % self.n_years,
+             "LOLF (Loss of Load Frequency):       %.4f occ/yr" % self.lolf,
+             "Mean duration:                       %.4f hr/occ" % self.mean_duration,
+             "Mean energy:                         %.4f MWh/occ" % self.mean_energy,
+             "Longest event: %d hr | Largest event: %.4f MWh | Highest peak: %.4f MW" % (self.max_duration, a.max_energy, a.max_peak),
+             "Median / 90 %% duration:              %s / %s hr" % (_fmt_hours(self.duration_quantile(0.5)), _fmt_hours(self.duration_quantile(0.9))),
+             "Events cut at a year's end: %d | Events without a new outage (load rise): %d" % (a.censored, a.load_onset_events),
+             "", "--- INITIATING OUTAGES ---"]
+        top = self.top_initiators(5, numGenerators)
+        if top:
+            L.append("Top 5 Components by Energy of the Events They Set Off:")
+            L += ["  %s %2d: %d events, %.4f MWh" % t for t in top]
+        else:
+            L.append("No loss event recorded to analyze initiating outages.")
+        return "\n".join(L)
+
+
+def _fmt_hours(v: float) -> str:
+    return "n/a" if v != v else "%d" % int(v)
